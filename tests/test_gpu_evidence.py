@@ -554,7 +554,7 @@ def test_bench_world2(launcher, model_root):
     same code with the default backend."""
     env = dict(os.environ, SMPLFIT_SYNTH_ROOT=model_root)
     common = ['--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '256', '--no-cpu-baseline',
-              '--backend', 'gloo', '--oversubscribe']
+              '--backend', 'gloo', '--oversubscribe', '--full']
     if launcher == 'self':
         cmd = [sys.executable, 'bench.py'] + common
     else:
@@ -567,6 +567,30 @@ def test_bench_world2(launcher, model_root):
     assert out['n_gpus'] == 2 and out['nccl_world_size'] == 2 and out['scaling'] == 'weak'
     assert out['config']['batch_per_gpu'] == 256 and out['value'] > 0
     assert 'all_gather_into_tensor' in out['collective']
+
+
+def test_bench_plain_line_and_dump(model_root, tmp_path):
+    """A plain `bench.py` run prints the headline only (the roofline, baseline and other legs are `--full`'s) and
+    `--dump-outputs` writes what the last timed step returned: float32 arrays of the batch, the same in two runs."""
+    env = dict(os.environ, SMPLFIT_SYNTH_ROOT=model_root)
+    outs = []
+    for i in range(2):
+        d = tmp_path / f'run{i}'
+        cmd = [sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--batch', '256', '--dump-outputs', str(d)]
+        p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
+        assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]
+        out = json.loads(lines[0])
+        assert out['unit'] == 'fits/s' and out['higher_is_better'] is True and out['dtype'] == 'f32'
+        assert out['steps'] == 3 and out['ms_per_step'] > 0
+        assert abs(out['value'] - 256 / (out['ms_per_step'] * 1e-3)) < 0.02 * out['value']
+        assert not {'roofline', 'cpu_baseline', 'other_configs', 'multi_gpu'} & set(out)
+        outs.append({f.stem: np.load(f) for f in sorted(d.glob('*.npy'))})
+    assert {'pose_rotvecs', 'shape_betas', 'trans'} <= set(outs[0]) and set(outs[0]) == set(outs[1])
+    assert outs[0]['pose_rotvecs'].shape == (256, 72) and outs[0]['shape_betas'].shape == (256, 10)
+    for k, a in outs[0].items():
+        assert a.dtype == np.float32 and a.shape[0] == 256 and np.isfinite(a).all(), k
+        assert np.array_equal(a, outs[1][k]), k
 
 
 def test_bench_refuses_missing_devices():
@@ -582,7 +606,7 @@ def test_bench_world1_rccl_gather(model_root):
     GPU: this is the part of the collective path that can run here)."""
     env = dict(os.environ, SMPLFIT_SYNTH_ROOT=model_root)
     cmd = [sys.executable, 'bench.py', '--steps', '2', '--warmup', '1', '--batch', '512', '--no-cpu-baseline',
-           '--collective-always']
+           '--collective-always', '--full']
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
     assert p.returncode == 0 and len(lines) == 1, p.stdout[-2000:] + p.stderr[-3000:]

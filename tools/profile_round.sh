@@ -16,6 +16,6 @@ cd $R
 python tools/profile_collect.py $OUT $TAG
 # the default line LAST, with this build's traffic figures in place (bench.py reads profiles/pmc_traffic.json)
 cp $OUT/out/pmc_traffic.json profiles/pmc_traffic.json
-python bench.py --steps 20 --warmup 5 > $OUT/out/${TAG}_bench_default.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $OUT/out/${TAG}_bench_default.json 2>/dev/null
 # keep the merge-back small: the raw traces stay on the box
 rm -rf $OUT/trace1 $OUT/trace2 $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE $OUT/pmc_MFMA
