@@ -751,7 +751,7 @@ __global__ __launch_bounds__(64 * kBW) __attribute__((amdgpu_waves_per_eu((NJ ==
   const uint32_t ul = (uint32_t)lane;
   const size_t cstr = (size_t)Vp * 64;
   float sb[3] = {0.f, 0.f, 0.f};  // Sb = sum_v b_v = the sum of the moments: the skinning weights of a vertex sum to
-                                  // one (bm_applies checks it), so the residual sum needs no accumulators of its own
+                                  // one (route_of checks it), so the residual sum needs no accumulators of its own
   const int ps = sv.piece_start[share * sv.mult], np = sv.piece_start[(share + 1) * sv.mult] - ps;
   {
     // The wave's step sequence: the vertices of every piece in turn, plus one step on the first padding slot (zero
@@ -1331,7 +1331,7 @@ __global__ __launch_bounds__(64 * kProWaves) void k_prologue_bm(DevModel m, Prol
 //   phase 3  relative rotations and the log map (:523-539), a wave per joint; pose (and the optional orientation
 //            outputs) through an LDS tile so that the caller's instance-major rows are written coalesced.
 // The arithmetic of every value is that of sf::refine_stage on the same inputs.  grid Mp / 64, block 64 * kRefWaves.
-// Applies with k_prologue_bm (ws.GT valid), models of at most 32 joints (the LDS budget) — refine_bm_applies.
+// Applies with k_prologue_bm (ws.GT valid), models of at most 32 joints (the LDS budget) — route_of.
 // ------------------------------------------------------------------------------------------------
 constexpr int kRefPitch = 65;  // LDS pitch of the transposed joint arrays (the fill walks k at a fixed instance)
 constexpr int kRefParts = 4;   // adjustable parts of one group at most (a wave keeps their part sums in registers)
@@ -1370,7 +1370,7 @@ __global__ __launch_bounds__(64 * kRefWaves) void k_refine_bm(DevModel m, Refine
   if (a.final_adjust) {
     // the wave's adjustable parts: their part sums — the rows of the last LBS pass in table order (k_psum_combine's
     // order; four rows requested together) — and their joints at the final solve
-    // the wave's parts in level order (at most kRefParts: refine_bm_applies)
+    // the wave's parts in level order (at most kRefParts: route_of)
     for (int u = 0, ai = 0; u < kRefParts; ++u) {
       while (ai < nadj && rg.wave[ai] != wave) ++ai;
       mine[u] = ai < nadj ? ai++ : -1;
@@ -1604,7 +1604,7 @@ __global__ __launch_bounds__(64 * kRefWaves) void k_refine_bm(DevModel m, Refine
 // fits every part's rotation (Kabsch on the part's joints, swing + twist of a bone part, or the projection of the
 // cross-covariance of its vertices: the code of sf::joint_stage per lane), phase 2 gives the toes their feet's
 // rotations, composes with the previous ones and writes ws.GT rows (coalesced).  k_prologue_bm follows.
-// grid Mp / 64, block 64 * kRefWaves.  Applies with k_refine_bm (rot_bm_applies).
+// grid Mp / 64, block 64 * kRefWaves.  Applies with k_refine_bm (route_of).
 // ------------------------------------------------------------------------------------------------
 constexpr int kRotJoints = 4;   // joints a wave fits per round (their part sums and previous rotations in registers)
 constexpr int kRotMaxJ = 64;    // (three 64-lane requests cover a row of 3 J joint coordinates)
@@ -1842,7 +1842,7 @@ __global__ __launch_bounds__(64 * kRefWaves) void k_rotations_bm_rounds(DevModel
 #pragma unroll
     for (int k = 0; k < 9; ++k) GT[(size_t)(j * 9 + k) * pitch] = G[k];
   };
-  // the wave's toes (at most two: rot_bm_applies): their previous rotations are requested now, used behind the last barrier
+  // the wave's toes (at most two: route_of): their previous rotations are requested now, used behind the last barrier
   int toej[2] = {-1, -1};
   float Gtoe[2][9];
   for (int j = wave, n = 0; j < J; j += kRefWaves)

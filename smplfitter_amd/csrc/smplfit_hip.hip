@@ -13,7 +13,7 @@
 //   k_lbs_partsum          K5  vertices at the solved shape fused with the part sums of the next rotation pass
 //   k_refine_epilogue      K6  dependent rotation refinement + relative rotations + log map
 //   k_forward_joint, k_lbs_partsum<MODE 2>   BodyModel.forward;  k_scale_trans  known-shape alignment
-// Batch-major kernels (LANE = INSTANCE; the default vertex block where they apply, see bm_applies): k_layout_targets,
+// Batch-major kernels (LANE = INSTANCE; the default vertex block where they apply, see route_of): k_layout_targets,
 //   k_mean_finish, k_template_partsum_bm, k_residual_bm, k_pair_gram_bm, k_gram_combine_bm, k_lbs_partsum_bm,
 //   k_psum_combine, k_regress_joints_bm, k_transpose_targets (joint rows) — grid = (vertex group | unit chunk) x
 //   instance blocks of 64; k_transfer_bm / k_transfer_rows: topology transfer (BodyConverter).
@@ -435,11 +435,7 @@ struct Tuning {
   bool bm = true;          // SMPLFIT_BM=0: wave-per-instance vertex kernels everywhere
   bool gemm_f32 = false;   // SMPLFIT_GEMM=f32: fp32-MFMA posedirs GEMM instead of the split-bf16 one
   bool pair_form = false;  // SMPLFIT_SHAPE_FORM=pair: pair-Gram form on the wave-per-instance path
-  bool k0_two = true;      // SMPLFIT_K0_TWO=0: K0 stages the whole row (one workgroup per CU)
   int chunks = 0;          // SMPLFIT_CHUNKS=1..4: concurrent batch chunks of one fit call (0: by model, see chunk_plan)
-  int gemm_nchunk = 0;     // SMPLFIT_GEMM_NCHUNK: column-tile chunks of the split-bf16 GEMM (0 = automatic)
-  int gemm_lds_kb = 0;     // SMPLFIT_GEMM_LDS_KB: LDS request of the fp32 A-stationary GEMM (occupancy experiments)
-  bool lbs_all_last = false;  // SMPLFIT_LBS_LAST=all: the last part sums of a fit over every used part (A/B of the adjustable-parts pass)
   int stage_half_b = 2048; // SMPLFIT_STAGE_HALF_B: smallest batch whose per-instance stages run two instances per wave (J <= 32)
   int fine_b = sf::kFineMaxBatch;  // SMPLFIT_FINE_B: largest batch that takes the fine cell tables (0: none; at most sf::kFineMaxBatch)
   bool bm_known_pose = true;  // SMPLFIT_BM_KNOWN_POSE=0: smplfit_shape_solve_ex_f32 on the wave-per-instance kernels (A/B)
@@ -447,15 +443,12 @@ struct Tuning {
   bool bm_scale = true;    // SMPLFIT_BM_SCALE=0: fit(scale_target / scale_fit) on the wave-per-instance kernels (A/B)
   bool bm_known_shape = true;  // SMPLFIT_BM_KNOWN_SHAPE=0: fit_with_known_shape on the wave-per-instance kernels (A/B)
   bool bm_weighted = true; // SMPLFIT_BM_WEIGHTED=0: fits with vertex weights on the wave-per-instance kernels (A/B)
-  int bm_slots = 4096;     // SMPLFIT_BM_SLOTS: resident waves a batch-major vertex pass is dealt for (share-count choice)
-  int gen_flush = 0;       // SMPLFIT_GEN_FLUSH: vertices between two fp64 additions of the general accumulate kernel's fp32 sums (0: 2048; a scaled iteration: every blend pass)
+  int share_slots = 4096;  // SMPLFIT_BM_SLOTS: resident waves a batch-major vertex pass is dealt for (share-count choice)
   bool gen_mfma = true;    // SMPLFIT_GEN_MFMA=0: the general path's vertex block on the vector ALUs (k_gen_accum) instead of the matrix cores (A/B)
   bool rot_bm = true;      // SMPLFIT_ROT_BM=0: the part rotations as the wave-per-instance k_joint_stage behind a part-sum combine instead of k_rotations_bm (A/B)
   bool refine_bm = true;   // SMPLFIT_REFINE_BM=0: the refinement + epilogue as the wave-per-instance k_refine_epilogue behind a part-sum combine instead of k_refine_bm (A/B)
   bool prologue_bm = true; // SMPLFIT_PROLOGUE_BM=0: the shape prologue inside k_joint_stage + the joint-row transpose instead of k_prologue_bm (A/B)
   bool solve_bm = true;    // SMPLFIT_SOLVE_BM=0: normal-equation combine + wave-per-instance solve as two launches instead of k_solve_bm (A/B)
-  int bm_lds_kb = 0;       // SMPLFIT_BM_LDS_KB: LDS request of the two batch-major vertex passes padded to this (54: three
-                           // workgroups per CU instead of four, which leaves registers / LDS for another chunk's small kernels)
 };
 // The current options: an immutable snapshot behind an atomic pointer.  smplfit_reload_options() publishes a new
 // snapshot; a launch that is reading the old one on another thread keeps a valid object (snapshots are never freed:
@@ -468,11 +461,7 @@ Tuning read_tuning() {
   if (const char* e = env("SMPLFIT_BM")) t.bm = e[0] != '0';
   if (const char* e = env("SMPLFIT_GEMM")) t.gemm_f32 = e[0] == 'f';
   if (const char* e = env("SMPLFIT_SHAPE_FORM")) t.pair_form = std::string(e) == "pair";
-  if (const char* e = env("SMPLFIT_K0_TWO")) t.k0_two = e[0] != '0';
   if (const char* e = env("SMPLFIT_CHUNKS")) t.chunks = std::min(std::max(atoi(e), 1), 4);
-  if (const char* e = env("SMPLFIT_GEMM_NCHUNK")) t.gemm_nchunk = std::max(1, atoi(e));
-  if (const char* e = env("SMPLFIT_GEMM_LDS_KB")) t.gemm_lds_kb = atoi(e);
-  if (const char* e = env("SMPLFIT_LBS_LAST")) t.lbs_all_last = e[0] == 'a';
   if (const char* e = env("SMPLFIT_BM_KNOWN_POSE")) t.bm_known_pose = e[0] != '0';
   if (const char* e = env("SMPLFIT_BM_FORWARD")) t.bm_forward = e[0] != '0';
   if (const char* e = env("SMPLFIT_BM_SCALE")) t.bm_scale = e[0] != '0';
@@ -480,14 +469,12 @@ Tuning read_tuning() {
   if (const char* e = env("SMPLFIT_BM_WEIGHTED")) t.bm_weighted = e[0] != '0';
   if (const char* e = env("SMPLFIT_FINE_B")) t.fine_b = std::min(std::max(atoi(e), 0), sf::kFineMaxBatch);
   if (const char* e = env("SMPLFIT_STAGE_HALF_B")) t.stage_half_b = std::max(atoi(e), 1);
-  if (const char* e = env("SMPLFIT_BM_SLOTS")) t.bm_slots = std::min(std::max(atoi(e), 256), 16384);
+  if (const char* e = env("SMPLFIT_BM_SLOTS")) t.share_slots = std::min(std::max(atoi(e), 256), 16384);
   if (const char* e = env("SMPLFIT_GEN_MFMA")) t.gen_mfma = e[0] != '0';
-  if (const char* e = env("SMPLFIT_GEN_FLUSH")) t.gen_flush = std::max(atoi(e), 0);
   if (const char* e = env("SMPLFIT_SOLVE_BM")) t.solve_bm = e[0] != '0';
   if (const char* e = env("SMPLFIT_PROLOGUE_BM")) t.prologue_bm = e[0] != '0';
   if (const char* e = env("SMPLFIT_REFINE_BM")) t.refine_bm = e[0] != '0';
   if (const char* e = env("SMPLFIT_ROT_BM")) t.rot_bm = e[0] != '0';
-  if (const char* e = env("SMPLFIT_BM_LDS_KB")) t.bm_lds_kb = std::min(std::max(atoi(e), 0), 64);
   return t;
 }
 void load_tuning() {
@@ -507,30 +494,6 @@ const Tuning& tune() {
   return *t;
 }
 
-// The unit-weight vertex block has two implementations:
-//   direct (default): k_shape_accum accumulates G, r, Sb per vertex (VALU-bound);
-//   pair  (SMPLFIT_SHAPE_FORM=pair): k_residual + k_pair_gram — 4x fewer per-vertex FLOPs, parity-tested,
-//          but not faster on wave-per-instance kernels (the batch-major path always uses the pair form).
-bool use_pair_form() { return tune().pair_form; }
-
-// Batch-major vertex kernels: the default whenever they apply (bm_applies); SMPLFIT_BM=0 selects the
-// wave-per-instance kernels everywhere (they also serve every other configuration).
-bool use_bm() { return tune().bm; }
-// Small vertex subsets stay on the wave-per-instance kernels: the pair-Gram and combine passes cost the
-// same per instance whatever V is (measured at V = 1024, B = 16384: 4.15 M fits/s batch-major vs 4.63 M).
-bool bm_applies(const DevModel& d) {
-  // (normalised skinning weights are checked where the handle is at hand: bm_applies(const smplfit_handle*))
-  // Vp > V: the batch-major loops run their out-of-range steps on the first padding slot
-  // (below ~1000 vertices the prologue of a wave outweighs its vertex work)
-  // (KW == 8 since round 5: pieces of up to eight joints, two waves per SIMD — 5-8 skinning weights per vertex)
-  // (16 betas ± the kid unknown since round 5 as well: the same kernels at two waves per SIMD)
-  return use_bm() && (d.KW == 4 || d.KW == 8) && sf::bm_shape_count(d.S) && d.bm_tables && d.V >= 1024 && d.Vp > d.V;
-}
-
-// The batch-major residual kernel derives sum_v b_v from the per-joint moments: exact only when every vertex's
-// skinning weights sum to one (sf::HostTables::wsum_dev) — other models stay on the wave-per-instance kernels.
-bool bm_applies(const smplfit_handle* h) { return bm_applies(h->d) && h->t.wsum_dev <= 1e-5f; }
-
 // joint rows of the current rotations, instance-innermost, for k_pair_gram_bm
 void launch_jd_transpose(const DevModel& d, const Workspace& ws, int B, hipStream_t st) {
   const int Mp = (int)align_up((size_t)B, 128), Ns = d.J * sf::jd_stride(d.S), Np = (int)align_up((size_t)Ns, 64);
@@ -544,7 +507,7 @@ ShareView share_view(const smplfit_handle* h, int kind, int B) {
   const int nblocks = (int)align_up((size_t)B, 128) / 64, idx = share_index(kind, B);
   ShareView sv = h->views[idx];
   sv.fine = idx >= sf::kShareFine;
-  sv.mult = sf::pick_share_mult(h->t, idx, nblocks, tune().bm_slots);
+  sv.mult = sf::pick_share_mult(h->t, idx, nblocks, tune().share_slots);
   return sv;
 }
 dim3 share_grid(const ShareView& sv, int Mp) { return dim3(Mp / 64, sv.ncells / sv.mult / kBW); }
@@ -553,9 +516,10 @@ void launch_psum_combine(const DevModel& d, const ShareView& sv, const Workspace
   else hipLaunchKernelGGL(k_psum_combine, dim3((B + 255) / 256, d.J), dim3(256), 0, st, d, sv, ws, B, Mp);
 }
 
-// part sums of the centred targets against the template + their combine (the first rotation estimate)
-void launch_template_partsum_bm(const smplfit_handle* h, const Workspace& ws, int B, hipStream_t st, bool weighted = false,
-                                bool combine = true) {
+// part sums of the centred targets against the template + their combine (the first rotation estimate); combine:
+// Route::psum_combine
+void launch_template_partsum_bm(const smplfit_handle* h, const Workspace& ws, int B, hipStream_t st, bool weighted,
+                                bool combine) {
   const DevModel& d = h->d;
   const int Mp = (int)align_up((size_t)B, 128);
   const ShareView sv = share_view(h, sf::kShareLbsUsed, B);
@@ -567,7 +531,7 @@ void launch_template_partsum_bm(const smplfit_handle* h, const Workspace& ws, in
 // One-pass target layout of the batch-major path (k_layout_targets, k_mean_finish, k_template_partsum_bm):
 // ws.tT, ws.mean, ws.tjc and the template part sums ws.psum.  ws.resP serves as the slab-sum scratch.
 void launch_layout_bm(const smplfit_handle* h, const float* tv, const float* tj, const Workspace& ws, int B, hipStream_t st,
-                      const float* vw = nullptr, bool template_sums = true, bool combine = true) {
+                      const float* vw, bool template_sums, bool combine) {
   const DevModel& d = h->d;
   if (vw)  // vertex weights: their stream first (the template part sums below read it)
     hipLaunchKernelGGL(k_layout_weights, dim3((d.V + 63) / 64 + 1, (int)align_up((size_t)B, 128) / 64), dim3(256), 0, st, d, vw,
@@ -588,10 +552,10 @@ void launch_residual_bm_s(const smplfit_handle* h, const Workspace& ws, int B, h
   const ShareView sv = share_view(h, sf::kShareResidual, B);
   if ((which & 1) && d.KW == 8)
     hipLaunchKernelGGL((k_residual_bm<S, 8>), share_grid(sv, Mp), dim3(64 * kBW),
-                       std::max(kResidualLds, (size_t)tune().bm_lds_kb * 1024), st, d, sv, ws, B, Mp);
+                       kResidualLds, st, d, sv, ws, B, Mp);
   else if (which & 1)
     hipLaunchKernelGGL((k_residual_bm<S>), share_grid(sv, Mp), dim3(64 * kBW),
-                       std::max(kResidualLds, (size_t)tune().bm_lds_kb * 1024), st, d, sv, ws, B, Mp);
+                       kResidualLds, st, d, sv, ws, B, Mp);
   if (which & 2) {
     hipLaunchKernelGGL((k_pair_gram_bm<S>), dim3(pair_gram_workgroups(d.J, d.jt.np), Mp / 64), dim3(64 * kPgWaves), 0, st, d, ws, B, Mp);
   }
@@ -640,33 +604,33 @@ void launch_accum_w_bm(const smplfit_handle* h, const Workspace& ws, int B, hipS
 // joints of the next rotation pass regressed from them into ws.rjreg.  adj_only (the last pass of a fit with target
 // joints): the part sums feed the dependent refinement alone, which reads them at the adjustable parts
 // (bodyfitter.py:1505-1517) — only those parts' slots are visited, the other rows of ws.psum become zero.
+// combine: Route::psum_combine / psum_combine_last.
 template <int S, int KW>
-void launch_lbs_bm(const smplfit_handle* h, const Workspace& ws, int B, hipStream_t st, bool write_v = false,
-                   bool adj_only = false, bool weighted = false, bool write_all = false, int regress = -1, bool combine = true) {
+void launch_lbs_bm(const smplfit_handle* h, const Workspace& ws, int B, hipStream_t st, bool combine, bool write_v,
+                   bool adj_only, bool weighted, bool write_all = false, int regress = -1) {
   const DevModel& d = h->d;
   const int Mp = (int)align_up((size_t)B, 128);
-  const size_t lds = (size_t)tune().bm_lds_kb * 1024;
   const ShareView sv = share_view(h, write_v ? sf::kShareLbsAll : adj_only ? sf::kShareLbsAdj : sf::kShareLbsUsed, B);
-  if constexpr ((KW == 4 || KW == 8) && sf::bm_shape_count(S)) {  // what bm_applies admits (10 / 16 betas with or without the kid unknown)
+  if constexpr ((KW == 4 || KW == 8) && sf::bm_shape_count(S)) {  // what route_of admits (10 / 16 betas with or without the kid unknown)
     if (write_v) {
       // (write_all: every posed vertex — the alignment sums of a known-shape fit; else the slots the regressor reads)
       const int wa = write_all ? 1 : 0;
       if (weighted)
-        hipLaunchKernelGGL((k_lbs_partsum_bm<S, KW, true, false, true>), share_grid(sv, Mp), dim3(64 * kBW), lds, st, d, sv, ws, B, Mp, wa);
+        hipLaunchKernelGGL((k_lbs_partsum_bm<S, KW, true, false, true>), share_grid(sv, Mp), dim3(64 * kBW), 0, st, d, sv, ws, B, Mp, wa);
       else
-        hipLaunchKernelGGL((k_lbs_partsum_bm<S, KW, true>), share_grid(sv, Mp), dim3(64 * kBW), lds, st, d, sv, ws, B, Mp, wa);
+        hipLaunchKernelGGL((k_lbs_partsum_bm<S, KW, true>), share_grid(sv, Mp), dim3(64 * kBW), 0, st, d, sv, ws, B, Mp, wa);
       // regress: the regressed reference joints are consumed (joints-omitted fits).  A known-shape fit WITH target
       // joints keeps the posed mesh for its alignment sums only; and a model without a regressor has none to apply
       const bool do_regress = (regress < 0 ? true : regress != 0) && h->t.has_regressor;
       if (do_regress)
         hipLaunchKernelGGL(k_regress_joints_bm<false>, dim3(Mp / 64, d.J), dim3(64), 0, st, d, ws.vpT, nullptr, ws.rjreg, B);
     } else if (weighted) {
-      hipLaunchKernelGGL((k_lbs_partsum_bm<S, KW, false, false, true>), share_grid(sv, Mp), dim3(64 * kBW), lds, st, d, sv, ws, B, Mp);
+      hipLaunchKernelGGL((k_lbs_partsum_bm<S, KW, false, false, true>), share_grid(sv, Mp), dim3(64 * kBW), 0, st, d, sv, ws, B, Mp);
     } else {
-      hipLaunchKernelGGL((k_lbs_partsum_bm<S, KW>), share_grid(sv, Mp), dim3(64 * kBW), lds, st, d, sv, ws, B, Mp);
+      hipLaunchKernelGGL((k_lbs_partsum_bm<S, KW>), share_grid(sv, Mp), dim3(64 * kBW), 0, st, d, sv, ws, B, Mp);
     }
   }
-  if (combine) launch_psum_combine(d, sv, ws, B, Mp, st);  // (k_refine_bm adds the rows of the last pass itself)
+  if (combine) launch_psum_combine(d, sv, ws, B, Mp, st);
 }
 
 // the forward-only variant of the batch-major LBS pass (posed vertices left in ws.vpT): input side of a fused
@@ -694,10 +658,14 @@ int launch_lbs_fwd_bm(const DevModel& d, const ShareView& sv, const Workspace& w
   return 0;
 }
 
+// The unit-weight vertex block has two implementations:
+//   direct (default): k_shape_accum accumulates G, r, Sb per vertex (VALU-bound);
+//   pair  (pair_form, Route::pair_in): k_residual + k_pair_gram — 4x fewer per-vertex FLOPs, parity-tested,
+//          but not faster on wave-per-instance kernels (the batch-major path always uses the pair form).
 template <int S, int KW>
-int launch_shape_accum(const DevModel& d, const Workspace& ws, int B, bool weighted, hipStream_t st) {
+int launch_shape_accum(const DevModel& d, const Workspace& ws, int B, bool weighted, bool pair_form, hipStream_t st) {
   const dim3 grid((B + kNW - 1) / kNW);
-  if (weighted || !use_pair_form()) {
+  if (weighted || !pair_form) {
     const size_t lds =
         ((size_t)kNW * d.J * sf::jd_stride(S) + 2 * 64 * sf::cpack_stride(S, KW) + 256 * 12) * 4;
     if (weighted)
@@ -741,7 +709,7 @@ void launch_center_sort(const DevModel& d, const float* tv, const float* tj, con
   int VL = d.V;
   {
     const int cap = ((80 * 1024 - 64 * 4) / 12) & ~1;
-    if (tune().k0_two && d.V > cap && d.V - cap <= d.V / 16) VL = cap;
+    if (d.V > cap && d.V - cap <= d.V / 16) VL = cap;
   }
   const size_t lds_row = ((size_t)((3 * VL + 3) & ~3) + 64) * 4;
   if (lds_row <= 160 * 1024) {
@@ -787,7 +755,7 @@ int launch_gen_accum_mfma(const DevModel& d, const Workspace& ws, int B, bool we
   const dim3 grid(B, gen2_groups(d.S));
   // blend passes (64 / 128 vertices) between two additions of the fp32 accumulators to the fp64 record: a scaled
   // iteration after every pass, the others after 2048 vertices (k_gen_accum_mfma; +2.5 % of its time, 1024: +5 %)
-  const int flush_every = vextra ? 1 : std::max(1, (tune().gen_flush ? tune().gen_flush : 2048) / gen2_sv(d.S));
+  const int flush_every = vextra ? 1 : std::max(1, 2048 / gen2_sv(d.S));
 #define SF_GEN2(W_, NW_, NBW_, ST_)                                                                                   \
   do {                                                                                                                \
     ensure_max_lds(reinterpret_cast<const void*>(&k_gen_accum_mfma<W_, NW_, NBW_, ST_>)); \
@@ -866,10 +834,11 @@ void launch_gen_lbs(const DevModel& d, const Workspace& ws, int B, bool weighted
 // the vertex block / the LBS pass of the wave-per-instance path OR the general one, by model
 // jrows_tj / jrows_jw: the centred target joints (and their weights) when gen_joint_rows() moved the joint block here
 // extras: also the extra sums of a scale unknown (general path: ws.gvex; the other paths run k_scale_extras)
-int launch_accum_any(const DevModel& d, const Workspace& ws, int B, bool weighted, hipStream_t st,
+// pair_form: Route::pair_in (wave-per-instance path)
+int launch_accum_any(const DevModel& d, const Workspace& ws, int B, bool weighted, bool pair_form, hipStream_t st,
                      const float* jrows_tj = nullptr, const float* jrows_jw = nullptr, bool extras = false) {
   if (d.general) return launch_gen_accum(d, ws, B, weighted, st, jrows_tj, jrows_jw, extras);
-#define SF_CALL_ACCUM(S_, KW_) launch_shape_accum<S_, KW_>(d, ws, B, weighted, st)
+#define SF_CALL_ACCUM(S_, KW_) launch_shape_accum<S_, KW_>(d, ws, B, weighted, pair_form, st)
   SF_DISPATCH_SKW(d, SF_CALL_ACCUM);
 #undef SF_CALL_ACCUM
   return 0;
@@ -915,9 +884,7 @@ int launch_gemm(const DevModel& d, const Workspace& ws, int B, hipStream_t st, b
     // together: the 39 KB tile images come out of that XCD's L2 and posedirs is fetched from HBM about twice
     // per launch instead of once per instance block (FETCH_SIZE: 444 -> 72 MB per launch at B = 4096).
     const int ntiles = N / 32, ny = (Mp + 32 * kGemmWaves - 1) / (32 * kGemmWaves);
-    int nchunk = std::max(8, (2 * 256 / ny + 4) / 8 * 8);
-    if (tune().gemm_nchunk > 0) nchunk = tune().gemm_nchunk;
-    nchunk = std::min(nchunk, ntiles);
+    const int nchunk = std::min(std::max(8, (2 * 256 / ny + 4) / 8 * 8), ntiles);
     const int per = (ntiles + nchunk - 1) / nchunk;  // trailing chunks may be empty (they return at once)
     const size_t lds = (size_t)kGemmRing * kGemmTileBytes;
     ensure_max_lds(reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<true>));
@@ -948,17 +915,7 @@ int launch_gemm(const DevModel& d, const Workspace& ws, int B, hipStream_t st, b
     nchunk = std::min(nchunk, ntiles);
     const int per = (ntiles + nchunk - 1) / nchunk;
     nchunk = (ntiles + per - 1) / per;
-    size_t lds = (size_t)2 * 32 * (2 * NK2 + 4) * 4;
-    {
-      // SMPLFIT_GEMM_LDS_KB: pad the workgroup's LDS request (84 = one GEMM workgroup per CU, which leaves
-      // LDS and registers for two batch-major workgroups of another chunk beside it)
-      const int pad_kb = tune().gemm_lds_kb;
-      if (pad_kb > 0) {
-        lds = std::max(lds, (size_t)pad_kb * 1024);
-        ensure_max_lds(reinterpret_cast<const void*>(&k_posedirs_gemm_as<NK2, true>));
-        ensure_max_lds(reinterpret_cast<const void*>(&k_posedirs_gemm_as<NK2, false>));
-      }
-    }
+    const size_t lds = (size_t)2 * 32 * (2 * NK2 + 4) * 4;
     if (transposed)
       hipLaunchKernelGGL((k_posedirs_gemm_as<NK2, true>), dim3(nchunk, Mp / 128), dim3(256), lds, st,
                          ws.rp, d.pdSw, ws.vpT, N, per, Mp);
@@ -1054,7 +1011,7 @@ void launch_shape_solve(const DevModel& d, const Workspace& ws, int B, hipStream
 // K4' (k_solve_bm): the normal-equation combine and the shape solve of the batch-major path as one launch, lane =
 // instance.  Applies to the plain per-instance solve on the sums of k_residual_bm + k_pair_gram_bm (unit vertex weights
 // in the solve, no share_beta, no scale unknown) for 10 / 11 shape unknowns; everything else keeps k_gram_combine_bm +
-// k_shape_solve (SMPLFIT_SOLVE_BM=0: everywhere, A/B).
+// k_shape_solve (route_of).
 constexpr int kSolveIB = 16;
 // what k_solve_bm needs beyond the model: the longest run of moment rows of a joint in the residual table of this batch
 // (rounded up to 8), the sizes of its three buffers (their descriptors take byte offsets below 2^31)
@@ -1067,7 +1024,7 @@ struct SolveBmPlan {
 SolveBmPlan solve_bm_plan(const smplfit_handle* h, int B) {
   SolveBmPlan p;
   const DevModel& d = h->d;
-  if (!tune().solve_bm || d.general || !(d.S == 10 || d.S == 11) || !d.bm_tables) return p;
+  if (d.general || !(d.S == 10 || d.S == 11) || !d.bm_tables) return p;
   const int idx = share_index(sf::kShareResidual, B);
   if (idx >= sf::kShareFine || (size_t)idx >= h->views.size()) return p;  // (small batches: the fine cell tables keep k_gram_combine_split + k_shape_solve)
   const sf::ShareTable& t = h->t.shares[idx];
@@ -1095,7 +1052,6 @@ SolveBmPlan solve_bm_plan(const smplfit_handle* h, int B) {
   p.ok = true;
   return p;
 }
-bool solve_bm_applies(const smplfit_handle* h, int B) { return solve_bm_plan(h, B).ok; }
 template <int S>
 void launch_solve_bm_s(const smplfit_handle* h, const Workspace& ws, int B, hipStream_t st, SolveBmPlan p) {
   const DevModel& d = h->d;
@@ -1104,10 +1060,10 @@ void launch_solve_bm_s(const smplfit_handle* h, const Workspace& ws, int B, hipS
   if (p.lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(&k_solve_bm<S, kSolveIB>));
   hipLaunchKernelGGL((k_solve_bm<S, kSolveIB>), dim3(groups), dim3(64 * kSolveWaves), p.lds, st, d, p.sv, ws, B, Mp, p.a);
 }
-// pro: the joint block and the FK rows come from k_prologue_bm (ws.gramjP, ws.pextT) instead of k_joint_stage
-void launch_solve_bm(const smplfit_handle* h, const Workspace& ws, int B, hipStream_t st, float beta_reg, float beta_reg2,
-                     float kid_reg, int use_ref, bool pro = false) {
-  SolveBmPlan p = solve_bm_plan(h, B);  // (callers ask solve_bm_applies first)
+// p: Route::solve_plan.  pro: the joint block and the FK rows come from k_prologue_bm (ws.gramjP, ws.pextT) instead of
+// k_joint_stage
+void launch_solve_bm(const smplfit_handle* h, SolveBmPlan p, const Workspace& ws, int B, hipStream_t st, float beta_reg,
+                     float beta_reg2, float kid_reg, int use_ref, bool pro) {
   p.a.gj_parts = pro ? prologue_splits(h->d.J) : 0;
   p.a.pext_t = pro ? 1 : 0;
   p.a.beta_reg = beta_reg;
@@ -1120,8 +1076,7 @@ void launch_solve_bm(const smplfit_handle* h, const Workspace& ws, int B, hipStr
 
 // K1p (k_prologue_bm): the shape prologue of the joint stage on the batch-major path — k_joint_stage then fits the
 // rotations only and leaves ws.GT.  Applies when every shape solve of the call is k_solve_bm (the one consumer of its
-// ws.gramjP / ws.pextT): the plain per-instance solve, unit vertex weights in the solve, 10 / 11 unknowns.
-bool prologue_bm_applies(const smplfit_handle* h, int B) { return tune().prologue_bm && solve_bm_applies(h, B); }
+// ws.gramjP / ws.pextT): route_of.
 void launch_prologue_bm(const smplfit_handle* h, const JointStageArgs& ja, const Workspace& ws, int B, hipStream_t st) {
   const DevModel& d = h->d;
   const int Mp = (int)align_up((size_t)B, 128);
@@ -1195,16 +1150,6 @@ int refine_bm_groups(const sf::HostTables& t, RefGroups* rg) {  // -> the most p
   }
   return mx;
 }
-bool refine_bm_applies(const smplfit_handle* h, bool pro) {
-  return pro && tune().refine_bm && h->d.J <= 32 && h->refine_group_max <= kRefParts &&
-         (size_t)refine_bm_lds_floats(h->d.J) * 4 <= 160 * 1024;
-}
-// (once k_rotations_bm runs nothing writes the instance-major ws.G any more: a model whose refinement stays on
-// k_refine_epilogue — more than 32 joints — gets it from k_gt_to_g in front of that kernel)
-bool rot_bm_applies(const smplfit_handle* h, bool pro) {
-  return pro && tune().rot_bm && h->d.J <= kRotMaxJ && h->rot_nslots <= kRotSlots && h->rot_toes_per_wave <= 2 &&
-         (size_t)rot_bm_lds_floats(h->d.J) * 4 <= 160 * 1024;
-}
 // sv: the table of the LBS pass whose rows hold the part sums (unused without final_adjust)
 void launch_refine_bm(const smplfit_handle* h, RefineArgs ra, const ShareView& sv, const Workspace& ws, int B, hipStream_t st) {
   const DevModel& d = h->d;
@@ -1219,6 +1164,91 @@ void launch_refine_bm(const smplfit_handle* h, RefineArgs ra, const ShareView& s
     if (lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(&k_refine_bm<10>));
     hipLaunchKernelGGL(k_refine_bm<10>, dim3((B + 63) / 64), dim3(64 * kRefWaves), lds, st, d, ra, sv, ws, ws.rjoints, Mp, h->refine_groups);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Kernel route of one call: which kernel family serves its vertex passes and which stage kernels run inside the
+// batch-major one, decided once per call by route_of() from the handle, the batch and the call's shape.  Nothing else
+// reads the routing switches (SMPLFIT_BM, SMPLFIT_BM_*, _ROT_BM, _REFINE_BM, _PROLOGUE_BM, _SOLVE_BM, _SHAPE_FORM).
+//
+//   condition                                                      -> kernels
+//   <= 8 skinning weights summing to one, 10 / 16 betas +- kid,      -> bm: the batch-major vertex passes; otherwise
+//     >= 1024 vertices; not rotations_only; per entry BM_KNOWN_POSE,    the wave-per-instance (or general) kernels
+//     BM_FORWARD, BM_KNOWN_SHAPE; vertex weights: BM_WEIGHTED; scale
+//     unknown: BM_SCALE; either in the solve: 10 betas, 4 weights
+//   bm, no weights in the solve, no share_beta, 10 / 11 unknowns,   -> unscaled solves: k_solve_bm on the partial sums;
+//     coarse tables, buffers < 2 GB (solve_bm_plan); SOLVE_BM           else k_gram_combine_bm + k_shape_solve
+//   a fit with k_solve_bm, no scale unknown; PROLOGUE_BM             -> k_prologue_bm, which writes ws.jdT: no k_jd_transpose
+//   k_prologue_bm, <= 64 joints, toe sources fit; ROT_BM             -> k_rotations_bm: no k_psum_combine behind the passes
+//                                                                      in front of a rotation pass
+//   k_prologue_bm, <= 32 joints, <= 4 adjustable parts a wave; REFINE_BM -> k_refine_bm: no k_psum_combine behind the last
+//                                                                      pass; else k_refine_epilogue (+ k_gt_to_g first
+//                                                                      when k_rotations_bm ran)
+//   no weights in the solve, not general; bm or SHAPE_FORM=pair      -> pair-Gram form (not the scaled solve of bm)
+// ------------------------------------------------------------------------------------------------
+enum class Entry { kFit, kConvert, kShapeSolve, kForward, kKnownShape };
+struct CallShape {
+  Entry entry = Entry::kFit;
+  bool joints = true;                // target joints given
+  bool vw = false, eff_v = false;    // vertex weights given; they enter the shape solve
+  int scale_mode = 0;
+  bool share_beta = false, rotations_only = false;
+  bool warm = false;                 // warm start: the first rotation pass reads the rows of the warm start's LBS pass
+};
+struct Route {
+  bool bm = false;                   // batch-major vertex kernels
+  bool solve_bm = false;             // unscaled, unshared solves are k_solve_bm (on solve_plan)
+  SolveBmPlan solve_plan{};
+  bool prologue_bm = false;          // k_prologue_bm
+  bool jd_transpose = false;         // k_jd_transpose in front of a fit iteration's vertex passes
+  bool rot_bm = false;               // k_rotations_bm, on the rows of the tables rot_kind_first / _next (else -1)
+  int rot_kind_first = -1, rot_kind_next = -1;
+  bool refine_bm = false;            // k_refine_bm on the rows of the table refine_kind (else -1); else k_refine_epilogue
+  int refine_kind = -1;
+  bool gt_to_g = false;              // k_gt_to_g in front of k_refine_epilogue
+  bool psum_combine = true, psum_combine_last = true;  // k_psum_combine behind the passes in front of a rotation pass / the last
+  int pair_in = 0, pair_in_scaled = 0;  // the unscaled / the scaled solve reads the pair-Gram form
+};
+Route route_of(const smplfit_handle* h, int B, const CallShape& c) {
+  const Tuning& tn = tune();
+  const DevModel& d = h->d;
+  Route r;
+  // Vp > V: the batch-major loops run their out-of-range steps on the first padding slot; small vertex subsets are faster
+  // on the wave-per-instance kernels (V = 1024, B = 16384: 4.15 M fits/s batch-major vs 4.63 M).  The residual kernel
+  // derives sum_v b_v from the per-joint moments: exact only when every vertex's skinning weights sum to one (wsum_dev).
+  const bool model_bm = tn.bm && (d.KW == 4 || d.KW == 8) && sf::bm_shape_count(d.S) && d.bm_tables && d.V >= 1024 &&
+                        d.Vp > d.V && h->t.wsum_dev <= 1e-5f;
+  const bool accum_w = d.S == 10 && d.KW == 4;  // what k_accum_w_bm is built for
+  const bool solves = c.entry != Entry::kForward && c.entry != Entry::kKnownShape;
+  if (c.entry == Entry::kForward) r.bm = model_bm && tn.bm_forward;
+  else if (c.entry == Entry::kKnownShape) r.bm = model_bm && (!c.vw || tn.bm_weighted) && tn.bm_known_shape;
+  else r.bm = model_bm && !c.rotations_only && (c.entry != Entry::kShapeSolve || tn.bm_known_pose) &&
+              (!c.vw || (tn.bm_weighted && (!c.eff_v || accum_w))) && (!c.scale_mode || (tn.bm_scale && accum_w));
+  if (solves && r.bm && !c.eff_v && !c.share_beta && tn.solve_bm) {
+    r.solve_plan = solve_bm_plan(h, B);
+    r.solve_bm = r.solve_plan.ok;
+  }
+  const bool fit = c.entry == Entry::kFit || c.entry == Entry::kConvert;
+  r.prologue_bm = fit && r.solve_bm && !c.scale_mode && tn.prologue_bm;
+  r.jd_transpose = r.bm && !r.prologue_bm;
+  // (once k_rotations_bm runs nothing writes the instance-major ws.G any more: a model whose refinement stays on
+  // k_refine_epilogue — more than 32 joints — gets it from k_gt_to_g in front of that kernel)
+  r.rot_bm = r.prologue_bm && tn.rot_bm && d.J <= kRotMaxJ && h->rot_nslots <= kRotSlots && h->rot_toes_per_wave <= 2 &&
+             (size_t)rot_bm_lds_floats(d.J) * 4 <= 160 * 1024;
+  r.refine_bm = r.prologue_bm && tn.refine_bm && d.J <= 32 && h->refine_group_max <= kRefParts &&
+                (size_t)refine_bm_lds_floats(d.J) * 4 <= 160 * 1024;
+  r.gt_to_g = r.rot_bm && !r.refine_bm;
+  r.psum_combine = !r.rot_bm;
+  r.psum_combine_last = !r.refine_bm;
+  // the tables of the passes in front (launch_lbs_bm): without target joints every slot, else the used parts — the
+  // last pass of a fit with target joints the adjustable ones
+  r.rot_kind_first = !r.rot_bm ? -1 : c.warm && !c.joints ? sf::kShareLbsAll : sf::kShareLbsUsed;
+  r.rot_kind_next = !r.rot_bm ? -1 : !c.joints ? sf::kShareLbsAll : sf::kShareLbsUsed;
+  r.refine_kind = !r.refine_bm ? -1 : !c.joints ? sf::kShareLbsAll : sf::kShareLbsAdj;
+  // (weights in the solve, and the scaled solve of the bm path: the accumulate kernel leaves the complete record)
+  r.pair_in = (!c.eff_v && !d.general && (r.bm || tn.pair_form)) ? 1 : 0;
+  r.pair_in_scaled = (!c.eff_v && !d.general && !r.bm && tn.pair_form) ? 1 : 0;
+  return r;
 }
 
 int post_launch_check() {
@@ -1257,7 +1287,7 @@ struct ConvertSource {
   int nb;
   Workspace wsi;  // forward-only workspace slice of the input model (carve(..., fwd_only))
 };
-int launch_convert_source(const ConvertSource& src, const DevModel& d_out, const Workspace& ws, int B, hipStream_t st);
+int launch_convert_source(const ConvertSource& src, const Route& r, const Workspace& ws, int B, hipStream_t st);
 
 // The solve of one shape pass on the sums already in the workspace: the plain per-instance solve, the
 // scaled solve (one more unknown; extra vertex sums first) or the shared solve (assemble, sum over the
@@ -1282,14 +1312,14 @@ int share_sum(const DevModel& d, const Workspace& ws, int B, const FitOptions& o
   return 0;
 }
 
-// fused: the handle when the sums in the workspace are the PARTIAL sums of k_residual_bm + k_pair_gram_bm (the combine
-// was not launched: fused_solve() said so) and k_solve_bm takes them from there; null: the record is in ws.gramv
-bool fused_solve(const smplfit_handle* h, int B, const FitOptions& o, int pair_in, bool scaled) {
-  return pair_in && !scaled && !o.share_beta && solve_bm_applies(h, B);
-}
-int enqueue_solve(const DevModel& d, const Workspace& ws, int B, const FitOptions& o, bool joints, bool eff_v,
-                  bool eff_j, const float* jw, int pair_in, int use_ref, bool scaled, hipStream_t st,
-                  bool extras_done = false, const smplfit_handle* fused = nullptr, bool pro = false) {
+// An unscaled solve on the bm path with r.solve_bm finds the PARTIAL sums of k_residual_bm + k_pair_gram_bm in the
+// workspace (the combine was not launched) and k_solve_bm takes them from there; otherwise the record is in ws.gramv.
+// The scaled solve of the bm path finds the extra sums of k_accum_w_bm in ws.vextra.
+int enqueue_solve(const smplfit_handle* h, const Route& r, const Workspace& ws, int B, const FitOptions& o, bool joints,
+                  bool eff_v, bool eff_j, const float* jw, int use_ref, bool scaled, hipStream_t st) {
+  const DevModel& d = h->d;
+  const int pair_in = scaled ? r.pair_in_scaled : r.pair_in;
+  const bool extras_done = r.bm && scaled;
   if (d.general && scaled && !tune().gen_mfma)
     return fail(SMPLFIT_ERR_UNSUPPORTED, "general path with SMPLFIT_GEN_MFMA=0: the scale unknown's extra sums come from the "
                                          "matrix-core accumulate kernel only");
@@ -1335,8 +1365,8 @@ int enqueue_solve(const DevModel& d, const Workspace& ws, int B, const FitOption
     };
     if (int rc = share_sum(d, ws, B, o, st, assemble)) return rc;
     launch_shape_solve(d, ws, B, st, o.beta_reg, o.beta_reg2, o.kid_reg, pair_in, 0, 2);
-  } else if (fused) {
-    launch_solve_bm(fused, ws, B, st, o.beta_reg, o.beta_reg2, o.kid_reg, use_ref, pro);
+  } else if (r.solve_bm) {
+    launch_solve_bm(h, r.solve_plan, ws, B, st, o.beta_reg, o.beta_reg2, o.kid_reg, use_ref, r.prologue_bm);
   } else {
     launch_shape_solve(d, ws, B, st, o.beta_reg, o.beta_reg2, o.kid_reg, pair_in, use_ref);
   }
@@ -1363,32 +1393,26 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
   // joints (bodyfitter.py:1018-1028)
   const bool eff_v = joints ? (vw && jw) : (vw != nullptr);
   const bool eff_j = joints && vw && jw;
+  const bool warm = o.init_pose || o.init_betas;
   // vertex weights on the batch-major path: the weight stream, weighted part sums, and — when the weights enter the
-  // shape solve — the weighted accumulate (built for 10 unknowns; with the kid unknown such a fit stays on the
-  // wave-per-instance kernels)
-  // scale_target / scale_fit: the LAST iteration's solve has one more unknown and needs extra vertex sums — that
-  // iteration runs the accumulate kernel (with or without weights) in its EXTRAS form
-  // (the accumulate kernel k_accum_w_bm — vertex weights in the solve, the scaled iteration — holds four joints per piece)
-  const bool bm_base = bm_applies(h) && !o.rotations_only && (!o.scale_mode || (tune().bm_scale && d.S == 10 && d.KW == 4));
-  const bool bm = bm_base && (!vw || (tune().bm_weighted && (!eff_v || (d.S == 10 && d.KW == 4))));
-  if (o.source && !bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "fused conversion: the batch-major path does not apply");
-  // (every solve of this call is k_solve_bm: the prologue runs as k_prologue_bm, which also writes ws.jdT)
-  const bool pro = bm && !o.rotations_only && !eff_v && !o.scale_mode && !o.share_beta && prologue_bm_applies(h, B);
-  const bool rbm = refine_bm_applies(h, pro);  // the refinement as k_refine_bm (adds the last pass's part-sum rows itself)
-  const bool rotbm = rot_bm_applies(h, pro);   // the part rotations as k_rotations_bm (adds the part-sum rows itself)
+  // shape solve — the weighted accumulate.  scale_target / scale_fit: the LAST iteration's solve has one more unknown
+  // and needs extra vertex sums — that iteration runs the accumulate kernel (with or without weights) in its EXTRAS form
+  const Route r = route_of(h, B, {o.source ? Entry::kConvert : Entry::kFit, joints, vweighted, eff_v, o.scale_mode,
+                                  o.share_beta != 0, o.rotations_only != 0, warm});
+  if (o.source && !r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "fused conversion: the batch-major path does not apply");
   // (a warm-started fit evaluates its first part sums against the posed initial model: on the batch-major path with
   // the LBS pass of the iterations — until round 4 with the wave-per-instance kernel over a second, sorted copy)
-  if (on(0) && !bm) launch_center_sort(d, tv, tj, vw, ws, B, st);
+  if (on(0) && !r.bm) launch_center_sort(d, tv, tj, vw, ws, B, st);
   if (!on(0)) {
-  } else if (bm && o.source) {
-    if (int rc = launch_convert_source(*o.source, d, ws, B, st)) return rc;
-  } else if (bm) {
-    launch_layout_bm(h, tv, tj, ws, B, st, vw, !(o.init_pose || o.init_betas), !rotbm);
+  } else if (r.bm && o.source) {
+    if (int rc = launch_convert_source(*o.source, r, ws, B, st)) return rc;
+  } else if (r.bm) {
+    launch_layout_bm(h, tv, tj, ws, B, st, vw, !warm, r.psum_combine);
   }
   const float* tj_rot = ws.tjc;
   if (!joints) {  // regressed target joints from the centred vertices (bodyfitter.py:1342-1344)
     if (!on(0)) {
-    } else if (bm)
+    } else if (r.bm)
       hipLaunchKernelGGL(k_regress_joints_bm<true>, dim3((int)align_up((size_t)B, 128) / 64, d.J), dim3(64), 0, st, d,
                          ws.tT, ws.mean, ws.tjreg, B);
     else
@@ -1408,7 +1432,6 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
   // bodyfitter.py:363-382: the first rotation pass runs against the posed model only when a pose or a
   // shape is given; the ridge references reach EVERY shape solve whenever they are given — also an
   // initial_kid_factor on its own (:413-414, :448-449)
-  const bool warm = o.init_pose || o.init_betas;
   const int use_ref = (o.init_betas || o.init_kid) ? 1 : 0;
   if (on(0) && (warm || use_ref))
     hipLaunchKernelGGL(k_fill_shape, dim3((B + 255) / 256), dim3(256), 0, st, ws, B, d.S, d.jt.n_kid,
@@ -1420,11 +1443,11 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
     fa.nb = d.S;
     fa.joints = ws.rjoints;
     fa.orient = ws.G;
-    if (on(0) && bm) {
+    if (on(0) && r.bm) {
       launch_forward_joint(d, fa, ws, B, st);
       if (int rc = launch_gemm(d, ws, B, st, true)) return rc;
       launch_jd_transpose(d, ws, B, st);
-#define SF_CALL_LBS(S_, KW_) launch_lbs_bm<S_, KW_>(h, ws, B, st, !joints, false, vweighted, false, -1, !rotbm)
+#define SF_CALL_LBS(S_, KW_) launch_lbs_bm<S_, KW_>(h, ws, B, st, r.psum_combine, !joints, false, vweighted)
       SF_DISPATCH_SKW(d, SF_CALL_LBS);
 #undef SF_CALL_LBS
     } else if (on(0)) {
@@ -1448,8 +1471,7 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
   // (first rotations: the rows of the template pass — or of the warm start's LBS pass —; previous rotations: the
   // instance-major ws.G of the warm start's forward stage, if any)
   if (on(0))
-    launch_joint_stage_fit(h, ja, ws, B, st, pro, !rotbm ? -1 : (warm && !joints) ? sf::kShareLbsAll : sf::kShareLbsUsed,
-                           ja.Gprev ? 2 : 0);
+    launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_first, ja.Gprev ? 2 : 0);
   if (o.rotations_only) {
     if (on(0)) hipLaunchKernelGGL(k_copy, dim3(256), dim3(256), 0, st, ws.G, orient, (size_t)B * d.J * 9);
     return post_launch_check();
@@ -1457,7 +1479,7 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
   for (int it = 0; it < o.num_iter; ++it) {
     const bool pa = on(1 + 2 * it), pb = on(2 + 2 * it);
     if (!pa) {
-    } else if (bm) {
+    } else if (r.bm) {
       // batch-major vertex block: one transposed GEMM feeds the residual pass and, after the solve,
       // the LBS / part-sum pass of this iteration
       const int Mp = (int)align_up((size_t)B, 128);
@@ -1467,32 +1489,27 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
       // not kept: k_joint_stage writing ws.jdT itself — 64 waves of one XCD completing every 256-byte row with
       // one float each — instead of this 8 us launch: 2.54 -> 2.50 M fits/s, SMPL-X 1.31 -> 1.24: the scattered
       // stores cost the latency-bound stage more than the transpose.)
-      if (!pro) launch_jd_transpose(d, ws, B, st);
+      if (r.jd_transpose) launch_jd_transpose(d, ws, B, st);
       if (o.scale_mode && it + 1 == o.num_iter) launch_accum_w_bm(h, ws, B, st, eff_v, true);
       else if (eff_v) launch_accum_w_bm(h, ws, B, st);
-      else launch_residual_bm(h, ws, B, st, fused_solve(h, B, o, 1, false) ? 3 : 7);  // (k_solve_bm adds the partial sums itself)
+      else launch_residual_bm(h, ws, B, st, r.solve_bm ? 3 : 7);  // (k_solve_bm adds the partial sums itself)
     } else {
       launch_gemm(d, ws, B, st);
-      if (int rc = launch_accum_any(d, ws, B, eff_v, st, gjr ? tj_rot : nullptr, gjr && eff_j ? jw : nullptr,
+      if (int rc = launch_accum_any(d, ws, B, eff_v, r.pair_in, st, gjr ? tj_rot : nullptr, gjr && eff_j ? jw : nullptr,
                                     o.scale_mode && it + 1 == o.num_iter))
         return rc;
     }
     // K4 stays its own launch: fused into the prologue of the LBS kernel (template flag SOLVE) its
     // ~40 serial barriers stall all four waves of the workgroup and the kernel ran 230 us longer
     const bool scaled_now = o.scale_mode && it + 1 == o.num_iter;  // only the last solve (:434-455)
-    // (the accumulate kernel — weighted fits, and the scaled iteration on the batch-major path — leaves the complete
-    // record: the classic form of the solve; the residual pass the pair-Gram form)
-    const int pair_in = (!eff_v && !d.general && !(bm && scaled_now) && (bm || use_pair_form())) ? 1 : 0;
     if (pb)
-      if (int rc = enqueue_solve(d, ws, B, o, joints, eff_v, eff_j, jw, pair_in, use_ref, scaled_now, st, bm && scaled_now,
-                                 bm && fused_solve(h, B, o, pair_in, scaled_now) ? h : nullptr, pro))
-        return rc;
+      if (int rc = enqueue_solve(h, r, ws, B, o, joints, eff_v, eff_j, jw, use_ref, scaled_now, st)) return rc;
     const bool last = it + 1 == o.num_iter;
     if (last && !o.final_adjust) break;  // nothing consumes the re-evaluated mesh
     if (!pb) {
-    } else if (bm) {
+    } else if (r.bm) {
 #define SF_CALL_LBS(S_, KW_) \
-  launch_lbs_bm<S_, KW_>(h, ws, B, st, !joints, last && joints && !tune().lbs_all_last, vweighted, false, -1, !(last ? rbm : rotbm))
+  launch_lbs_bm<S_, KW_>(h, ws, B, st, last ? r.psum_combine_last : r.psum_combine, !joints, last && joints, vweighted)
       SF_DISPATCH_SKW(d, SF_CALL_LBS);
 #undef SF_CALL_LBS
     } else if (joints) {
@@ -1505,7 +1522,7 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
     ja.rj = joints ? ws.rjoints : ws.rjreg;
     ja.rj_shared = 0;
     ja.Gprev = ws.G;
-    if (pb) launch_joint_stage_fit(h, ja, ws, B, st, pro, !rotbm ? -1 : !joints ? sf::kShareLbsAll : sf::kShareLbsUsed, 1);
+    if (pb) launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_next, 1);
   }
   if (!on(1 + 2 * o.num_iter)) return post_launch_check();
   RefineArgs ra{};
@@ -1527,10 +1544,10 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
     if (o.scale_out)
       hipLaunchKernelGGL(k_copy, dim3(16), dim3(256), 0, st, ws.scale, o.scale_out, (size_t)B);
   }
-  if (rbm)  // (the table of the last LBS pass: every slot without target joints, else the adjustable / the used parts)
-    launch_refine_bm(h, ra, share_view(h, !joints ? sf::kShareLbsAll : tune().lbs_all_last ? sf::kShareLbsUsed : sf::kShareLbsAdj, B), ws, B, st);
-  else {
-    if (rotbm)  // (k_rotations_bm left the rotations instance-innermost only)
+  if (r.refine_bm) {
+    launch_refine_bm(h, ra, share_view(h, r.refine_kind, B), ws, B, st);
+  } else {
+    if (r.gt_to_g)  // (k_rotations_bm left the rotations instance-innermost only)
       hipLaunchKernelGGL(k_gt_to_g, dim3((B + 63) / 64, (d.J + 15) / 16), dim3(256), 0, st, ws, d.J, B, (int)align_up((size_t)B, 128));
     launch_refine(d, ra, ws, B, st);
   }
@@ -1557,15 +1574,11 @@ int run_fit_known_shape(const smplfit_handle* h, const float* betas, int nb, con
   const bool vweighted = vw != nullptr;
   // the batch-major vertex kernels (round 4): target (+ weight) streams, transposed GEMM, part sums with lane =
   // instance (the LAST pass leaves the posed vertices in ws.vpT), alignment sums over the streams
-  const bool bm = bm_applies(h) && (!vw || tune().bm_weighted) && tune().bm_known_shape;
+  const Route r = route_of(h, B, {Entry::kKnownShape, joints, vweighted});
   const int Mp = (int)align_up((size_t)B, 128);
   const float* tj_rot = ws.tjc;
-  if (bm) {
-    const int nslab = (d.V + kSlabV - 1) / kSlabV;
-    if (vw) hipLaunchKernelGGL(k_layout_weights, dim3((d.V + 63) / 64 + 1, Mp / 64), dim3(256), 0, st, d, vw, ws.wT, B);
-    hipLaunchKernelGGL(k_layout_targets, dim3(nslab, Mp / 64), dim3(256), (size_t)64 * kSlabRow * 4, st, d, tv, ws.tT, ws.resP,
-                       B, Mp);
-    hipLaunchKernelGGL(k_mean_finish, dim3(Mp / 64), dim3(64 * kMeanWaves), 0, st, d, tj, ws.resP, ws, B, Mp, nslab);
+  if (r.bm) {
+    launch_layout_bm(h, tv, tj, ws, B, st, vw, false, r.psum_combine);
     if (!joints) {
       hipLaunchKernelGGL(k_regress_joints_bm<true>, dim3(Mp / 64, d.J), dim3(64), 0, st, d, ws.tT, ws.mean, ws.tjreg, B);
       tj_rot = ws.tjreg;
@@ -1594,12 +1607,13 @@ int run_fit_known_shape(const smplfit_handle* h, const float* betas, int nb, con
   ja.Gprev = ws.G;
   for (int it = 0; it <= o.num_iter; ++it) {
     launch_forward_joint(d, fa, ws, B, st);
-    if (bm) {
+    if (r.bm) {
       if (int rc = launch_gemm(d, ws, B, st, true)) return rc;
-      launch_jd_transpose(d, ws, B, st);
+      if (r.jd_transpose) launch_jd_transpose(d, ws, B, st);
       // the posed mesh is kept (in place, ws.vpT) where it is read: regressed joints, and the alignment sums behind the
       // last pass
-#define SF_CALL_LBS(S_, KW_) launch_lbs_bm<S_, KW_>(h, ws, B, st, !joints || it == o.num_iter, false, vweighted, it == o.num_iter, joints ? 0 : 1)
+#define SF_CALL_LBS(S_, KW_) \
+  launch_lbs_bm<S_, KW_>(h, ws, B, st, r.psum_combine, !joints || it == o.num_iter, false, vweighted, it == o.num_iter, joints ? 0 : 1)
       SF_DISPATCH_SKW(d, SF_CALL_LBS);
 #undef SF_CALL_LBS
     } else {
@@ -1623,7 +1637,7 @@ int run_fit_known_shape(const smplfit_handle* h, const float* betas, int nb, con
   sa.with_scale = o.scale_fit;
   sa.regressed = joints ? 0 : 1;
   sa.scale_out = o.scale_fit ? scale_out : nullptr;
-  if (bm) {
+  if (r.bm) {
     AlignArgs aa{};
     aa.tj = sa.tj;
     aa.jw = sa.jw;
@@ -1665,8 +1679,10 @@ int run_fit_known_shape(const smplfit_handle* h, const float* betas, int nb, con
 //   forward of the INPUT model on the batch-major kernels (k_forward_joint, transposed GEMM, joint-row transpose,
 //   forward-only LBS pass: the posed vertices stay in the input model's instance-innermost buffer),
 //   k_transfer_bm into the OUTPUT model's target stream + slab sums, then the tail of launch_layout_bm.
-int launch_convert_source(const ConvertSource& src, const DevModel& d, const Workspace& ws, int B, hipStream_t st) {
+// r: the route of the fit the targets feed
+int launch_convert_source(const ConvertSource& src, const Route& r, const Workspace& ws, int B, hipStream_t st) {
   const smplfit_convert_plan& pl = *src.plan;
+  const DevModel& d = pl.out->d;
   const DevModel& di = pl.in->d;
   const Workspace& wi = src.wsi;
   const int Mp = (int)align_up((size_t)B, 128);
@@ -1680,16 +1696,12 @@ int launch_convert_source(const ConvertSource& src, const DevModel& d, const Wor
   launch_forward_joint(di, fa, wi, B, st);
   if (int rc = launch_gemm(di, wi, B, st, true)) return rc;
   launch_jd_transpose(di, wi, B, st);
-  {
-    const ShareView sv = share_view(pl.in, sf::kShareLbsAll, B);
-    const dim3 grid = share_grid(sv, Mp);
-    if (int rc_f = launch_lbs_fwd_bm(di, sv, wi, B, Mp, st)) return rc_f;
-  }
+  if (int rc_f = launch_lbs_fwd_bm(di, share_view(pl.in, sf::kShareLbsAll, B), wi, B, Mp, st)) return rc_f;
   TransferTabs tt{pl.d_oslot, pl.d_start, pl.d_islot, pl.d_w, d.V};
   hipLaunchKernelGGL(k_transfer_bm, dim3(pl.nslab, Mp / 64), dim3(256), 0, st, tt, wi.vpT, di.Vp, ws.tT, d.Vp, ws.resP, Mp);
   hipLaunchKernelGGL(k_mean_finish, dim3(Mp / 64), dim3(64 * kMeanWaves), 0, st, d, (const float*)nullptr, ws.resP, ws, B, Mp,
                      pl.nslab);
-  launch_template_partsum_bm(pl.out, ws, B, st);
+  launch_template_partsum_bm(pl.out, ws, B, st, false, r.psum_combine);
   return 0;
 }
 
@@ -1924,7 +1936,7 @@ int smplfit_create(const smplfit_model_desc* desc, int flags, smplfit_handle** o
     return SMPLFIT_OK;
   }
   // stage images of the tiled split-bf16 GEMM (94 MB for SMPL-X): only for a model whose fits can take the
-  // batch-major path (the only launches that read them; the structural part of bm_applies)
+  // batch-major path (the only launches that read them; the structural part of route_of's batch-major rule)
   if ((h->t.KW == 4 || h->t.KW == 8) && sf::bm_shape_count(h->t.S) && h->t.wsum_dev <= 1e-5f)
     sf::build_tiled_gemm_images(h->t);
   const sf::HostTables& t = h->t;
@@ -2181,7 +2193,8 @@ int smplfit_get_info(const smplfit_handle* h, smplfit_info* info) {
   info->adj_last_level = t.adj_last_level;
   info->has_device = h->has_device ? 1 : 0;
   info->gemm_vgprs = h->gemm_vgprs;
-  info->vertex_path = t.general ? SMPLFIT_PATH_GENERAL : bm_applies(h) ? SMPLFIT_PATH_BATCH_MAJOR : SMPLFIT_PATH_WAVE;
+  // (the path of a default fit; whether it is batch-major does not depend on the batch)
+  info->vertex_path = t.general ? SMPLFIT_PATH_GENERAL : route_of(h, 1, CallShape{}).bm ? SMPLFIT_PATH_BATCH_MAJOR : SMPLFIT_PATH_WAVE;
   info->share_fallback = t.share_fallback;
   return SMPLFIT_OK;
 }
@@ -2244,7 +2257,7 @@ int smplfit_get_share_table(const smplfit_handle* h, int kind, int what, int32_t
 
 int smplfit_pick_share_mult(const smplfit_handle* h, int kind, int batch) {
   if (!h || h->t.shares.empty() || kind < 0 || kind >= sf::kShareKinds || batch <= 0) return -1;
-  return sf::pick_share_mult(h->t, share_index(kind, batch), (int)align_up((size_t)batch, 128) / 64, tune().bm_slots);
+  return sf::pick_share_mult(h->t, share_index(kind, batch), (int)align_up((size_t)batch, 128) / 64, tune().share_slots);
 }
 
 size_t smplfit_workspace_bytes(const smplfit_handle* h, int batch) {
@@ -2380,7 +2393,7 @@ int smplfit_forward_ex_f32(const smplfit_handle* h, const smplfit_forward_args* 
   fa.joints = joints;
   fa.orient = args->orientations;
   launch_forward_joint(d, fa, ws, batch, st);
-  if (vertices && bm_applies(h) && tune().bm_forward) {
+  if (vertices && route_of(h, batch, {Entry::kForward}).bm) {
     // the batch-major kernels (round 4; what the input side of a fused conversion runs): shape / translation rows, the
     // transposed GEMM, the forward-only LBS pass over every slot (posed vertices in place in ws.vpT), and the inverse
     // of the target layout into the caller's (B, V, 3)
@@ -2390,7 +2403,6 @@ int smplfit_forward_ex_f32(const smplfit_handle* h, const smplfit_forward_args* 
     if (int rc2 = launch_gemm(d, ws, batch, st, true)) return rc2;
     launch_jd_transpose(d, ws, batch, st);
     const ShareView sv = share_view(h, sf::kShareLbsAll, batch);
-    const dim3 grid = share_grid(sv, Mp);
     if (int rc_f = launch_lbs_fwd_bm(d, sv, ws, batch, Mp, st)) return rc_f;
     hipLaunchKernelGGL(k_unlayout_vertices, dim3((d.V + kSlabV - 1) / kSlabV, Mp / 64), dim3(256), (size_t)64 * kSlabRow * 4, st, d,
                        ws.vpT, vertices, batch);
@@ -2462,18 +2474,10 @@ int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solv
   // the batch-major vertex kernels (round 4): streams, transposed GEMM, residual pass + pair-Gram (unit weights) or the
   // accumulate kernel (vertex weights in the solve / a scale unknown), as one iteration of fit()
   const bool scaled = o.scale_mode != 0;
-  const bool bm = bm_applies(h) && tune().bm_known_pose &&
-                  (!vertex_weights || (tune().bm_weighted && (!eff_v || (d.S == 10 && d.KW == 4)))) &&
-                  (!scaled || (tune().bm_scale && d.S == 10 && d.KW == 4));
+  const Route r = route_of(h, batch, {Entry::kShapeSolve, joints, vertex_weights != nullptr, eff_v, o.scale_mode, o.share_beta != 0});
   const int Mp = (int)align_up((size_t)batch, 128);
-  if (bm) {
-    const int nslab = (d.V + kSlabV - 1) / kSlabV;
-    if (eff_v)
-      hipLaunchKernelGGL(k_layout_weights, dim3((d.V + 63) / 64 + 1, Mp / 64), dim3(256), 0, st, d, vertex_weights, ws.wT, batch);
-    hipLaunchKernelGGL(k_layout_targets, dim3(nslab, Mp / 64), dim3(256), (size_t)64 * kSlabRow * 4, st, d, args->target_vertices,
-                       ws.tT, ws.resP, batch, Mp);
-    hipLaunchKernelGGL(k_mean_finish, dim3(Mp / 64), dim3(64 * kMeanWaves), 0, st, d, args->target_joints, ws.resP, ws, batch, Mp,
-                       nslab);
+  if (r.bm) {  // (the weight stream only where the weights enter the solve)
+    launch_layout_bm(h, args->target_vertices, args->target_joints, ws, batch, st, eff_v ? vertex_weights : nullptr, false, true);
   } else {
     launch_center_sort(d, args->target_vertices, args->target_joints, vertex_weights, ws, batch, st);
   }
@@ -2491,22 +2495,19 @@ int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solv
   ja.vertex_sa_closed_form = (eff_v || d.general) ? 0 : 1;  // (the general accumulate sums SA itself)
   if (!joints) hipMemsetAsync(ws.tjreg, 0, (size_t)batch * d.J * 3 * 4, st);
   launch_joint_stage(d, ja, ws, batch, st);
-  if (bm) {
+  if (r.bm) {
     if (int rc2 = launch_gemm(d, ws, batch, st, true)) return rc2;
-    launch_jd_transpose(d, ws, batch, st);
+    if (r.jd_transpose) launch_jd_transpose(d, ws, batch, st);
     if (scaled) launch_accum_w_bm(h, ws, batch, st, eff_v, true);
     else if (eff_v) launch_accum_w_bm(h, ws, batch, st);
-    else launch_residual_bm(h, ws, batch, st, fused_solve(h, batch, o, 1, false) ? 3 : 7);
-    const int pair_kp = (!eff_v && !scaled) ? 1 : 0;
-    rc = enqueue_solve(d, ws, batch, o, joints, eff_v, eff_j, joint_weights, pair_kp, use_ref, scaled, st, scaled,
-                       fused_solve(h, batch, o, pair_kp, scaled) ? h : nullptr);
+    else launch_residual_bm(h, ws, batch, st, r.solve_bm ? 3 : 7);
   } else {
     launch_gemm(d, ws, batch, st);
-    if (int rc = launch_accum_any(d, ws, batch, eff_v, st, gjr ? ja.tj : nullptr, gjr && eff_j ? joint_weights : nullptr, scaled))
+    if (int rc = launch_accum_any(d, ws, batch, eff_v, r.pair_in, st, gjr ? ja.tj : nullptr, gjr && eff_j ? joint_weights : nullptr,
+                                  scaled))
       return rc;
-    rc = enqueue_solve(d, ws, batch, o, joints, eff_v, eff_j, joint_weights, (!eff_v && !d.general && use_pair_form()) ? 1 : 0,
-                       use_ref, scaled, st);
   }
+  rc = enqueue_solve(h, r, ws, batch, o, joints, eff_v, eff_j, joint_weights, use_ref, scaled, st);
   if (rc) return rc;
   // a scaled solve leaves the shape as the reference returns it (undivided, :1277-1283) in beta_out
   hipLaunchKernelGGL(k_emit_solution, dim3((batch + 255) / 256), dim3(256), 0, st, ws,
@@ -2517,9 +2518,8 @@ int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solv
   if (args->joints_out)
     hipLaunchKernelGGL(k_copy, dim3(64), dim3(256), 0, st, ws.rjoints, args->joints_out,
                        (size_t)batch * d.J * 3);
-  if (args->vertices_out && bm) {  // the mesh at the solution: forward-only LBS pass + the inverse of the target layout
+  if (args->vertices_out && r.bm) {  // the mesh at the solution: forward-only LBS pass + the inverse of the target layout
     const ShareView sv = share_view(h, sf::kShareLbsAll, batch);
-    const dim3 grid = share_grid(sv, Mp);
     if (int rc_f = launch_lbs_fwd_bm(d, sv, ws, batch, Mp, st)) return rc_f;
     hipLaunchKernelGGL(k_unlayout_vertices, dim3((d.V + kSlabV - 1) / kSlabV, Mp / 64), dim3(256), (size_t)64 * kSlabRow * 4, st, d,
                        ws.vpT, args->vertices_out, batch);
@@ -2601,7 +2601,8 @@ int smplfit_convert_plan_create(const smplfit_handle* in, const smplfit_handle* 
     return fail(SMPLFIT_ERR_HIP, "smplfit_convert_plan_create: both handles need a device");
   if (transfer ? (transfer->v_in != in->t.V || transfer->v_out != out->t.V) : (in->t.V != out->t.V))
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_convert_plan_create: vertex counts of the models and the matrix disagree");
-  if (!bm_applies(in) || !bm_applies(out) || !out->t.has_regressor)
+  const CallShape conv{Entry::kConvert, false};  // (whether the route is batch-major does not depend on the batch)
+  if (!route_of(in, 1, conv).bm || !route_of(out, 1, conv).bm || !out->t.has_regressor)
     return fail(SMPLFIT_ERR_UNSUPPORTED,
                 "smplfit_convert_plan_create: the fused conversion needs the batch-major kernels on both models "
                 "(<= 4 skinning weights per vertex, 10 betas, >= 1024 vertices) and the output model's joint "
@@ -2660,7 +2661,8 @@ int smplfit_convert_f32(const smplfit_convert_plan* p, const smplfit_convert_arg
   if (a->shape_betas && (a->num_betas_given < 0 || a->num_betas_given > p->in->t.num_betas()))
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_convert_f32: more betas than the input model holds; slice first");
   // the plan was made while the batch-major path applied; a later smplfit_reload_options may have switched it off
-  if (!bm_applies(p->in) || !bm_applies(p->out))
+  const CallShape conv{Entry::kConvert, false};
+  if (!route_of(p->in, 1, conv).bm || !route_of(p->out, a->batch, conv).bm)
     return fail(SMPLFIT_ERR_UNSUPPORTED, "smplfit_convert_f32: the batch-major path is switched off");
   smplfit_fit_args f{};
   f.batch = a->batch;
@@ -2701,45 +2703,45 @@ int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, i
   hipEvent_t e0, e1;
   SF_HIP_TRY(hipEventCreate(&e0));
   SF_HIP_TRY(hipEventCreate(&e1));
-  const bool bm = bm_applies(h);  // time the kernels the default fit runs
+  // time the kernels the default fit runs: target joints given, unit weights, no scale unknown, no shared shape
+  const Route r = route_of(h, batch, CallShape{});
   const int Mp = (int)align_up((size_t)batch, 128);
   auto once = [&]() -> int {
     switch (kernel_id) {
-      case SMPLFIT_KERNEL_POSEDIRS_GEMM: return launch_gemm(d, ws, batch, st, bm);
+      case SMPLFIT_KERNEL_POSEDIRS_GEMM: return launch_gemm(d, ws, batch, st, r.bm);
       case SMPLFIT_KERNEL_PAIR_GRAM:
-        if (!bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "pair-Gram kernel: batch-major path not active");
+        if (!r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "pair-Gram kernel: batch-major path not active");
         launch_residual_bm(h, ws, batch, st, 2);
         return 0;
       case SMPLFIT_KERNEL_TRANSPOSE:
-        if (!bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "layout kernel: batch-major path not active");
+        if (!r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "layout kernel: batch-major path not active");
         // the hook has no target pointer: ws.tvs (unused on this path, >= B*V*3 floats) stands in for the rows
         hipLaunchKernelGGL(k_layout_targets, dim3((d.V + kSlabV - 1) / kSlabV, Mp / 64), dim3(256),
                            (size_t)64 * kSlabRow * 4, st, d, ws.tvs, ws.tT, ws.resP, batch, Mp);
         return 0;
       case SMPLFIT_KERNEL_TEMPLATE_PARTSUM:
-        if (!bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "template part sums: batch-major path not active");
+        if (!r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "template part sums: batch-major path not active");
         {
           const ShareView sv = share_view(h, sf::kShareLbsUsed, batch);
           hipLaunchKernelGGL(k_template_partsum_bm<false>, share_grid(sv, Mp), dim3(64 * kBW), 0, st, d, sv, ws, batch, Mp);
         }
         return 0;
       case SMPLFIT_KERNEL_SHAPE_ACCUM: {
-        if (bm) {
+        if (r.bm) {
           launch_residual_bm(h, ws, batch, st, 1);
           return 0;
         }
-        if (int rc = launch_accum_any(d, ws, batch, false, st, gen_joint_rows(d) ? ws.tjc : nullptr)) return rc;
+        if (int rc = launch_accum_any(d, ws, batch, false, r.pair_in, st, gen_joint_rows(d) ? ws.tjc : nullptr)) return rc;
         return 0;
       }
       case SMPLFIT_KERNEL_SHAPE_SOLVE:
         // (the default fit's solve: k_solve_bm on the partial sums the last fit left, else the wave-per-instance stage)
-        if (bm && solve_bm_applies(h, batch)) launch_solve_bm(h, ws, batch, st, 1.0f, 0.0f, 1.0f, 0, prologue_bm_applies(h, batch));
-        else launch_shape_solve(d, ws, batch, st, 1.0f, 0.0f, 1.0f, (bm || use_pair_form()) ? 1 : 0, 0);
+        if (r.solve_bm) launch_solve_bm(h, r.solve_plan, ws, batch, st, 1.0f, 0.0f, 1.0f, 0, r.prologue_bm);
+        else launch_shape_solve(d, ws, batch, st, 1.0f, 0.0f, 1.0f, r.pair_in, 0);
         return 0;
       case SMPLFIT_KERNEL_LBS_PARTSUM: {
-        if (bm) {
-#define SF_CALL_LBS(S_, KW_) \
-  launch_lbs_bm<S_, KW_>(h, ws, batch, st, false, false, false, false, -1, !rot_bm_applies(h, prologue_bm_applies(h, batch)))
+        if (r.bm) {
+#define SF_CALL_LBS(S_, KW_) launch_lbs_bm<S_, KW_>(h, ws, batch, st, r.psum_combine, false, false, false)
           SF_DISPATCH_SKW(d, SF_CALL_LBS);
 #undef SF_CALL_LBS
           return 0;
@@ -2760,10 +2762,7 @@ int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, i
         ja.joint_block_weighted = 0;
         ja.vertex_sa_closed_form = d.general ? 0 : 1;
         // (what a default fit runs: the rotations + k_prologue_bm where that applies)
-        {
-          const bool pro_h = bm && prologue_bm_applies(h, batch);
-          launch_joint_stage_fit(h, ja, ws, batch, st, pro_h, rot_bm_applies(h, pro_h) ? sf::kShareLbsUsed : -1, 1);
-        }
+        launch_joint_stage_fit(h, ja, ws, batch, st, r.prologue_bm, r.rot_kind_next, 1);
         return 0;
       }
       case SMPLFIT_KERNEL_REFINE: {  // (outputs into the workspace: ws.tvs is unused between fits)
@@ -2772,7 +2771,7 @@ int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, i
         ra.rj_term = ws.rjoints;
         ra.jw = nullptr;
         ra.final_adjust = 1;
-        float* scratch = bm ? ws.tvs : ws.rverts;
+        float* scratch = r.bm ? ws.tvs : ws.rverts;
         ra.pose = scratch;
         ra.betas = scratch + (size_t)batch * d.J * 3;
         ra.trans = ra.betas + (size_t)batch * d.S;
@@ -2780,36 +2779,35 @@ int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, i
         ra.orient = ra.trans + (size_t)batch * 3;  // (a fit always writes the orientations and the relative rotations)
         ra.rel = ra.orient + (size_t)batch * d.J * 9;
         // (what a default fit runs: k_refine_bm on the rows of the last LBS pass where that applies)
-        if (refine_bm_applies(h, bm && prologue_bm_applies(h, batch))) launch_refine_bm(h, ra, share_view(h, sf::kShareLbsAdj, batch), ws, batch, st);
+        if (r.refine_bm) launch_refine_bm(h, ra, share_view(h, r.refine_kind, batch), ws, batch, st);
         else launch_refine(d, ra, ws, batch, st);
         return 0;
       }
       case SMPLFIT_KERNEL_GRAM_COMBINE:
-        if (!bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "normal-equation combine: batch-major path not active");
-        if (solve_bm_applies(h, batch)) return fail(SMPLFIT_ERR_UNSUPPORTED, "normal-equation combine: part of k_solve_bm (SMPLFIT_KERNEL_SHAPE_SOLVE)");
+        if (!r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "normal-equation combine: batch-major path not active");
+        if (r.solve_bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "normal-equation combine: part of k_solve_bm (SMPLFIT_KERNEL_SHAPE_SOLVE)");
         launch_residual_bm(h, ws, batch, st, 4);
         return 0;
       case SMPLFIT_KERNEL_PSUM_COMBINE:
-        if (!bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "part-sum combine: batch-major path not active");
-        if (rot_bm_applies(h, prologue_bm_applies(h, batch))) return fail(SMPLFIT_ERR_UNSUPPORTED, "part-sum combine: k_rotations_bm / k_refine_bm add the rows themselves");
+        if (!r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "part-sum combine: batch-major path not active");
+        if (!r.psum_combine) return fail(SMPLFIT_ERR_UNSUPPORTED, "part-sum combine: k_rotations_bm / k_refine_bm add the rows themselves");
         launch_psum_combine(d, share_view(h, sf::kShareLbsUsed, batch), ws, batch, Mp, st);
         return 0;
       case SMPLFIT_KERNEL_JD_TRANSPOSE:
-        if (!bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "joint-row transpose: batch-major path not active");
-        if (prologue_bm_applies(h, batch)) return fail(SMPLFIT_ERR_UNSUPPORTED, "joint-row transpose: k_prologue_bm writes ws.jdT itself");
+        if (!r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "joint-row transpose: batch-major path not active");
+        if (!r.jd_transpose) return fail(SMPLFIT_ERR_UNSUPPORTED, "joint-row transpose: k_prologue_bm writes ws.jdT itself");
         launch_jd_transpose(d, ws, batch, st);
         return 0;
       case SMPLFIT_KERNEL_MEAN_FINISH:
-        if (!bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "mean pass: batch-major path not active");
+        if (!r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "mean pass: batch-major path not active");
         // (the slab sums of the layout pass are gone from ws.resP by now: the values are arbitrary, the work is the same;
         // the outputs go where the fit left them)
         hipLaunchKernelGGL(k_mean_finish, dim3(Mp / 64), dim3(64 * kMeanWaves), 0, st, d, ws.rjoints, ws.resP, ws, batch, Mp,
                            (d.V + kSlabV - 1) / kSlabV);
         return 0;
       case SMPLFIT_KERNEL_LBS_LAST:
-        if (!bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "last LBS pass: batch-major path not active");
-#define SF_CALL_LBS(S_, KW_) \
-  launch_lbs_bm<S_, KW_>(h, ws, batch, st, false, true, false, false, -1, !refine_bm_applies(h, prologue_bm_applies(h, batch)))
+        if (!r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "last LBS pass: batch-major path not active");
+#define SF_CALL_LBS(S_, KW_) launch_lbs_bm<S_, KW_>(h, ws, batch, st, r.psum_combine_last, false, true, false)
         SF_DISPATCH_SKW(d, SF_CALL_LBS);
 #undef SF_CALL_LBS
         return 0;
@@ -2819,16 +2817,14 @@ int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, i
   // Each timed launch runs right after the kernel that precedes it inside a fit (K2 before K3, K3
   // before K5), so caches are in the state the kernel sees in situ; only the target kernel is
   // bracketed by the two events.
-  const bool nopre = getenv("SMPLFIT_TIME_NOPRE") != nullptr;  // (measurement hook only: the kernel without its producer in front)
   auto pre = [&]() {
-    if (nopre) return 0;
-    if (kernel_id == SMPLFIT_KERNEL_SHAPE_ACCUM) launch_gemm(d, ws, batch, st, bm);
-    if ((kernel_id == SMPLFIT_KERNEL_LBS_PARTSUM || kernel_id == SMPLFIT_KERNEL_LBS_LAST) && bm) {
-      if (solve_bm_applies(h, batch)) launch_solve_bm(h, ws, batch, st, 1.0f, 0.0f, 1.0f, 0, prologue_bm_applies(h, batch));
-      else launch_shape_solve(d, ws, batch, st, 1.0f, 0.0f, 1.0f, 1, 0);
+    if (kernel_id == SMPLFIT_KERNEL_SHAPE_ACCUM) launch_gemm(d, ws, batch, st, r.bm);
+    if ((kernel_id == SMPLFIT_KERNEL_LBS_PARTSUM || kernel_id == SMPLFIT_KERNEL_LBS_LAST) && r.bm) {
+      if (r.solve_bm) launch_solve_bm(h, r.solve_plan, ws, batch, st, 1.0f, 0.0f, 1.0f, 0, r.prologue_bm);
+      else launch_shape_solve(d, ws, batch, st, 1.0f, 0.0f, 1.0f, r.pair_in, 0);
     }
-    if (kernel_id == SMPLFIT_KERNEL_LBS_PARTSUM && !bm) {
-      if (int rc = launch_accum_any(d, ws, batch, false, st)) return rc;
+    if (kernel_id == SMPLFIT_KERNEL_LBS_PARTSUM && !r.bm) {
+      if (int rc = launch_accum_any(d, ws, batch, false, r.pair_in, st)) return rc;
     }
     return 0;
   };

@@ -49,7 +49,6 @@ SMPLFIT_LIB=build_ab/libwstamp.so timeout 200 python tools/wave_stamps.py 4096 >
 # overlap probe (pair-Gram under the residual pass), the result gather (world-1 RCCL: overlapped / in line / none)
 { for a in "4096 smpl" "16384 smpl" "4096 smplx"; do SMPLFIT_LIB=build_ab/libsstamp.so timeout 200 python tools/solve_stamps.py $a 2>&1 < /dev/null | grep -v amdgpu.ids; done; } > $F/solve_stamps.txt; head -9 $F/solve_stamps.txt
 { timeout 300 python tools/solve_ab_time.py smpl < /dev/null; timeout 300 python tools/solve_ab_time.py smplx 2048 4096 8192 < /dev/null; } 2>&1 | grep -v amdgpu.ids > $F/solve_ab_time.txt; cat $F/solve_ab_time.txt
-timeout 200 python tools/overlap_probe.py smpl 4096 2>&1 < /dev/null | grep -v amdgpu.ids > $F/overlap_probe.txt; cat $F/overlap_probe.txt
 timeout 300 python bench.py --full --steps 50 --warmup 5 --collective-always --no-cpu-baseline > $F/bench_collective.json 2>/dev/null < /dev/null; python -c "
 import json
 d=[json.loads(l) for l in open('$F/bench_collective.json') if l.startswith('{')][0]; print('collective-always', d['value'], d['ms_per_step'], json.dumps(d['multi_gpu'])[:900])"
