@@ -282,19 +282,6 @@ __device__ __forceinline__ void rec_arrived_request_next(const float* brec, cons
     load_rec<S, NJ>(brec, vnext, next);
   }
 }
-// Debug build -DSMPLFIT_WAVE_STAMPS (tools/wave_stamps.py): every wave of the two vertex passes records the wall clock
-// (100 MHz, the same counter on every CU) at entry, at its first vertex step, behind its last one and at exit, and
-// where it ran (HW_ID) — when the waves of a launch start and finish.
-#ifdef SMPLFIT_WAVE_STAMPS
-__device__ unsigned long long g_wave_stamps[8192 * 5];
-#define SF_WSTAMP(idx, k) do { if (lane == 0) g_wave_stamps[(size_t)(idx) * 5 + (k)] = wall_clock64(); } while (0)
-#define SF_WSTAMP_HW(idx) do { if (lane == 0) { unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw)); \
-    unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc)); \
-    g_wave_stamps[(size_t)(idx) * 5 + 4] = ((unsigned long long)xcc << 32) | hw; } } while (0)
-#else
-#define SF_WSTAMP(idx, k) do { } while (0)
-#define SF_WSTAMP_HW(idx) do { } while (0)
-#endif
 
 // K5 (batch-major): vertices at the solved shape + part sums against the targets.
 // grid (Mp/64, ncells / mult / kBW), block 64 * kBW: wave = one share (mult cells) of one instance block.  Output: a row of ws.psumP
@@ -708,9 +695,6 @@ __global__ __launch_bounds__(64 * kBW) __attribute__((amdgpu_waves_per_eu((NJ ==
   const int b = bcol < B ? bcol : B - 1;
   const int Np = (J * STRIDE + 63) / 64 * 64;
   const float* jdb = ws.jdT + (size_t)blk * Np * 64 + lane;
-  const int wstamp = (blockIdx.y * gridDim.x + blockIdx.x) * kBW + wave;  // (debug builds)
-  SF_WSTAMP(wstamp, 0);
-  SF_WSTAMP_HW(wstamp);
   // the wave's moment accumulators (the slots of a segment) start at zero
   float* macc = smem + (size_t)wave * NM * 64 + lane;
 #pragma unroll
@@ -841,12 +825,10 @@ __global__ __launch_bounds__(64 * kBW) __attribute__((amdgpu_waves_per_eu((NJ ==
         r = i < len ? vb + i : r;
         return r;
       };
-      if (p == 0) SF_WSTAMP(wstamp, 1);
       for (int i = 0; i < l2; i += 2) {
         step(vb + i, at(i + 1), at(i + 2), rA, recA, kRecAhead ? recB : recA);
         step(at(i + 1), at(i + 2), at(i + 3), rB, kRecAhead ? recB : recA, recA);
       }
-      if (p + 1 == np) SF_WSTAMP(wstamp, 2);
       // end of the piece: its four moment sums go to the wave's accumulator rows of the joints' segment slots (two
       // padding joints of a piece may share a slot: the adds are sequential)
 #pragma unroll
@@ -891,7 +873,6 @@ __global__ __launch_bounds__(64 * kBW) __attribute__((amdgpu_waves_per_eu((NJ ==
       pc += RS;
     }
   }
-  SF_WSTAMP(wstamp, 3);
 }
 
 // K3g (batch-major): the Gramian of the vertex block from the rotations alone (the "pair-Gram" form of
@@ -2006,20 +1987,6 @@ __global__ __launch_bounds__(256) void k_gt_to_g(Workspace ws, int J, int B, int
 // ------------------------------------------------------------------------------------------------
 constexpr int kSolveWaves = 8;  // (8 waves: 256 registers per lane — at 16 waves / 128 registers the kernel spilled, and in this
                                 // latency-bound code every reload is a memory round trip: phase D took 10 us)
-// debug build -DSMPLFIT_SOLVE_STAMPS (tools/solve_stamps.py): thread 0 of every workgroup records the wall clock at the
-// phase boundaries of k_solve_bm
-#ifdef SMPLFIT_SOLVE_STAMPS
-__device__ unsigned long long g_solve_stamps[4096 * 8];
-#define SF_SSTAMP_T(k, t) do { if (threadIdx.x == (t) && blockIdx.x < 4096) g_solve_stamps[(size_t)blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
-#define SF_SSTAMP(k) SF_SSTAMP_T(k, 0)
-#else
-#define SF_SSTAMP(k) do { } while (0)
-#define SF_SSTAMP_T(k, t) do { } while (0)
-#endif
-// timing-only builds (wrong results): SMPLFIT_SOLVE_ABL bit 8 drops the scattered stores of phase D
-#ifndef SMPLFIT_SOLVE_ABL
-#define SMPLFIT_SOLVE_ABL 0
-#endif
 constexpr int kSolveT3 = 64;  // most moment rows of a joint (coarse residual table) the kernel takes; the launch checks
 __host__ __device__ constexpr size_t solve_bm_lds_bytes(int S, int IB, int J, int ncells, int maxn, bool stage) {
   return (size_t)IB * (8 * (sf::kSolveParts * S + S * S + 3 * S + 2 * (S + 3)) +
@@ -2043,7 +2010,7 @@ __device__ __forceinline__ f4 buf_load4(__amdgpu_buffer_rsrc_t r, uint32_t voff,
   return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }
 
-// What shaped the kernel (phase stamps of a debug build, tools/solve_stamps.py): it is NOT bound by bytes or by memory
+// What shaped the kernel (phase stamps of a debug build, since removed: profiles/README.md, round 6 files): it is NOT bound by bytes or by memory
 // latency but by how many vector-memory instructions a CU has to issue — the partial sums are rows of Mp floats, a
 // workgroup of 16 instances owns 64 bytes of each of ~3600 rows, and a wave-wide dword request (four 64-byte pieces
 // of four rows) occupied the CU's address path for ~20 cycles: 900 of them were 9 us, the address arithmetic and the
@@ -2078,10 +2045,6 @@ __global__ __launch_bounds__(64 * kSolveWaves) void k_solve_bm(DevModel m, Share
   const int wg = blockIdx.x, wslot = wg >> 3;
   const int grp = (((wslot >> 2) << 3) + (wg & 7)) * 4 + (wslot & 3);
   if (grp * IB >= B) return;
-  SF_SSTAMP(0);
-#ifdef SMPLFIT_SOLVE_STAMPS
-  if (threadIdx.x == 0 && blockIdx.x < 4096) g_solve_stamps[(size_t)blockIdx.x * 8 + 6] = __builtin_readcyclecounter();
-#endif
   const int tid = threadIdx.x, lane = tid & 63, quad = lane & 3;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int slot = wave * 16 + (lane >> 2);  // one of 256 task slots; the lane holds the instances 4 quad .. 4 quad + 3 of it
@@ -2256,7 +2219,6 @@ __global__ __launch_bounds__(64 * kSolveWaves) void k_solve_bm(DevModel m, Share
     for (int q = early ? slot + NSLOT : slot; q < nb; q += NSLOT) bundle(q);
     stage_store();
   }
-  SF_SSTAMP(1);
   __syncthreads();
   // ---------------- phase B: a (task, four instances) per lane, like the lanes of sf::solve_stage
   {
@@ -2334,7 +2296,6 @@ __global__ __launch_bounds__(64 * kSolveWaves) void k_solve_bm(DevModel m, Share
         chd[e * IB + i0 + 3] = (double)acc.w + fjd[3];
       }
     }
-    SF_SSTAMP(2);
     __syncthreads();
     // ---------------- phase B': the right-hand side (and Sb / W) — needs the r2p of every run
     for (int t = slot; t < S + 3 + 3 * S; t += NSLOT) {
@@ -2367,7 +2328,6 @@ __global__ __launch_bounds__(64 * kSolveWaves) void k_solve_bm(DevModel m, Share
       }
     }
   }
-  SF_SSTAMP(3);
   __syncthreads();
   // ---------------- phase C: one lane per instance — L D L^T of the system in its LDS column (sf::ldlt_solve: the same
   // expressions; column by column, a non-positive pivot becomes NaN), substitutions in registers
@@ -2426,10 +2386,6 @@ __global__ __launch_bounds__(64 * kSolveWaves) void k_solve_bm(DevModel m, Share
       if (bcol < B) ws.trans[(size_t)b * 3 + c] = (float)v;
     }
   }
-  SF_SSTAMP(4);
-#ifdef SMPLFIT_SOLVE_STAMPS
-  if (threadIdx.x == 0 && blockIdx.x < 4096) g_solve_stamps[(size_t)blockIdx.x * 8 + 7] = __builtin_readcyclecounter();
-#endif
   __syncthreads();
   // ---------------- phase D: joints (:1093-1098) and skinning translations T0 + T' beta (:1099-1101) at the solution
   // (explicit fused multiply-adds: what the compiler makes of sf::solve_stage's loops; left to itself it pairs the
@@ -2494,14 +2450,11 @@ __global__ __launch_bounds__(64 * kSolveWaves) void k_solve_bm(DevModel m, Share
       for (int u = 0; u < 4; ++u)
         if (c0 + u < B) {
           if (c0 + 3 >= B) jbT[(size_t)(j * 4 + c) * 64 + u] = jbs[u];
-          if constexpr ((SMPLFIT_SOLVE_ABL & 8) == 0) {
-            ws.jb[((size_t)(c0 + u) * J + j) * 4 + c] = jbs[u];
-            ws.rjoints[(size_t)(c0 + u) * J * 3 + idx] = rjs[u];
-          } else if (jbs[u] == 123.456f) ws.rjoints[0] = rjs[u];
+          ws.jb[((size_t)(c0 + u) * J + j) * 4 + c] = jbs[u];
+          ws.rjoints[(size_t)(c0 + u) * J * 3 + idx] = rjs[u];
         }
     }
   }
-  SF_SSTAMP(5);
 }
 
 // ------------------------------------------------------------------------------------------------

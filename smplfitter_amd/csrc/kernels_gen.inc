@@ -616,9 +616,6 @@ __global__ __launch_bounds__(64 * NW) void k_gen_accum_mfma(DevModel m, Workspac
   };
   // ---- the update: a k-step is two rows of the tile (lanes 0-31 the even one, 32-63 the odd one); rwt: the rows' weights
   auto update = [&](const float* rwt) {
-#if defined(SMPLFIT_GEN_DBG) && SMPLFIT_GEN_DBG == 1  // (timing experiment: no matrix products)
-    return;
-#endif
     if (nblk == 0) return;
     // the operands of k-step kk + 1 are requested before the products of k-step kk are issued (two register sets; the
     // scheduling barriers keep the compiler from sinking every read next to its product again: read, wait, product, seven
@@ -655,12 +652,6 @@ __global__ __launch_bounds__(64 * NW) void k_gen_accum_mfma(DevModel m, Workspac
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-#if defined(SMPLFIT_GEN_DBG) && SMPLFIT_GEN_DBG == 3
-  long long tacc[6] = {0, 0, 0, 0, 0, 0}, tlast = __builtin_readcyclecounter();
-#define SF_GSTAMP(k) do { const long long now_ = __builtin_readcyclecounter(); tacc[k] += now_ - tlast; tlast = now_; } while (0)
-#else
-#define SF_GSTAMP(k)
-#endif
   // ---- the entries leave the accumulators for the record (and the scale unknown's extra sums), as fp64 sums of fp32
   // partial sums: every flush_every blend passes (64 / 128 vertices each) the accumulators are ADDED to the record and
   // restart from zero.  One fp32 accumulator per entry over all 3 V rows is a chain of 20 k additions: good for the
@@ -724,7 +715,6 @@ __global__ __launch_bounds__(64 * NW) void k_gen_accum_mfma(DevModel m, Workspac
   request(0);
   __syncthreads();
   for (int sv0 = 0; sv0 < V; sv0 += SV) {
-    SF_GSTAMP(5);
     if (tid < SV) {  // the vertex's skinning pairs, blended rotation, residual (bodyfitter.py:1136-1160)
       const int i = sv0 + tid;
       float Rv[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, T0[3] = {0, 0, 0};
@@ -766,12 +756,10 @@ __global__ __launch_bounds__(64 * NW) void k_gen_accum_mfma(DevModel m, Workspac
       }
     }
     __syncthreads();
-    SF_GSTAMP(0);
     for (int ti = 0; ti < SV / TV; ++ti) {
       const int v0 = sv0 + ti * TV;
       if (v0 >= V) break;
       // ---- the tile's rows
-#if !defined(SMPLFIT_GEN_DBG) || SMPLFIT_GEN_DBG != 2  // (timing experiment 2: the rows are not formed)
 #pragma unroll
       for (int u = 0; u < U; ++u)
         if (tid + u * NT < nquads) form_quad(tid + u * NT, v0, ti, sdv[u]);
@@ -780,7 +768,6 @@ __global__ __launch_bounds__(64 * NW) void k_gen_accum_mfma(DevModel m, Workspac
         load_quad(idx, v0, sd);
         form_quad(idx, v0, ti, sd);
       }
-#endif
       if (tid < R) {  // the five columns beside the unknowns
         const int r = tid, c = r % 3, l3 = ti * R + r;
         float* o = AT + (size_t)r * LD + S;
@@ -790,25 +777,16 @@ __global__ __launch_bounds__(64 * NW) void k_gen_accum_mfma(DevModel m, Workspac
         for (int c2 = 0; c2 < 3; ++c2) o[1 + c2] = c2 == c ? one : 0.f;
         o[4] = rt[l3];
       }
-      SF_GSTAMP(1);
       __syncthreads();
-      SF_GSTAMP(2);
       request(v0 + TV);  // (past the last vertex: nothing is read)
       update(rw + ti * R);
-      SF_GSTAMP(3);
       __syncthreads();
-      SF_GSTAMP(4);
     }
     if (++since_flush == flush_every && sv0 + SV < V) {
       flush();
       since_flush = 0;
     }
   }
-#if defined(SMPLFIT_GEN_DBG) && SMPLFIT_GEN_DBG == 3
-  if (b == 0 && blockIdx.y == 0 && (tid == 0 || tid == NT - 64))
-    printf("gen_accum stamps (thread %d): blend %lld form %lld wait1 %lld update %lld wait2 %lld other %lld\n", tid, tacc[0], tacc[1],
-           tacc[2], tacc[3], tacc[4], tacc[5]);
-#endif
   // ---- the target joints are further rows of the design matrix (bodyfitter.py:1161-1170: target_both = cat(vertices,
   // joints)): row (j, c) = P'_j[c][s] of the joint stage, residual t_j - P0_j, weight jw_j — the joint block of the
   // normal equations, which the other paths take from k_joint_stage (3 J serial rows per entry: 5 ms at S = 300)

@@ -341,11 +341,6 @@ __global__ __launch_bounds__(64, N == 64 ? SMPLFIT_JOINT_OCC : 2) void k_joint_s
                   ws.rp + (size_t)b * m.Kp, ws.jd + (size_t)b * J * sf::jd_stride(S),
                   ws.pext + (size_t)b * J * 3 * (S + 1), ws.gramj + (size_t)b * NE1,
                   a.gt_pitch > 0 ? ws.GT + b : nullptr, a.gt_pitch);
-#ifdef SMPLFIT_STAGE_STAMPS
-  if (b == SMPLFIT_STAMP_B && threadIdx.x == 0 && a.do_prologue)
-    printf("joint_stage stamps: kabsch %lld toes %lld rel %lld fk %lld jd %lld gram %lld\n", cx.t[1] - cx.t[0], cx.t[2] - cx.t[1],
-           cx.t[3] - cx.t[2], cx.t[4] - cx.t[3], cx.t[5] - cx.t[4], cx.t[6] - cx.t[5]);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -609,9 +604,11 @@ constexpr int kGemmWaves = SMPLFIT_GEMM_WAVES;        // waves per workgroup (32
 #define SMPLFIT_GEMM_RING 2
 #endif
 // LDS ring of tile images (kGemmRing - 1 tiles requested ahead).  Measured at 4096 (SMPL): 2 / 3 / 4 slots 102 / 102 /
-// 105 us -- the tile request is not what the kernel waits for: timing-only ablations (kGemmAbl) of the three-product
-// form give 83 without the output stores, 99 without the LDS-DMA, 96 without the fragment reads, 68.5 with none of the
-// three (3.3 M MFMAs = 52 us of matrix-pipe time at 2.0 GHz + the feature prologue of the 512 workgroups).
+// 105 us -- the tile request is not what the kernel waits for: timing-only ablation builds (wrong results; since
+// removed, numbers in profiles/README.md, rounds 2 and 3) of the three-product form give 83 without the output stores,
+// 99 without the LDS-DMA, 96 without the fragment reads, 68.5 with none of the three (3.3 M MFMAs = 52 us of
+// matrix-pipe time at 2.0 GHz + the feature prologue of the 512 workgroups); the six-product form gave 158 us -> 141 /
+// 133 / 161, all three 122 us.
 constexpr int kGemmRing = SMPLFIT_GEMM_RING;
 static_assert(kGemmRing >= 2 && 16 * (kGemmRing - 1) + (kGemmRing - 2) * (kGemmTileBytes / 1024 / kGemmWaves + 1) <= 63,
               "s_waitcnt vmcnt is a 6-bit count");
@@ -619,13 +616,6 @@ template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
-// timing experiments only (tools/build_variant.sh gablN -DSMPLFIT_GEMM_ABL=N; results are wrong when set):
-// bit 0 drops the output stores, 1 the tile DMA after the first tile, 2 the LDS fragment reads.  0 in every
-// product build.  Measured (profiles/r02_gemm_ablation.jsonl): 158 us -> 141 / 133 / 161, all three 122 us.
-#ifndef SMPLFIT_GEMM_ABL
-#define SMPLFIT_GEMM_ABL 0
-#endif
-constexpr int kGemmAbl = SMPLFIT_GEMM_ABL;
 // Products per k-step of the split-bf16 GEMMs (sf::kGemm3, -DSMPLFIT_GEMM_PRODUCTS).  6: every term down to 2^-24 of
 // |feature| |posedirs| (fp32-equivalent on every term).  3 (default): x1 y1 + x1 y2 + x2 y1 — the terms of order 2^-18
 // are dropped on the POSE-CORRECTIVE rows only, whose sum is a vertex offset of at most a few centimetres: 2^-18 of that
@@ -644,7 +634,7 @@ __device__ __forceinline__ void lds_dma16(const char* src, uint32_t lane_off, ch
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(l), "v"(lane_off), "s"(src) : "memory", "m0");
 }
 
-// EXCLUSIVE CU.  Measured on MI355X (tools/dbg_pg.py, profiles/README.md): while a wave streams LDS
+// EXCLUSIVE CU.  Measured on MI355X (DESIGN.md §8 item 3, profiles/README.md): while a wave streams LDS
 // fragments into bf16 MFMAs, OTHER kernels' waves resident on the same CU occasionally receive a wrong
 // last quarter (lanes 48-63) of a broadcast-type read (uniform-address LDS / vector loads) — k_pair_gram_bm
 // and k_lbs_partsum_bm beside this kernel produced run-to-run different sums; neither the fp32-MFMA GEMM
@@ -661,9 +651,7 @@ __global__ __launch_bounds__(64 * kGemmWaves, 2) void k_posedirs_gemm_bf16x3(con
   constexpr int KS = kGemmKS, KP = 16 * KS, NW = kGemmWaves;
   constexpr int NDMA = kGemmTileBytes / 1024;  // 1 KB per wave-instruction: 39
   extern __shared__ __attribute__((aligned(16))) char smem_b[];  // [kGemmRing][kGemmTileBytes]
-#ifndef SMPLFIT_GEMM_SHARED_CU  // (debug builds of tools/dbg_pg.py only: lets other kernels' waves onto the CU)
   asm volatile("v_mov_b32 v255, 0" ::: "v255");  // 256 VGPRs per wave: see "exclusive CU" above
-#endif
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, kg = lane >> 5;
@@ -721,14 +709,13 @@ __global__ __launch_bounds__(64 * kGemmWaves, 2) void k_posedirs_gemm_bf16x3(con
   int buf = 0, buf_req = LEAD;          // ring slots of tile t and of tile t + LEAD (the slot of t - 1: free since the barrier)
   for (int t = t_begin; t < t_end; ++t) {
     const bool more = t + 1 < t_end;
-    if (!(kGemmAbl & 2)) dma_tile(min(t + LEAD, t_end - 1), buf_req);
+    dma_tile(min(t + LEAD, t_end - 1), buf_req);
     if (active) {
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
       const char* base = smem_b + buf * kGemmTileBytes + frag_off;
       auto frag = [&](int plane, int s) {
-        if constexpr ((kGemmAbl & 4) != 0) return plane == 0 ? f1[s] : (plane == 1 ? f2[s] : f3[s]);
         if constexpr (kGemm3) {
           // third plane: the last k-step only, rows of 32 bytes (slot = this lane's k-octet)
           if (plane == 2) return *reinterpret_cast<const bf16x8*>(smem_b + buf * kGemmTileBytes + 2 * kGemmPlaneBytes + l31 * 32 + kg * 16);
@@ -771,8 +758,7 @@ __global__ __launch_bounds__(64 * kGemmWaves, 2) void k_posedirs_gemm_bf16x3(con
         }
       }
       // C layout of 32x32: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-      if ((kGemmAbl & 1) && acc[0] != 12345.678f) {
-      } else if (TRANSPOSED) {  // batch-major: [m0 / 64][n][64]; 32 consecutive instances per half wave
+      if (TRANSPOSED) {  // batch-major: [m0 / 64][n][64]; 32 consecutive instances per half wave
         float* ccol = C + ((size_t)(m0 >> 6) * N + t * 32) * 64 + (m0 & 63) + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) st_stream<2>(ccol + (size_t)((r & 3) + 8 * (r >> 2) + 4 * kg) * 64, acc[r]);
@@ -788,8 +774,8 @@ __global__ __launch_bounds__(64 * kGemmWaves, 2) void k_posedirs_gemm_bf16x3(con
     // the 16 stores of each of the LEAD tiles multiplied since (idle waves have no stores); then the workgroup meets:
     // every wave has finished reading this buffer and can see the next one.  The last tile drains everything: no
     // LDS-DMA may be in flight when the workgroup's LDS is released.
-    constexpr int N0 = (LEAD - 1) * (NDMA / NW), N1 = (LEAD - 1) * (NDMA / NW + 1), ST = (kGemmAbl & 1) ? 0 : 16 * LEAD;
-    if (!more || (kGemmAbl & 2)) wait_vmcnt<0>();
+    constexpr int N0 = (LEAD - 1) * (NDMA / NW), N1 = (LEAD - 1) * (NDMA / NW + 1), ST = 16 * LEAD;
+    if (!more) wait_vmcnt<0>();
     else if (active) {
       if (extra) wait_vmcnt<ST + N1>();
       else wait_vmcnt<ST + N0>();
@@ -1288,11 +1274,6 @@ __global__ __launch_bounds__(GEN ? 1024 : 64) void k_shape_solve(DevModel m, Wor
                   mode == 1 ? ws.cen + (size_t)(b - cen_b0) * (S * S + S) : ws.censum,
                   ws.jbT ? ws.jbT + ((size_t)(b >> 6) * J * 4) * 64 + (b & 63) : nullptr,
                   GEN ? reinterpret_cast<double*>(smem) : nullptr);
-#ifdef SMPLFIT_STAGE_STAMPS
-  if (b == SMPLFIT_STAMP_B && threadIdx.x == 0 && (pair_form || GEN))
-    printf("solve_stage stamps: sums %lld system %lld cholesky %lld subst %lld outputs %lld\n", cx.t[1] - cx.t[0], cx.t[2] - cx.t[1],
-           cx.t[3] - cx.t[2], cx.t[4] - cx.t[3], cx.t[5] - cx.t[4]);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -108,21 +108,16 @@ SF_HD int solve_scratch_floats(int S) {
 }
 
 #define SF_FOR(i, count) for (int i = cx.lane; i < (count); i += cx.n)
-// timing experiments (tools/stage_stamps.sh, -DSMPLFIT_STAGE_STAMPS): cycle stamps at the sync points of the joint stages
-#ifdef SMPLFIT_STAGE_STAMPS
-#define SF_STAMP(k) cx.stamp(k)
-#else
-#define SF_STAMP(k)
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // Joint block of the normal equations (+ the closed-form vertex SA) with a lane per JOINT: every lane accumulates the
 // terms of its joints' three rows in registers, then one wave sum per entry (cx.sum_to_last: the total on the last lane,
 // which stores it).  The entry-per-lane form in joint_stage below walks the 3 J rows serially in every lane, once per
 // branch the wave's lanes diverge into: 37 k of the 93 k cycles of k_joint_stage for SMPL, 78 k of 160 k for the
-// SMPL-X-shaped model (tools/stage_stamps.sh); this form: see DESIGN.md.  Two phases (the Gramian, then everything
-// else) keep the live accumulators under the registers of four waves per SIMD.  Same sums as the generic form; on the
-// device the order of the additions differs (a tree over the lanes instead of one chain).
+// SMPL-X-shaped model (cycle stamps of a debug build, since removed: profiles/README.md, round 3 history); this form:
+// see DESIGN.md.  Two phases (the Gramian, then everything else) keep the live accumulators under the registers of
+// four waves per SIMD.  Same sums as the generic form; on the device the order of the additions differs (a tree over
+// the lanes instead of one chain).
 // ---------------------------------------------------------------------------------------------
 template <int S, class Ctx>
 SF_HD void joint_gram_by_joint(Ctx& cx, const JointTabs& tb, const JointScratch& sh, const float* jw, bool joint_block,
@@ -239,7 +234,6 @@ SF_HD void joint_stage(Ctx& cx, const JointTabs& tb, const JointScratch& sh, con
   // GT_out[(j * 9 + k) * gt_pitch] — for the batch-major prologue kernel k_prologue_bm, which then follows instead of
   // the prologue below (do_prologue = false)
   const int J = tb.J, S = tb.S, S1 = S + 1;
-  SF_STAMP(0);
   SF_FOR(k, J * 3) {
     sh.tj[k] = tjc[k];
     sh.rj[k] = rj_in ? rj_in[k] : 0.f;
@@ -304,7 +298,6 @@ SF_HD void joint_stage(Ctx& cx, const JointTabs& tb, const JointScratch& sh, con
     for (int k = 0; k < 9; ++k) sh.R[j * 9 + k] = R[k];
   }
   cx.sync();
-  SF_STAMP(1);
   SF_FOR(j, J) {  // toes take the feet; compose with the previous rotations (:422-433)
     if (!fit_rotations) break;
     const int src = tb.toe_src[j] >= 0 ? tb.toe_src[j] : j;
@@ -321,7 +314,6 @@ SF_HD void joint_stage(Ctx& cx, const JointTabs& tb, const JointScratch& sh, con
     }
   }
   cx.sync();
-  SF_STAMP(2);
   if (!do_prologue) return;
 
   // relative rotations -> pose feature (:869-876, :913); root row of P (:889-891)
@@ -336,7 +328,6 @@ SF_HD void joint_stage(Ctx& cx, const JointTabs& tb, const JointScratch& sh, con
   SF_FOR(k, tb.Kp - tb.P) rp_out[rp_pos(tb.P + k, tb.Kp)] = k == 0 ? 1.f : 0.f;
   SF_FOR(k, 3 * S1) sh.P[k] = tb.j_ext[k];
   cx.sync();
-  SF_STAMP(3);
   // level-batched FK of positions and their beta-Jacobian (:892-907)
   for (int lv = 0; lv < tb.num_levels; ++lv) {
     const int l0 = tb.fk_level_start[lv], nl = tb.fk_level_start[lv + 1] - l0;
@@ -354,7 +345,6 @@ SF_HD void joint_stage(Ctx& cx, const JointTabs& tb, const JointScratch& sh, con
     }
     cx.sync();
   }
-  SF_STAMP(4);
   // T = P - G J_ext (:909-911); joint block for the vertex kernels; P for the solve stage
   const int stride = jd_stride(S), row = jd_row(S);
   // (the table values of a lane's NEXT item are requested before the current one is processed: the loop is a chain of
@@ -395,13 +385,11 @@ SF_HD void joint_stage(Ctx& cx, const JointTabs& tb, const JointScratch& sh, con
   // joint block of the normal equations, fp32 sums (:1051-1053, _gram_block :1598-1625)
   const int NG = ne_ng(S), NE = ne_size(S);
   cx.sync();
-  SF_STAMP(5);
   if (S == 10 || S == 11) {  // (the shapes the batch-major path serves; more unknowns: the Gramian does not fit registers)
     if (S == 10)
       joint_gram_by_joint<10>(cx, tb, sh, jw, joint_block, joint_block_weighted, vertex_sa_closed_form, gramj_out);
     else
       joint_gram_by_joint<11>(cx, tb, sh, jw, joint_block, joint_block_weighted, vertex_sa_closed_form, gramj_out);
-    SF_STAMP(6);
     return;
   }
   SF_FOR(e, NE + 1) {
@@ -459,7 +447,6 @@ SF_HD void joint_stage(Ctx& cx, const JointTabs& tb, const JointScratch& sh, con
     }
     gramj_out[e] = acc;
   }
-  SF_STAMP(6);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -550,7 +537,6 @@ SF_HD void ldlt_solve(Ctx& cx, double* M, int ld, int n, double* x, double* rd, 
       }
     }
     cx.sync();
-    SF_STAMP(3);
   } else {
   for (int k = 0; k < n; ++k) {
     cx.sync();
@@ -566,7 +552,6 @@ SF_HD void ldlt_solve(Ctx& cx, double* M, int ld, int n, double* x, double* rd, 
       }
     }
   }
-  SF_STAMP(3);
   for (int k = 0; k < n; ++k) {  // forward: y = L^-1 b
     cx.sync();
     const double yk = x[k] * rd[k];
@@ -620,7 +605,6 @@ SF_HD void solve_stage(Ctx& cx, const JointTabs& tb, float* scratch, const doubl
   double* x = M + S * S;                             // S
   double* r2p = x + S;                               // kSolveParts * S
   float* aux = reinterpret_cast<float*>(r2p + kSolveParts * S);  // S+3
-  SF_STAMP(0);
   if (mb) {
     // pair-Gram form: the residual kernel delivers r1 = sum_v S_v^T (Rt_v^T b_v) and the per-joint residual moments
     // mb_j = sum_v w_vj b_v; the T' part of Jac^T b is sum_j T'_j^T mb_j.  kSolveParts lanes per unknown sum a run of
@@ -647,7 +631,6 @@ SF_HD void solve_stage(Ctx& cx, const JointTabs& tb, float* scratch, const doubl
     sum[e] = v;
   }
   cx.sync();
-  SF_STAMP(1);
   double W = sum[NE];
   if (W == 0.0) W = 1.0;  // w_sum_safe (:1060)
   const double* SA = sum + NG + S;
@@ -679,11 +662,9 @@ SF_HD void solve_stage(Ctx& cx, const JointTabs& tb, float* scratch, const doubl
     SF_FOR(i, S) x[i] = cen[S * S + i];
     cx.sync();
   }
-  SF_STAMP(2);
   // rd ALIASES r2p: the partial sums of r2 were read by the sum loop above, and the cx.sync() that opens the
   // factorisation is what orders those reads before the first write of rd[0].
   ldlt_solve(cx, M, S, S, x, r2p, panel);  // (rd ALIASES r2p: see below)
-  SF_STAMP(4);
   // translation (:1086-1088) and outputs, cast to fp32 (:1088-1089)
   float* betaf = aux;       // S
   float* transf = aux + S;  // 3
@@ -712,7 +693,6 @@ SF_HD void solve_stage(Ctx& cx, const JointTabs& tb, float* scratch, const doubl
     jb_out[j * 4 + c] = jd[j * stride + 9 + c] + tb0;
     if (jbT_out) jbT_out[(j * 4 + c) * 64] = jd[j * stride + 9 + c] + tb0;
   }
-  SF_STAMP(5);
 }
 
 // ---------------------------------------------------------------------------------------------
