@@ -547,3 +547,140 @@ def check_convert(om_out, tag, case, o, gc):
         print(f'[convert] {tag} {case}: vertex L2 {err:.2e}, trans {np.abs(o["trans"] - ref["trans"]).max():.1e}')
     assert err < 1e-4, (tag, case, err)
     return err
+
+
+# ---- BodyModel.forward against fp64 (tests/test_gpu_forward.py; the helpers' own checks in test_forward_reference.py) --
+# Gate: vertices / joints |ours - fp64| <= FWD_GATE_M + 4 ulp_fp32(|fp64|) (the ulp term only matters for the instance
+# translated by ~1000 m); test_gpu_forward.py tightens it per model to about twice what it measured
+FWD_GATE_M = 2e-6
+FWD_FAR = 2  # the instance of forward_inputs translated by ~1000 m
+
+
+def compose_glob(rel, parents):
+    """Global rotations (B, J, 3, 3) of relative ones along the kinematic chain, in fp64."""
+    rel = np.asarray(rel, np.float64)
+    glob = [rel[:, 0]]
+    for i in range(1, rel.shape[1]):
+        glob.append(glob[parents[i]] @ rel[:, i])
+    return np.stack(glob, 1)
+
+
+def rotation_forms(pose, parents):
+    """(glob32, rel32) of pose rotation vectors: Rodrigues and the chain in fp64, each rounded once to fp32."""
+    B = pose.shape[0]
+    rel = O.rotvec2mat(np.asarray(pose, np.float64).reshape(B, -1, 3))
+    return compose_glob(rel, parents).astype(np.float32), rel.astype(np.float32)
+
+
+def forward64(om, pose_rotvecs=None, shape_betas=None, trans=None, kid_factor=None, glob_rotmats=None,
+              rel_rotmats=None, rows=None, chunk=256):
+    """``om.forward`` (an fp64 ``OracleModel``) with the input forms of ``BodyModel.forward``: ``rel_rotmats`` are composed
+    to global rotations in fp64, no rotation input is the rest pose, ``trans`` of shape (1, 3) and a scalar
+    ``kid_factor`` apply to every instance.  ``rows``: the instances to evaluate (default all), in chunks of at most
+    ``chunk`` so that the (B, V, 3, 3) blend stays small."""
+    per = dict(pose_rotvecs=pose_rotvecs, shape_betas=shape_betas, glob_rotmats=glob_rotmats, rel_rotmats=rel_rotmats)
+    per = {k: np.asarray(v) for k, v in per.items() if v is not None}
+    tr = None if trans is None else np.asarray(trans, np.float64).reshape(-1, 3)
+    kid = None if kid_factor is None else np.asarray(kid_factor, np.float64).reshape(-1)
+    B = next(iter(per.values())).shape[0] if per else (tr.shape[0] if tr is not None else 1)
+    if tr is not None and tr.shape[0] == B:
+        per['trans'] = tr
+    if kid is not None and kid.shape[0] == B and B > 1:
+        per['kid_factor'] = kid
+    rows = np.arange(B) if rows is None else np.asarray(rows)
+    out = dict(vertices=[], joints=[], orientations=[])
+    for c0 in range(0, len(rows), chunk):
+        r = rows[c0:c0 + chunk]
+        a = {k: v[r] for k, v in per.items()}
+        a.setdefault('trans', tr)
+        a.setdefault('kid_factor', kid)
+        if 'rel_rotmats' in a:
+            a['glob_rotmats'] = compose_glob(a.pop('rel_rotmats'), om.parents)
+        elif 'pose_rotvecs' not in a and 'glob_rotmats' not in a:
+            a['glob_rotmats'] = np.broadcast_to(np.eye(3), (len(r), om.J, 3, 3))
+        if 'glob_rotmats' in a:
+            a['glob_rotmats'] = np.asarray(a['glob_rotmats'], np.float64)
+        f = om.forward(**a)
+        for k in out:
+            out[k].append(f[k])
+    return {k: np.concatenate(v) for k, v in out.items()}
+
+
+def forward_inputs(B, J, S, seed=0):
+    """Seeded forward inputs with the values where the arithmetic branches, mixed per joint and per instance: each
+    joint's rotation vector is ordinary (0.3 rad per component), exactly zero, a tiny angle (1e-7 .. 1e-4 rad: Rodrigues'
+    small-angle path), large (up to 3 rad per component: pose features of order 2) or near and above pi; every eleventh
+    instance has an all-zero pose; betas up to +-5 (every seventh instance at the corners) with a last column of at
+    least 0.5 in magnitude (both scaled by 0.15 for more than 32 betas); instance FWD_FAR translated by ~1000 m; kid factors in [-0.5, 1.5].  The batches of a test are
+    prefixes of one such set, so that they share the fp64 reference of their common rows (Ref64)."""
+    rs = np.random.RandomState(seed)
+    cls = rs.choice(5, size=(B, J), p=[0.4, 0.15, 0.15, 0.15, 0.15])
+    axis = rs.randn(B, J, 3)
+    axis /= np.linalg.norm(axis, axis=-1, keepdims=True)
+    tiny = axis * 10.0 ** rs.uniform(-7, -4, (B, J, 1))
+    near_pi = axis * (np.pi + rs.uniform(-1e-3, 0.3, (B, J, 1)))
+    ordinary, large = rs.randn(B, J, 3) * 0.3, rs.uniform(-3, 3, (B, J, 3))
+    pose = np.select([cls[..., None] == k for k in range(5)], [ordinary, 0 * ordinary, tiny, large, near_pi])
+    pose[np.arange(B) % 11 == 5] = 0.0
+    betas = np.clip(rs.randn(B, S) * 1.5, -5, 5)
+    corner = np.arange(B) % 7 == 3
+    betas[corner] = rs.choice([-5.0, 5.0], size=(int(corner.sum()), S))
+    betas[:, -1] = rs.choice([-1.0, 1.0], B) * rs.uniform(0.5, 5, B)
+    if S > 32:  # (as test_general_full_size: 300 shape terms of +-5 are a 36 m lever whose fp32 sum alone rounds to 6e-6 m)
+        betas *= 0.15
+    trans = rs.randn(B, 3)
+    if B > FWD_FAR:
+        trans[FWD_FAR] += (1000.0, -1000.0, 1000.0)
+    kid = rs.uniform(-0.5, 1.5, B)
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)  # noqa: E731
+    return dict(pose_rotvecs=f32(pose.reshape(B, 3 * J)), shape_betas=f32(betas), trans=f32(trans), kid_factor=f32(kid))
+
+
+def forward_rows(B, n=64, seed=0):
+    """Every row up to 300 instances; above, about ``n``: both ends, FWD_FAR, the rows on both sides of every 64-, 128-
+    and 256-boundary near the tail and of the fine / coarse table limit (768), the middle, and a seeded scatter."""
+    if B <= 300:
+        return np.arange(B)
+    fixed = {0, 1, FWD_FAR, 63, 64, 127, 128, 255, 256, B // 2 - 1, B // 2, B - 2, B - 1}
+    for m in (64, 128, 256):
+        e = (B - 1) // m * m  # the last boundary in front of the tail
+        fixed |= {e - 1, e, e - m - 1, e - m}
+    if B > 768:
+        fixed |= {767, 768}
+    rs = np.random.RandomState(seed)
+    rest = np.setdiff1d(np.arange(B), sorted(fixed))
+    extra = rs.choice(rest, size=max(0, n - len(fixed)), replace=False)
+    return np.array(sorted(fixed | set(extra.tolist())))
+
+
+class Ref64:
+    """The fp64 reference of one input set (``forward64`` keyword arguments over the largest batch), row by row on
+    demand and cached: every batch of a test is a prefix of the same inputs."""
+
+    def __init__(self, om, **inputs):
+        self.om, self.inputs, self.cache = om, inputs, {}
+
+    def rows(self, idx):
+        idx = np.asarray(idx)
+        todo = np.array(sorted(set(idx.tolist()) - set(self.cache)), dtype=np.int64)
+        if len(todo):
+            f = forward64(self.om, rows=todo, **self.inputs)
+            for i, r in enumerate(todo.tolist()):
+                self.cache[r] = {k: v[i] for k, v in f.items()}
+        return {k: np.stack([self.cache[r][k] for r in idx.tolist()]) for k in ('vertices', 'joints', 'orientations')}
+
+
+def forward_excess(ours, ref):
+    """max over elements of |ours - ref| - 4 ulp_fp32(|ref|): what FWD_GATE_M bounds."""
+    ref = np.asarray(ref, np.float64)
+    d = np.abs(np.asarray(ours, np.float64) - ref) - 4 * np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
+    return float(np.nanmax(d)) if np.isfinite(ours).all() else float('inf')
+
+
+def forward_errors(ours, ref):
+    """(vertices, joints, orientations) errors of a forward result against forward64 rows (vertices absent: nan)."""
+    ev = forward_excess(ours['vertices'], ref['vertices']) if 'vertices' in ours else float('nan')
+    ej = forward_excess(ours['joints'], ref['joints'])
+    o = np.asarray(ours['orientations'], np.float64)
+    eo = float(np.abs(o - ref['orientations']).max()) if np.isfinite(o).all() else float('inf')
+    return ev, ej, eo
