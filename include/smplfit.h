@@ -73,7 +73,7 @@ const char* smplfit_last_error(void);
 const char* smplfit_version(void);
 /* Version of this header's structs and entry points; bumped whenever a struct gains a field or a signature
  * changes.  A client compares it with the SMPLFIT_ABI_VERSION it was built against before the first call. */
-#define SMPLFIT_ABI_VERSION 5
+#define SMPLFIT_ABI_VERSION 6
 int smplfit_abi_version(void);
 
 typedef struct smplfit_info {
@@ -350,7 +350,11 @@ int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solv
  * SMPLFIT_CREATE_HOST_ONLY: no upload, for tests).  smplfit_transfer_f32: in_vertices (B,V_in,3) ->
  * out_vertices (B,V_out,3), device pointers; the entries of a row are added in CSR order, as the reference's sparse
  * product does.
+ * flags | SMPLFIT_TRANSFER_NEGATE_X: the product is followed by x -> -x (BodyFlipper.flip_vertices,
+ * pt/bodyflipper.py:99-119: the mirror matrix, then the x axis flipped); every use of the matrix — smplfit_transfer_f32
+ * and the fused calls — honours it.  Other flag bits are rejected.
  */
+enum { SMPLFIT_TRANSFER_NEGATE_X = 2 };
 typedef struct smplfit_transfer smplfit_transfer;
 int smplfit_transfer_create(int32_t num_vertices_in, int32_t num_vertices_out, const int32_t* indptr,
                             const int32_t* indices, const float* values, int flags, smplfit_transfer** out);
@@ -397,6 +401,48 @@ typedef struct smplfit_convert_args {
   void* hip_stream;
 } smplfit_convert_args;
 int smplfit_convert_f32(const smplfit_convert_plan* plan, const smplfit_convert_args* args);
+
+/*
+ * BodyFlipper.flip (pt/bodyflipper.py:34-92) as ONE call: forward of the input parameters WITH kid_factor, the mirror
+ * transfer (a smplfit_transfer made with SMPLFIT_TRANSFER_NEGATE_X) straight into the fit's target stream, the naively
+ * flipped pose (joints permuted, rotation vectors times (1,-1,-1), pt/bodyflipper.py:121-133) written to the
+ * workspace, and the fit warm-started from that pose and the input betas (first rotation pass against the model posed
+ * with them; ridge reference = the input betas).  No (B,V,3) intermediate is written and nothing synchronises.
+ *   smplfit_flip_plan_create(h, mirror, joint_perm, &plan): `h` = handle of the model with the kid unknown (the
+ *   flipper's BodyFitter(enable_kid=True)), `mirror` = (V x V) transfer, `joint_perm` (J) = the joint mirror map
+ *   (HOST pointer; must be in range and an involution).  SMPLFIT_ERR_UNSUPPORTED where the batch-major kernels do not
+ *   take the model — the caller then runs forward + smplfit_transfer_f32 + smplfit_fit_warm_f32.  The plan borrows
+ *   the handle (keep it alive) and owns its re-indexed copy of the matrix and of the permutation.
+ *   smplfit_flip_f32: inputs pose_rotvecs (B,3J), shape_betas (B,num_betas_given) or NULL, trans (B,3) or NULL,
+ *   kid_factor (B) or NULL (the input mesh is evaluated with it); fit options as smplfit_fit_f32 (the reference passes
+ *   beta_regularizer = beta_regularizer2 = 1e-2, final_adjust_rots = 1, kid_regularizer = 1e9 without kid_factor,
+ *   else 0); outputs as smplfit_fit_f32.  Workspace: smplfit_flip_workspace_bytes(plan, batch).
+ */
+typedef struct smplfit_flip_plan smplfit_flip_plan;
+int smplfit_flip_plan_create(const smplfit_handle* h, const smplfit_transfer* mirror, const int32_t* joint_perm,
+                             smplfit_flip_plan** plan);
+void smplfit_flip_plan_destroy(smplfit_flip_plan* plan);
+size_t smplfit_flip_workspace_bytes(const smplfit_flip_plan* plan, int batch);
+typedef struct smplfit_flip_args {
+  const float* pose_rotvecs;         /* (B,3J) */
+  const float* shape_betas;          /* (B,num_betas_given) or NULL */
+  int32_t num_betas_given;
+  const float* trans;                /* (B,3) or NULL */
+  const float* kid_factor;           /* (B) or NULL */
+  int32_t batch, num_iter;
+  float beta_regularizer, beta_regularizer2, kid_regularizer;
+  int32_t final_adjust_rots;
+  float* out_pose_rotvecs;           /* (B,3J) */
+  float* out_shape_betas;            /* (B,S) */
+  float* out_trans;                  /* (B,3) */
+  float* out_kid_factor;             /* (B) or NULL */
+  float* out_orientations;           /* (B,J,3,3) or NULL */
+  float* out_relative_orientations;  /* (B,J,3,3) or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  void* hip_stream;
+} smplfit_flip_args;
+int smplfit_flip_f32(const smplfit_flip_plan* plan, const smplfit_flip_args* args);
 
 /* Re-reads the SMPLFIT_* tuning variables (INTEGRATION.md lists them).  They are read once, at first use; tests and
  * the A/B tools that switch kernel paths inside one process call this after changing the environment.  Not to be

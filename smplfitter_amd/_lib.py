@@ -24,7 +24,8 @@ SMPLFIT_PATH_WAVE, SMPLFIT_PATH_BATCH_MAJOR, SMPLFIT_PATH_GENERAL = 0, 1, 2  # s
 SMPLFIT_ERR_WORKSPACE = -3
 SMPLFIT_ERR_HIP = -4
 SMPLFIT_CREATE_HOST_ONLY = 1
-SMPLFIT_ABI_VERSION = 5  # include/smplfit.h; checked against smplfit_abi_version() when the library is loaded
+SMPLFIT_TRANSFER_NEGATE_X = 2  # smplfit_transfer_create: x -> -x after the product (the mirror)
+SMPLFIT_ABI_VERSION = 6  # include/smplfit.h; checked against smplfit_abi_version() when the library is loaded
 
 TABLE_IDS = dict(
     part_assignment=0, sort_perm=1, part_type=2, fk_order=3, fk_level_start=4, adj_flag=5,
@@ -40,7 +41,8 @@ EXPORTED_SYMBOLS = [
     'smplfit_time_kernel_f32', 'smplfit_primitives_f32', 'smplfit_forward_ex_f32',
     'smplfit_transfer_create', 'smplfit_transfer_destroy', 'smplfit_transfer_f32',
     'smplfit_convert_plan_create', 'smplfit_convert_plan_destroy', 'smplfit_convert_workspace_bytes',
-    'smplfit_convert_f32', 'smplfit_reload_options', 'smplfit_get_share_table', 'smplfit_pick_share_mult',
+    'smplfit_convert_f32', 'smplfit_flip_plan_create', 'smplfit_flip_plan_destroy', 'smplfit_flip_workspace_bytes',
+    'smplfit_flip_f32', 'smplfit_reload_options', 'smplfit_get_share_table', 'smplfit_pick_share_mult',
     'smplfit_abi_version',
 ]  # fmt: skip
 
@@ -102,6 +104,19 @@ class ConvertArgs(C.Structure):
     _fields_ = [
         ('pose_rotvecs', C.c_void_p), ('shape_betas', C.c_void_p), ('num_betas_given', C.c_int32),
         ('trans', C.c_void_p), ('batch', C.c_int32), ('num_iter', C.c_int32),
+        ('beta_regularizer', C.c_float), ('beta_regularizer2', C.c_float), ('kid_regularizer', C.c_float),
+        ('final_adjust_rots', C.c_int32), ('out_pose_rotvecs', C.c_void_p), ('out_shape_betas', C.c_void_p),
+        ('out_trans', C.c_void_p), ('out_kid_factor', C.c_void_p), ('out_orientations', C.c_void_p),
+        ('out_relative_orientations', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
+        ('hip_stream', C.c_void_p),
+    ]
+
+
+class FlipArgs(C.Structure):
+    """smplfit_flip_args (include/smplfit.h)."""
+    _fields_ = [
+        ('pose_rotvecs', C.c_void_p), ('shape_betas', C.c_void_p), ('num_betas_given', C.c_int32),
+        ('trans', C.c_void_p), ('kid_factor', C.c_void_p), ('batch', C.c_int32), ('num_iter', C.c_int32),
         ('beta_regularizer', C.c_float), ('beta_regularizer2', C.c_float), ('kid_regularizer', C.c_float),
         ('final_adjust_rots', C.c_int32), ('out_pose_rotvecs', C.c_void_p), ('out_shape_betas', C.c_void_p),
         ('out_trans', C.c_void_p), ('out_kid_factor', C.c_void_p), ('out_orientations', C.c_void_p),
@@ -214,6 +229,14 @@ def load():
     lib.smplfit_convert_workspace_bytes.restype = sz
     lib.smplfit_convert_f32.argtypes = [vp, C.POINTER(ConvertArgs)]
     lib.smplfit_convert_f32.restype = i32
+    lib.smplfit_flip_plan_create.argtypes = [vp, vp, _ip, C.POINTER(vp)]
+    lib.smplfit_flip_plan_create.restype = i32
+    lib.smplfit_flip_plan_destroy.argtypes = [vp]
+    lib.smplfit_flip_plan_destroy.restype = None
+    lib.smplfit_flip_workspace_bytes.argtypes = [vp, i32]
+    lib.smplfit_flip_workspace_bytes.restype = sz
+    lib.smplfit_flip_f32.argtypes = [vp, C.POINTER(FlipArgs)]
+    lib.smplfit_flip_f32.restype = i32
     lib.smplfit_reload_options.argtypes = []
     lib.smplfit_reload_options.restype = i32
     if os.environ.get('SMPLFIT_LIB') and not hasattr(lib, 'smplfit_abi_version'):
@@ -341,9 +364,11 @@ def reload_options():
 
 
 class Transfer:
-    """Owns a ``smplfit_transfer*``: the (V_out x V_in) CSR topology-transfer matrix on the current device."""
+    """Owns a ``smplfit_transfer*``: the (V_out x V_in) CSR topology-transfer matrix on the current device
+    (``negate_x``: followed by x -> -x, the mirror of ``BodyFlipper``)."""
 
-    def __init__(self, num_vertices_in: int, num_vertices_out: int, indptr, indices, values, host_only: bool = False):
+    def __init__(self, num_vertices_in: int, num_vertices_out: int, indptr, indices, values, host_only: bool = False,
+                 negate_x: bool = False):
         lib = load()
         ip = np.ascontiguousarray(indptr, dtype=np.int32)
         ix = np.ascontiguousarray(indices, dtype=np.int32)
@@ -354,7 +379,9 @@ class Transfer:
         self._t = C.c_void_p()
         check(lib.smplfit_transfer_create(
             int(num_vertices_in), int(num_vertices_out), ip.ctypes.data_as(_ip), ix.ctypes.data_as(_ip),
-            va.ctypes.data_as(_fp), SMPLFIT_CREATE_HOST_ONLY if host_only else 0, C.byref(self._t)))
+            va.ctypes.data_as(_fp),
+            (SMPLFIT_CREATE_HOST_ONLY if host_only else 0) | (SMPLFIT_TRANSFER_NEGATE_X if negate_x else 0),
+            C.byref(self._t)))
 
     @property
     def ptr(self):
@@ -392,6 +419,35 @@ class ConvertPlan:
     def close(self):
         if getattr(self, '_p', None) is not None and self._p.value:
             load().smplfit_convert_plan_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FlipPlan:
+    """Owns a ``smplfit_flip_plan*`` and keeps the kid handle and the mirror matrix it borrows alive.  Raises
+    ``NotImplementedError`` when the fused flip does not apply to the model."""
+
+    def __init__(self, h: Handle, mirror: Transfer, joint_perm):
+        perm = np.ascontiguousarray(joint_perm, dtype=np.int32)
+        self._keep = (h, mirror)
+        self._p = C.c_void_p()
+        check(load().smplfit_flip_plan_create(h.ptr, mirror.ptr, perm.ctypes.data_as(_ip), C.byref(self._p)))
+
+    @property
+    def ptr(self):
+        return self._p
+
+    def workspace_bytes(self, batch: int) -> int:
+        return int(load().smplfit_flip_workspace_bytes(self._p, int(batch)))
+
+    def close(self):
+        if getattr(self, '_p', None) is not None and self._p.value:
+            load().smplfit_flip_plan_destroy(self._p)
             self._p = C.c_void_p()
 
     def __del__(self):

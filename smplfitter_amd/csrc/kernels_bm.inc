@@ -3129,6 +3129,9 @@ __global__ __launch_bounds__(256) void k_psum_combine(DevModel m, ShareView sv, 
 // (scalar loads), every gathered value is one coalesced 256-byte row.  Entries are added in table (CSR) order.
 // grid (ceil(V_out / kSlabV), Mp/64), block 256: a workgroup takes kSlabV consecutive ORIGINAL output vertices,
 // wave w the vertices w, w + 4, ...; `part` (slab, 3, Mp) as in k_layout_targets.
+// NEG (a SMPLFIT_TRANSFER_NEGATE_X matrix, the mirror of smplfit_flip_f32): x -> -x after the row sum, in the stream
+// AND in the slab sums, so that k_mean_finish takes the mean of the flipped mesh.  Negation is exact: the values equal
+// those of k_transfer_rows<_, true>.
 // ------------------------------------------------------------------------------------------------
 struct TransferTabs {
   const int32_t* oslot;   // (V_out) sorted slot of the output vertex in the output model
@@ -3138,6 +3141,7 @@ struct TransferTabs {
   int v_out;
 };
 
+template <bool NEG>
 __global__ __launch_bounds__(256) void k_transfer_bm(TransferTabs tt, const float* __restrict__ srcT, int VpIn,
                                                      float* __restrict__ tT, int VpOut, float* __restrict__ part, int Mp) {
   __shared__ float red[4 * 3 * 64];
@@ -3174,6 +3178,7 @@ __global__ __launch_bounds__(256) void k_transfer_bm(TransferTabs tt, const floa
         a2 += w[u] * x[u][2];
       }
     }
+    if constexpr (NEG) a0 = -a0;
     st_stream<8>(d + (size_t)oslot * 64, a0);
     st_stream<8>(d + cout + (size_t)oslot * 64, a1);
     st_stream<8>(d + 2 * cout + (size_t)oslot * 64, a2);
@@ -3195,7 +3200,8 @@ __global__ __launch_bounds__(256) void k_transfer_bm(TransferTabs tt, const floa
 // coalesced loads (gathering 12-byte vertices from global memory pulls ~8x the row through the fabric, see K0), then
 // every thread forms output vertices from LDS and the rows go out as contiguous 12-byte pieces.
 // grid B, block 1024, dynamic LDS 12 V_in bytes; STAGED = false (V_in beyond the LDS): gathers from global memory.
-template <bool STAGED>
+// NEG: x -> -x after the row sum (SMPLFIT_TRANSFER_NEGATE_X).
+template <bool STAGED, bool NEG>
 __global__ __launch_bounds__(1024) void k_transfer_rows(const float* __restrict__ in, float* __restrict__ out,
                                                         const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices,
                                                         const float* __restrict__ values, int Vin, int Vout) {
@@ -3227,8 +3233,28 @@ __global__ __launch_bounds__(1024) void k_transfer_rows(const float* __restrict_
       a1 += w * s[3 * c + 1];
       a2 += w * s[3 * c + 2];
     }
-    dst[3 * r] = a0;
+    dst[3 * r] = NEG ? -a0 : a0;
     dst[3 * r + 1] = a1;
     dst[3 * r + 2] = a2;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_naive_flip — BodyFlipper.naive_flip_rotvecs (reference pt/bodyflipper.py:121-133): the joints reordered by the
+// joint mirror map and every rotation vector multiplied by (1, -1, -1); the warm start of smplfit_flip_f32.  Exact
+// (a permutation and sign changes).  lane = instance: grid ceil(B / 256), block 256; perm (J) lies in [0, J) (checked
+// when the plan is made).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_naive_flip(const float* __restrict__ pose, const int32_t* __restrict__ perm,
+                                                    float* __restrict__ out, int B, int J) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float* src = pose + (size_t)b * J * 3;
+  float* dst = out + (size_t)b * J * 3;
+  for (int j = 0; j < J; ++j) {
+    const int k = perm[j];
+    dst[3 * j] = src[3 * k];
+    dst[3 * j + 1] = -src[3 * k + 1];
+    dst[3 * j + 2] = -src[3 * k + 2];
   }
 }

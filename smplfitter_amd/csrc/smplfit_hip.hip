@@ -141,6 +141,7 @@ struct smplfit_transfer {
   std::vector<float> values;
   int32_t *d_indptr = nullptr, *d_indices = nullptr;
   float* d_values = nullptr;
+  bool negate_x = false;  // SMPLFIT_TRANSFER_NEGATE_X: x -> -x after the product (the mirror of BodyFlipper)
 };
 
 // Fused conversion plan (smplfit_convert_f32): the transfer matrix re-indexed to the sorted slots of the two models.
@@ -149,6 +150,14 @@ struct smplfit_convert_plan {
   int nslab = 0;
   int32_t *d_oslot = nullptr, *d_start = nullptr, *d_islot = nullptr;
   float* d_w = nullptr;
+  bool negate_x = false;  // the matrix was made with SMPLFIT_TRANSFER_NEGATE_X
+};
+
+// Fused flip plan (smplfit_flip_f32): the mirror matrix at the sorted slots of the kid handle (in = out) and the
+// joint mirror map.
+struct smplfit_flip_plan {
+  smplfit_convert_plan conv;
+  int32_t* d_perm = nullptr;  // (J)
 };
 
 namespace {
@@ -1174,6 +1183,10 @@ void launch_refine_bm(const smplfit_handle* h, RefineArgs ra, const ShareView& s
 //                                                                      pass; else k_refine_epilogue (+ k_gt_to_g first
 //                                                                      when k_rotations_bm ran)
 //   no weights in the solve, not general; bm or SHAPE_FORM=pair      -> pair-Gram form (not the scaled solve of bm)
+//   flip (smplfit_flip_f32): the conversion's entry (kConvert, no    -> bm as a conversion; k_naive_flip, then the source
+//     target joints) with warm = true; not bm: no fused call           of the conversion with k_transfer_bm<true> and
+//                                                                      no k_template_partsum_bm (the first rotation pass
+//                                                                      reads the warm start's LBS rows, kShareLbsAll)
 // ------------------------------------------------------------------------------------------------
 enum class Entry { kFit, kConvert, kShapeSolve, kForward, kKnownShape };
 struct CallShape {
@@ -1273,10 +1286,12 @@ struct FitOptions {
 struct ConvertSource {
   const smplfit_convert_plan* plan;
   const float *pose, *betas, *trans;  // this chunk's rows of the input parameters; betas (B, nb) / trans may be null
+  const float* kid;                   // (B) kid factor of the input mesh (the flip) or null (the conversion: none)
   int nb;
   Workspace wsi;  // forward-only workspace slice of the input model (carve(..., fwd_only))
 };
-int launch_convert_source(const ConvertSource& src, const Route& r, const Workspace& ws, int B, hipStream_t st);
+int launch_convert_source(const ConvertSource& src, const Route& r, const Workspace& ws, int B, hipStream_t st,
+                          bool template_sums);
 
 // The solve of one shape pass on the sums already in the workspace: the plain per-instance solve, the
 // scaled solve (one more unknown; extra vertex sums first) or the shared solve (assemble, sum over the
@@ -1394,7 +1409,7 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
   if (on(0) && !r.bm) launch_center_sort(d, tv, tj, vw, ws, B, st);
   if (!on(0)) {
   } else if (r.bm && o.source) {
-    if (int rc = launch_convert_source(*o.source, r, ws, B, st)) return rc;
+    if (int rc = launch_convert_source(*o.source, r, ws, B, st, !warm)) return rc;
   } else if (r.bm) {
     launch_layout_bm(h, tv, tj, ws, B, st, vw, !warm, r.psum_combine);
   }
@@ -1668,15 +1683,18 @@ int run_fit_known_shape(const smplfit_handle* h, const float* betas, int nb, con
 //   forward of the INPUT model on the batch-major kernels (k_forward_joint, transposed GEMM, joint-row transpose,
 //   forward-only LBS pass: the posed vertices stay in the input model's instance-innermost buffer),
 //   k_transfer_bm into the OUTPUT model's target stream + slab sums, then the tail of launch_layout_bm.
-// r: the route of the fit the targets feed
-int launch_convert_source(const ConvertSource& src, const Route& r, const Workspace& ws, int B, hipStream_t st) {
+// r: the route of the fit the targets feed; template_sums: as launch_layout_bm's (a warm-started fit — the flip —
+// takes its first part sums against the posed initial model instead).  src.kid: the flip's input mesh is evaluated
+// with the kid factor (the input handle is then the kid handle); the conversion passes none.
+int launch_convert_source(const ConvertSource& src, const Route& r, const Workspace& ws, int B, hipStream_t st,
+                          bool template_sums) {
   const smplfit_convert_plan& pl = *src.plan;
   const DevModel& d = pl.out->d;
   const DevModel& di = pl.in->d;
   const Workspace& wi = src.wsi;
   const int Mp = (int)align_up((size_t)B, 128);
   hipLaunchKernelGGL(k_fill_shape, dim3((B + 255) / 256), dim3(256), 0, st, wi, B, di.S, di.jt.n_kid, src.betas,
-                     src.betas ? std::min(src.nb, di.S - di.jt.n_kid - di.jt.n_pad) : 0, (const float*)nullptr, src.trans);
+                     src.betas ? std::min(src.nb, di.S - di.jt.n_kid - di.jt.n_pad) : 0, src.kid, src.trans);
   ForwardArgs fa{};
   fa.pose = src.pose;
   fa.betas = wi.beta;  // (B,S) rows, zero beyond the given betas
@@ -1687,10 +1705,13 @@ int launch_convert_source(const ConvertSource& src, const Route& r, const Worksp
   launch_jd_transpose(di, wi, B, st);
   if (int rc_f = launch_lbs_fwd_bm(di, share_view(pl.in, sf::kShareLbsAll, B), wi, B, Mp, st)) return rc_f;
   TransferTabs tt{pl.d_oslot, pl.d_start, pl.d_islot, pl.d_w, d.V};
-  hipLaunchKernelGGL(k_transfer_bm, dim3(pl.nslab, Mp / 64), dim3(256), 0, st, tt, wi.vpT, di.Vp, ws.tT, d.Vp, ws.resP, Mp);
+  if (pl.negate_x)
+    hipLaunchKernelGGL(k_transfer_bm<true>, dim3(pl.nslab, Mp / 64), dim3(256), 0, st, tt, wi.vpT, di.Vp, ws.tT, d.Vp, ws.resP, Mp);
+  else
+    hipLaunchKernelGGL(k_transfer_bm<false>, dim3(pl.nslab, Mp / 64), dim3(256), 0, st, tt, wi.vpT, di.Vp, ws.tT, d.Vp, ws.resP, Mp);
   hipLaunchKernelGGL(k_mean_finish, dim3(Mp / 64), dim3(64 * kMeanWaves), 0, st, d, (const float*)nullptr, ws.resP, ws, B, Mp,
                      pl.nslab);
-  launch_template_partsum_bm(pl.out, ws, B, st, false, r.psum_combine);
+  if (template_sums) launch_template_partsum_bm(pl.out, ws, B, st, false, r.psum_combine);
   return 0;
 }
 
@@ -1750,6 +1771,7 @@ struct ConvertJob {
   const smplfit_convert_plan* plan;
   const float *pose, *betas, *trans;
   int nb;
+  const float* kid;  // (B) or null
 };
 int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const ConvertJob* job);
 
@@ -1812,6 +1834,7 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
       src.betas = job->betas ? job->betas + (size_t)b0 * job->nb : nullptr;
       src.trans = job->trans ? job->trans + (size_t)b0 * 3 : nullptr;
       src.nb = job->nb;
+      src.kid = job->kid ? job->kid + b0 : nullptr;
       carve(job->plan->in->t, nb, wsbase + own, &src.wsi, true);
       oc.source = &src;
     }
@@ -1890,6 +1913,62 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
   if (first_error) return fail(first_error, first_msg);
   return SMPLFIT_OK;
 }
+
+// smplfit_transfer_f32: the staged form where the input rows fit the LDS
+template <bool NEG>
+void launch_transfer_rows(const smplfit_transfer* t, const float* in, int batch, float* out, size_t lds, hipStream_t st) {
+  if (lds <= 160 * 1024) {
+    ensure_max_lds(reinterpret_cast<const void*>(&k_transfer_rows<true, NEG>));
+    hipLaunchKernelGGL((k_transfer_rows<true, NEG>), dim3(batch), dim3(1024), lds, st, in, out, t->d_indptr, t->d_indices,
+                       t->d_values, t->v_in, t->v_out);
+  } else {
+    hipLaunchKernelGGL((k_transfer_rows<false, NEG>), dim3(batch), dim3(1024), 0, st, in, out, t->d_indptr, t->d_indices,
+                       t->d_values, t->v_in, t->v_out);
+  }
+}
+
+// The tables of k_transfer_bm in `p` (models p->in / p->out set): the matrix (NULL = identity) re-indexed to the sorted
+// slots of the two models, uploaded to the current device.  Shared by the conversion and the flip plans.
+int upload_slot_transfer(smplfit_convert_plan* p, const smplfit_transfer* transfer, const char* who) {
+  const smplfit_handle *in = p->in, *out = p->out;
+  const int Vo = out->t.V;
+  std::vector<int32_t> inv_in(in->t.V, 0), oslot(Vo, 0), start(Vo + 1, 0), islot;
+  std::vector<float> w;
+  for (int i = 0; i < in->t.Vp; ++i)
+    if (in->t.perm[i] >= 0) inv_in[in->t.perm[i]] = i;
+  for (int i = 0; i < out->t.Vp; ++i)
+    if (out->t.perm[i] >= 0) oslot[out->t.perm[i]] = i;
+  for (int r = 0; r < Vo; ++r) {
+    if (transfer) {
+      for (int e = transfer->indptr[r]; e < transfer->indptr[r + 1]; ++e) {
+        islot.push_back(inv_in[transfer->indices[e]]);
+        w.push_back(transfer->values[e]);
+      }
+    } else {  // same topology: the identity
+      islot.push_back(inv_in[r]);
+      w.push_back(1.f);
+    }
+    start[r + 1] = (int32_t)islot.size();
+  }
+  p->nslab = (Vo + kSlabV - 1) / kSlabV;
+  p->negate_x = transfer && transfer->negate_x;
+  auto up = [&](const void* src, size_t bytes, void** dst) {
+    if (hipMalloc(dst, std::max<size_t>(bytes, 16)) != hipSuccess) return false;
+    return bytes == 0 || hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+  };
+  if (!up(oslot.data(), oslot.size() * 4, (void**)&p->d_oslot) || !up(start.data(), start.size() * 4, (void**)&p->d_start) ||
+      !up(islot.data(), islot.size() * 4, (void**)&p->d_islot) || !up(w.data(), w.size() * 4, (void**)&p->d_w))
+    return fail(SMPLFIT_ERR_HIP, std::string(who) + ": device upload failed");
+  return 0;
+}
+
+void free_slot_transfer(smplfit_convert_plan* p) {
+  for (void* q : {(void*)p->d_oslot, (void*)p->d_start, (void*)p->d_islot, (void*)p->d_w})
+    if (q) (void)hipFree(q);
+}
+
+// the naively flipped pose of smplfit_flip_f32 at the front of its workspace; the fit's workspace follows
+size_t flip_pose_bytes(const smplfit_handle* h, int batch) { return align_up((size_t)batch * h->t.J * 3 * 4, 256); }
 
 
 }  // namespace
@@ -2522,6 +2601,8 @@ int smplfit_transfer_create(int32_t num_vertices_in, int32_t num_vertices_out, c
   if (!out || !indptr || num_vertices_in <= 0 || num_vertices_out <= 0)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_transfer_create: null argument / empty matrix");
   *out = nullptr;
+  if (flags & ~(SMPLFIT_CREATE_HOST_ONLY | SMPLFIT_TRANSFER_NEGATE_X))
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_transfer_create: unknown flag bits");
   if (indptr[0] != 0) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_transfer_create: indptr[0] must be 0");
   for (int r = 0; r < num_vertices_out; ++r)
     if (indptr[r + 1] < indptr[r]) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_transfer_create: indptr must not decrease");
@@ -2536,6 +2617,7 @@ int smplfit_transfer_create(int32_t num_vertices_in, int32_t num_vertices_out, c
   t->indptr.assign(indptr, indptr + num_vertices_out + 1);
   t->indices.assign(indices, indices + nnz);
   t->values.assign(values, values + nnz);
+  t->negate_x = (flags & SMPLFIT_TRANSFER_NEGATE_X) != 0;
   if (!(flags & SMPLFIT_CREATE_HOST_ONLY)) {
     auto up = [&](const void* src, size_t bytes, void** dst) {
       if (hipMalloc(dst, std::max<size_t>(bytes, 16)) != hipSuccess) return false;
@@ -2568,14 +2650,8 @@ int smplfit_transfer_f32(const smplfit_transfer* t, const float* in_vertices, in
   if (batch == 0) return SMPLFIT_OK;
   hipStream_t st = (hipStream_t)hip_stream;
   const size_t lds = (size_t)t->v_in * 12;
-  if (lds <= 160 * 1024) {
-    ensure_max_lds(reinterpret_cast<const void*>(&k_transfer_rows<true>));
-    hipLaunchKernelGGL(k_transfer_rows<true>, dim3(batch), dim3(1024), lds, st, in_vertices, out_vertices, t->d_indptr,
-                       t->d_indices, t->d_values, t->v_in, t->v_out);
-  } else {
-    hipLaunchKernelGGL(k_transfer_rows<false>, dim3(batch), dim3(1024), 0, st, in_vertices, out_vertices, t->d_indptr,
-                       t->d_indices, t->d_values, t->v_in, t->v_out);
-  }
+  if (t->negate_x) launch_transfer_rows<true>(t, in_vertices, batch, out_vertices, lds, st);
+  else launch_transfer_rows<false>(t, in_vertices, batch, out_vertices, lds, st);
   return post_launch_check();
 }
 
@@ -2593,37 +2669,12 @@ int smplfit_convert_plan_create(const smplfit_handle* in, const smplfit_handle* 
                 "smplfit_convert_plan_create: the fused conversion needs the batch-major kernels on both models "
                 "(<= 4 skinning weights per vertex, 10 betas, >= 1024 vertices) and the output model's joint "
                 "regressor; use forward + smplfit_transfer_f32 + fit");
-  const int Vo = out->t.V;
-  std::vector<int32_t> inv_in(in->t.V, 0), oslot(Vo, 0), start(Vo + 1, 0), islot;
-  std::vector<float> w;
-  for (int i = 0; i < in->t.Vp; ++i)
-    if (in->t.perm[i] >= 0) inv_in[in->t.perm[i]] = i;
-  for (int i = 0; i < out->t.Vp; ++i)
-    if (out->t.perm[i] >= 0) oslot[out->t.perm[i]] = i;
-  for (int r = 0; r < Vo; ++r) {
-    if (transfer) {
-      for (int e = transfer->indptr[r]; e < transfer->indptr[r + 1]; ++e) {
-        islot.push_back(inv_in[transfer->indices[e]]);
-        w.push_back(transfer->values[e]);
-      }
-    } else {  // same topology: the identity
-      islot.push_back(inv_in[r]);
-      w.push_back(1.f);
-    }
-    start[r + 1] = (int32_t)islot.size();
-  }
   auto* p = new smplfit_convert_plan();
   p->in = in;
   p->out = out;
-  p->nslab = (Vo + kSlabV - 1) / kSlabV;
-  auto up = [&](const void* src, size_t bytes, void** dst) {
-    if (hipMalloc(dst, std::max<size_t>(bytes, 16)) != hipSuccess) return false;
-    return bytes == 0 || hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
-  if (!up(oslot.data(), oslot.size() * 4, (void**)&p->d_oslot) || !up(start.data(), start.size() * 4, (void**)&p->d_start) ||
-      !up(islot.data(), islot.size() * 4, (void**)&p->d_islot) || !up(w.data(), w.size() * 4, (void**)&p->d_w)) {
+  if (int rc = upload_slot_transfer(p, transfer, "smplfit_convert_plan_create")) {
     smplfit_convert_plan_destroy(p);
-    return fail(SMPLFIT_ERR_HIP, "smplfit_convert_plan_create: device upload failed");
+    return rc;
   }
   *plan = p;
   return SMPLFIT_OK;
@@ -2631,8 +2682,7 @@ int smplfit_convert_plan_create(const smplfit_handle* in, const smplfit_handle* 
 
 void smplfit_convert_plan_destroy(smplfit_convert_plan* p) {
   if (!p) return;
-  for (void* q : {(void*)p->d_oslot, (void*)p->d_start, (void*)p->d_islot, (void*)p->d_w})
-    if (q) (void)hipFree(q);
+  free_slot_transfer(p);
   delete p;
 }
 
@@ -2666,8 +2716,101 @@ int smplfit_convert_f32(const smplfit_convert_plan* p, const smplfit_convert_arg
   f.workspace = a->workspace;
   f.workspace_bytes = a->workspace_bytes;
   f.hip_stream = a->hip_stream;
-  ConvertJob job{p, a->pose_rotvecs, a->shape_betas, a->trans, a->shape_betas ? a->num_betas_given : 0};
+  ConvertJob job{p, a->pose_rotvecs, a->shape_betas, a->trans, a->shape_betas ? a->num_betas_given : 0, nullptr};
   return fit_impl(p->out, &f, &job);
+}
+
+// ---- fused flip (BodyFlipper.flip) ------------------------------------------------------------------
+// The conversion's pipeline with in = out = the kid handle: the mirror matrix (x negated in k_transfer_bm), the input
+// mesh evaluated with kid_factor, and a warm-started fit (k_naive_flip writes its initial pose to the workspace).
+int smplfit_flip_plan_create(const smplfit_handle* h, const smplfit_transfer* mirror, const int32_t* joint_perm,
+                             smplfit_flip_plan** plan) {
+  if (!h || !mirror || !joint_perm || !plan) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_plan_create: null argument");
+  *plan = nullptr;
+  if (mirror->v_in != h->t.V || mirror->v_out != h->t.V)
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_plan_create: the mirror matrix is not (V x V) for this model");
+  const int J = h->t.J;
+  for (int j = 0; j < J; ++j)
+    if (joint_perm[j] < 0 || joint_perm[j] >= J || joint_perm[joint_perm[j]] != j)
+      return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_plan_create: joint_perm must map [0, J) onto itself and be an involution");
+  if (!h->has_device) return fail(SMPLFIT_ERR_HIP, "smplfit_flip_plan_create: the handle needs a device");
+  const CallShape conv{Entry::kConvert, false};  // (whether the route is batch-major does not depend on the batch)
+  if (!route_of(h, 1, conv).bm || !h->t.has_regressor)
+    return fail(SMPLFIT_ERR_UNSUPPORTED,
+                "smplfit_flip_plan_create: the fused flip needs the batch-major kernels (<= 8 skinning weights per "
+                "vertex, 10 / 16 betas, >= 1024 vertices) and the model's joint regressor; use forward + "
+                "smplfit_transfer_f32 + smplfit_fit_warm_f32");
+  auto* p = new smplfit_flip_plan();
+  p->conv.in = h;
+  p->conv.out = h;
+  int rc = upload_slot_transfer(&p->conv, mirror, "smplfit_flip_plan_create");
+  if (!rc && (hipMalloc((void**)&p->d_perm, (size_t)J * 4) != hipSuccess ||
+              hipMemcpy(p->d_perm, joint_perm, (size_t)J * 4, hipMemcpyHostToDevice) != hipSuccess))
+    rc = fail(SMPLFIT_ERR_HIP, "smplfit_flip_plan_create: device upload failed");
+  if (rc) {
+    smplfit_flip_plan_destroy(p);
+    return rc;
+  }
+  *plan = p;
+  return SMPLFIT_OK;
+}
+
+void smplfit_flip_plan_destroy(smplfit_flip_plan* p) {
+  if (!p) return;
+  free_slot_transfer(&p->conv);
+  if (p->d_perm) (void)hipFree(p->d_perm);
+  delete p;
+}
+
+size_t smplfit_flip_workspace_bytes(const smplfit_flip_plan* p, int batch) {
+  if (!p || batch <= 0) return 0;
+  return flip_pose_bytes(p->conv.out, batch) + chunked_workspace_bytes(p->conv.out->t, batch, &p->conv.in->t);
+}
+
+int smplfit_flip_f32(const smplfit_flip_plan* p, const smplfit_flip_args* a) {
+  if (!p || !a) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: null argument");
+  const smplfit_handle* h = p->conv.out;
+  const int B = a->batch;
+  if (!a->pose_rotvecs) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: pose_rotvecs is required");
+  if (B <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: batch must be positive");
+  if (a->shape_betas && (a->num_betas_given < 0 || a->num_betas_given > h->t.num_betas()))
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: more betas than the model holds; slice first");
+  if (!a->out_pose_rotvecs || !a->out_shape_betas || !a->out_trans)
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: null output pointer");
+  if (a->num_iter < 1) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: num_iter must be >= 1");
+  if (!a->workspace || ((uintptr_t)a->workspace & 255))
+    return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
+  if (a->workspace_bytes < smplfit_flip_workspace_bytes(p, B))
+    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (see smplfit_flip_workspace_bytes)");
+  // the plan was made while the batch-major path applied; a later smplfit_reload_options may have switched it off
+  const CallShape conv{Entry::kConvert, false};
+  if (!route_of(h, B, conv).bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "smplfit_flip_f32: the batch-major path is switched off");
+  hipStream_t st = (hipStream_t)a->hip_stream;
+  const size_t pose_bytes = flip_pose_bytes(h, B);
+  float* init_pose = (float*)a->workspace;
+  hipLaunchKernelGGL(k_naive_flip, dim3((B + 255) / 256), dim3(256), 0, st, a->pose_rotvecs, p->d_perm, init_pose, B, h->t.J);
+  smplfit_fit_args f{};
+  f.batch = B;
+  f.num_iter = a->num_iter;
+  f.beta_regularizer = a->beta_regularizer;
+  f.beta_regularizer2 = a->beta_regularizer2;
+  f.kid_regularizer = a->kid_regularizer;
+  f.final_adjust_rots = a->final_adjust_rots;
+  f.initial_pose_rotvecs = init_pose;
+  f.initial_shape_betas = a->shape_betas;
+  f.num_initial_betas = a->shape_betas ? a->num_betas_given : 0;
+  f.pose_rotvecs = a->out_pose_rotvecs;
+  f.shape_betas = a->out_shape_betas;
+  f.trans = a->out_trans;
+  f.kid_factor = a->out_kid_factor;
+  f.orientations = a->out_orientations;
+  f.relative_orientations = a->out_relative_orientations;
+  f.workspace = (char*)a->workspace + pose_bytes;
+  f.workspace_bytes = a->workspace_bytes - pose_bytes;
+  f.hip_stream = a->hip_stream;
+  ConvertJob job{&p->conv, a->pose_rotvecs, a->shape_betas, a->trans, a->shape_betas ? a->num_betas_given : 0,
+                 a->kid_factor};
+  return fit_impl(h, &f, &job);
 }
 
 int smplfit_reload_options(void) {
