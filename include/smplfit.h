@@ -73,7 +73,7 @@ const char* smplfit_last_error(void);
 const char* smplfit_version(void);
 /* Version of this header's structs and entry points; bumped whenever a struct gains a field or a signature
  * changes.  A client compares it with the SMPLFIT_ABI_VERSION it was built against before the first call. */
-#define SMPLFIT_ABI_VERSION 6
+#define SMPLFIT_ABI_VERSION 7
 int smplfit_abi_version(void);
 
 typedef struct smplfit_info {
@@ -191,6 +191,41 @@ typedef struct smplfit_forward_args {
   void* hip_stream;
 } smplfit_forward_args;
 int smplfit_forward_ex_f32(const smplfit_handle* h, const smplfit_forward_args* args);
+
+/* Vector-Jacobian product of smplfit_forward_ex_f32 (the backward of BodyModel.forward under autograd).
+ * Inputs: the forward's, exactly as in the forward arguments struct (one rotation form or none).  Upstream gradients, each may
+ * be NULL (= zero): grad_vertices (B,V,3), grad_joints (B,J,3), grad_orientations (B,J,3,3).  Outputs, each may be
+ * NULL (= not wanted): the gradient of the rotation form given (grad_pose_rotvecs (B,3J) | grad_glob_rotmats (B,J,3,3)
+ * | grad_rel_rotmats (B,J,3,3)), grad_shape_betas (B,num_betas_given), grad_trans (B,3), grad_kid_factor (B).
+ * The call recomputes the forward's joint stage and posedirs product from the inputs (nothing is kept from a forward
+ * call); with grad_vertices NULL no vertex-sized kernel runs.  Rotation vectors: the derivative of the exponential
+ * map at r = 0 is [e_i]x (the reference's autograd returns 0 there).  Deterministic: no float atomics.
+ * Workspace: smplfit_forward_backward_workspace_bytes (its own query; smplfit_workspace_bytes is unchanged).
+ * Zero-initialise. */
+size_t smplfit_forward_backward_workspace_bytes(const smplfit_handle* h, int batch);
+typedef struct smplfit_forward_backward_args {
+  const float* pose_rotvecs;       /* (B,3J) or NULL */
+  const float* glob_rotmats;       /* (B,J,3,3) or NULL */
+  const float* rel_rotmats;        /* (B,J,3,3) or NULL */
+  const float* shape_betas;        /* (B,num_betas_given) or NULL */
+  int32_t num_betas_given;
+  const float* trans;              /* (B,3) or NULL (the gradients do not depend on it) */
+  const float* kid_factor;         /* (B) or NULL (kid handles only) */
+  int32_t batch;
+  const float* grad_vertices;      /* (B,V,3) or NULL */
+  const float* grad_joints;        /* (B,J,3) or NULL */
+  const float* grad_orientations;  /* (B,J,3,3) or NULL */
+  float* grad_pose_rotvecs;        /* out (B,3J) or NULL */
+  float* grad_glob_rotmats;        /* out (B,J,3,3) or NULL */
+  float* grad_rel_rotmats;         /* out (B,J,3,3) or NULL */
+  float* grad_shape_betas;         /* out (B,num_betas_given) or NULL */
+  float* grad_trans;               /* out (B,3) or NULL */
+  float* grad_kid_factor;          /* out (B) or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  void* hip_stream;
+} smplfit_forward_backward_args;
+int smplfit_forward_backward_f32(const smplfit_handle* h, const smplfit_forward_backward_args* args);
 
 /* BodyFitter.fit with a warm start (pt/bodyfitter.py:363-382): smplfit_fit_f32 plus
  *   initial_pose_rotvecs (B,3J) or NULL, initial_shape_betas (B,num_initial_betas) or NULL,

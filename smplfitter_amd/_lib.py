@@ -25,7 +25,7 @@ SMPLFIT_ERR_WORKSPACE = -3
 SMPLFIT_ERR_HIP = -4
 SMPLFIT_CREATE_HOST_ONLY = 1
 SMPLFIT_TRANSFER_NEGATE_X = 2  # smplfit_transfer_create: x -> -x after the product (the mirror)
-SMPLFIT_ABI_VERSION = 6  # include/smplfit.h; checked against smplfit_abi_version() when the library is loaded
+SMPLFIT_ABI_VERSION = 7  # include/smplfit.h; checked against smplfit_abi_version() when the library is loaded
 
 TABLE_IDS = dict(
     part_assignment=0, sort_perm=1, part_type=2, fk_order=3, fk_level_start=4, adj_flag=5,
@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = [
     'smplfit_convert_plan_create', 'smplfit_convert_plan_destroy', 'smplfit_convert_workspace_bytes',
     'smplfit_convert_f32', 'smplfit_flip_plan_create', 'smplfit_flip_plan_destroy', 'smplfit_flip_workspace_bytes',
     'smplfit_flip_f32', 'smplfit_reload_options', 'smplfit_get_share_table', 'smplfit_pick_share_mult',
-    'smplfit_abi_version',
+    'smplfit_abi_version', 'smplfit_forward_backward_workspace_bytes', 'smplfit_forward_backward_f32',
 ]  # fmt: skip
 
 _fp = C.POINTER(C.c_float)
@@ -95,6 +95,19 @@ class ForwardArgs(C.Structure):
         ('shape_betas', C.c_void_p), ('num_betas_given', C.c_int32), ('trans', C.c_void_p),
         ('kid_factor', C.c_void_p), ('batch', C.c_int32), ('vertices', C.c_void_p), ('joints', C.c_void_p),
         ('orientations', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
+        ('hip_stream', C.c_void_p),
+    ]
+
+
+class ForwardBackwardArgs(C.Structure):
+    """smplfit_forward_backward_args (include/smplfit.h)."""
+    _fields_ = [
+        ('pose_rotvecs', C.c_void_p), ('glob_rotmats', C.c_void_p), ('rel_rotmats', C.c_void_p),
+        ('shape_betas', C.c_void_p), ('num_betas_given', C.c_int32), ('trans', C.c_void_p),
+        ('kid_factor', C.c_void_p), ('batch', C.c_int32), ('grad_vertices', C.c_void_p), ('grad_joints', C.c_void_p),
+        ('grad_orientations', C.c_void_p), ('grad_pose_rotvecs', C.c_void_p), ('grad_glob_rotmats', C.c_void_p),
+        ('grad_rel_rotmats', C.c_void_p), ('grad_shape_betas', C.c_void_p), ('grad_trans', C.c_void_p),
+        ('grad_kid_factor', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
         ('hip_stream', C.c_void_p),
     ]
 
@@ -215,6 +228,10 @@ def load():
     lib.smplfit_primitives_f32.restype = i32
     lib.smplfit_forward_ex_f32.argtypes = [vp, C.POINTER(ForwardArgs)]
     lib.smplfit_forward_ex_f32.restype = i32
+    lib.smplfit_forward_backward_workspace_bytes.argtypes = [vp, i32]
+    lib.smplfit_forward_backward_workspace_bytes.restype = sz
+    lib.smplfit_forward_backward_f32.argtypes = [vp, C.POINTER(ForwardBackwardArgs)]
+    lib.smplfit_forward_backward_f32.restype = i32
     lib.smplfit_transfer_create.argtypes = [i32, i32, _ip, _ip, _fp, i32, C.POINTER(vp)]
     lib.smplfit_transfer_create.restype = i32
     lib.smplfit_transfer_destroy.argtypes = [vp]
@@ -344,6 +361,9 @@ class Handle:
 
     def workspace_bytes(self, batch: int) -> int:
         return int(load().smplfit_workspace_bytes(self._h, int(batch)))
+
+    def forward_backward_workspace_bytes(self, batch: int) -> int:
+        return int(load().smplfit_forward_backward_workspace_bytes(self._h, int(batch)))
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h.value:

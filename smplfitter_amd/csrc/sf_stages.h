@@ -1503,6 +1503,200 @@ SF_HD void partsum_vertex(const float* t, const float* a_in, float w, bool weigh
   acc[15] += weighted ? w : 1.0f;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Backward of forward_joint_stage (smplfit_forward_backward_f32), ONE lane per instance.
+// Recomputes the forward's rotations, rest joints and FK positions from the inputs, then folds the cotangents back
+// through the chain in reverse tree order:
+//   dA (J,12) or NULL: [dG_k (3x3 row-major) | dt_k] of the vertex pass, sum_v w_vk g_v (x) [v_posed_v, 1];
+//   gjoints (J,3), gorient (J,9) or NULL: the caller's cotangents of joints / orientations;
+//   dfeat (P) or NULL: the pose-feature cotangent, feature order (j-1)*9 + k;
+//   dshape (S) or NULL: shapedirs^T dv_posed of the vertex pass (kid column last).
+// Outputs (each may be NULL): the gradient of the rotation form given (g_pose (J,3) | g_glob (J,9) | g_rel (J,9)),
+// g_betas (nb), g_kid (1), g_trans_joints (3) = sum_j gjoints_j.  scratch: joint_bwd_scratch_floats(J).
+// Rotation vectors: the true derivative of the exponential map, by a series below an angle of 0.5 (at r = 0:
+// dR/dr_i = [e_i]x; the reference's autograd returns 0 there).
+// ---------------------------------------------------------------------------------------------
+SF_HD int joint_bwd_scratch_floats(int J) { return J * 48; }
+
+// d<dR, R(r)>/dr for the exponential map R = I + a K + b K^2, K = [r]x, theta = |r|
+SF_HD void rotvec2mat_vjp(const float* r, const float* dR, float* dr) {
+  const float t2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2], th = sqrtf(t2);
+  float a, b, c, d;  // a = sin/t, b = (1 - cos)/t^2, c = a'/t, d = b'/t
+  if (th < 0.5f) {
+    const float t4 = t2 * t2, t6 = t4 * t2;
+    a = 1.f - t2 / 6.f + t4 / 120.f - t6 / 5040.f;
+    b = 0.5f - t2 / 24.f + t4 / 720.f - t6 / 40320.f;
+    c = -1.f / 3.f + t2 / 30.f - t4 / 840.f + t6 / 45360.f;
+    d = -1.f / 12.f + t2 / 180.f - t4 / 6720.f + t6 / 453600.f;
+  } else {
+    const float sn = sinf(th), cs = cosf(th);
+    a = sn / th;
+    b = (1.f - cs) / t2;
+    c = (th * cs - sn) / (t2 * th);
+    d = (th * sn - 2.f * (1.f - cs)) / (t2 * t2);
+  }
+  const float K[9] = {0.f, -r[2], r[1], r[2], 0.f, -r[0], -r[1], r[0], 0.f};
+  float K2[9];
+  m3_mul(K, K, K2);
+  // <dR, K>, <dR, K^2>
+  float dK = 0.f, dK2 = 0.f;
+  for (int e = 0; e < 9; ++e) {
+    dK += dR[e] * K[e];
+    dK2 += dR[e] * K2[e];
+  }
+  for (int i = 0; i < 3; ++i) {
+    float E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // [e_i]x
+    if (i == 0) { E[5] = -1.f; E[7] = 1.f; }
+    if (i == 1) { E[2] = 1.f; E[6] = -1.f; }
+    if (i == 2) { E[1] = -1.f; E[3] = 1.f; }
+    float EK[9], KE[9];
+    m3_mul(E, K, EK);
+    m3_mul(K, E, KE);
+    float s = c * r[i] * dK + d * r[i] * dK2;
+    for (int e = 0; e < 9; ++e) s += dR[e] * (a * E[e] + b * (EK[e] + KE[e]));
+    dr[i] = s;
+  }
+}
+
+SF_HD void forward_joint_backward(const JointTabs& tb, const float* pose_rotvecs, const float* glob_in,
+                                  const float* rel_in, const float* betas, int nb, const float* kid,
+                                  const float* dA, const float* gjoints, const float* gorient, const float* dfeat,
+                                  const float* dshape, float* scratch, float* g_pose, float* g_glob, float* g_rel,
+                                  float* g_betas, float* g_kid, float* g_trans_joints) {
+  const int J = tb.J, S = tb.S, S1 = S + 1, nfk = tb.fk_level_start[tb.num_levels];
+  float* R = scratch;          // (J,9) relative rotations
+  float* G = R + J * 9;        // (J,9) global rotations
+  float* dG = G + J * 9;       // (J,9)
+  float* dR = dG + J * 9;      // (J,9)
+  float* Jr = dR + J * 9;      // (J,3) rest joints at the shape
+  float* pos = Jr + J * 3;     // (J,3) FK positions
+  float* dpos = pos + J * 3;   // (J,3)
+  float* dJr = dpos + J * 3;   // (J,3)
+  // ---- forward recompute (forward_joint_stage's arithmetic)
+  for (int j = 0; j < J; ++j) {
+    float* m = R + j * 9;
+    if (glob_in) {
+      for (int k = 0; k < 9; ++k) G[j * 9 + k] = glob_in[j * 9 + k];
+    } else if (rel_in) {
+      for (int k = 0; k < 9; ++k) m[k] = rel_in[j * 9 + k];
+    } else if (pose_rotvecs) {
+      rotvec2mat(pose_rotvecs + j * 3, m);
+    } else {
+      m3_identity(m);
+    }
+  }
+  if (!glob_in) {
+    for (int k = 0; k < 9; ++k) G[k] = R[k];
+    for (int q = 0; q < nfk; ++q) {
+      const int j = tb.fk_js[q];
+      m3_mul(G + tb.parents[j] * 9, R + j * 9, G + j * 9);
+    }
+  }
+  for (int k = 0; k < J * 3; ++k) {
+    float acc = 0.f;
+    for (int s = 0; s < nb; ++s) acc += tb.j_ext[k * S1 + 1 + s] * betas[s];
+    if (kid && tb.n_kid) acc += tb.j_ext[k * S1 + S] * kid[0];
+    Jr[k] = tb.j_ext[k * S1] + acc;
+  }
+  for (int c = 0; c < 3; ++c) pos[c] = Jr[c];
+  for (int q = 0; q < nfk; ++q) {
+    const int j = tb.fk_js[q], p = tb.parents[j];
+    const float bone[3] = {Jr[j * 3] - Jr[p * 3], Jr[j * 3 + 1] - Jr[p * 3 + 1], Jr[j * 3 + 2] - Jr[p * 3 + 2]};
+    float rb[3];
+    m3_vec(G + p * 9, bone, rb);
+    for (int c = 0; c < 3; ++c) pos[j * 3 + c] = pos[p * 3 + c] + rb[c];
+  }
+  // ---- seeds: dA, orientations, joints; t_k = pos_k - G_k Jr_k
+  float gt[3] = {0.f, 0.f, 0.f};
+  for (int j = 0; j < J; ++j) {
+    const float* a = dA ? dA + j * 12 : nullptr;
+    for (int k = 0; k < 9; ++k) {
+      dG[j * 9 + k] = (a ? a[k] : 0.f) + (gorient ? gorient[j * 9 + k] : 0.f);
+      dR[j * 9 + k] = 0.f;
+    }
+    const float dt[3] = {a ? a[9] : 0.f, a ? a[10] : 0.f, a ? a[11] : 0.f};
+    for (int c = 0; c < 3; ++c) {
+      const float gj = gjoints ? gjoints[j * 3 + c] : 0.f;
+      gt[c] += gj;
+      dpos[j * 3 + c] = dt[c] + gj;
+      for (int e = 0; e < 3; ++e) dG[j * 9 + c * 3 + e] -= dt[c] * Jr[j * 3 + e];
+    }
+    for (int e = 0; e < 3; ++e)
+      dJr[j * 3 + e] = -(G[j * 9 + e] * dt[0] + G[j * 9 + 3 + e] * dt[1] + G[j * 9 + 6 + e] * dt[2]);
+  }
+  // ---- positions, reverse tree order: pos_j = pos_p + G_p (Jr_j - Jr_p)
+  for (int q = nfk - 1; q >= 0; --q) {
+    const int j = tb.fk_js[q], p = tb.parents[j];
+    const float* dp = dpos + j * 3;
+    const float* Gp = G + p * 9;
+    for (int c = 0; c < 3; ++c) {
+      dpos[p * 3 + c] += dp[c];
+      for (int e = 0; e < 3; ++e) dG[p * 9 + c * 3 + e] += dp[c] * (Jr[j * 3 + e] - Jr[p * 3 + e]);
+    }
+    for (int e = 0; e < 3; ++e) {
+      const float v = Gp[e] * dp[0] + Gp[3 + e] * dp[1] + Gp[6 + e] * dp[2];
+      dJr[j * 3 + e] += v;
+      dJr[p * 3 + e] -= v;
+    }
+  }
+  for (int c = 0; c < 3; ++c) dJr[c] += dpos[c];
+  // ---- shape: J_shapedirs^T dJr (+ the vertex pass's shapedirs^T dv_posed)
+  if (g_betas)
+    for (int s = 0; s < nb; ++s) {
+      float acc = dshape ? dshape[s] : 0.f;
+      for (int k = 0; k < J * 3; ++k) acc += tb.j_ext[k * S1 + 1 + s] * dJr[k];
+      g_betas[s] = acc;
+    }
+  if (g_kid) {
+    float acc = 0.f;
+    if (tb.n_kid) {
+      acc = dshape ? dshape[S - 1] : 0.f;
+      for (int k = 0; k < J * 3; ++k) acc += tb.j_ext[k * S1 + S] * dJr[k];
+    }
+    g_kid[0] = acc;
+  }
+  if (g_trans_joints)
+    for (int c = 0; c < 3; ++c) g_trans_joints[c] = gt[c];
+  // ---- pose features (j >= 1): rel_j, or G_p^T G_j for global rotations given
+  if (dfeat)
+    for (int j = 1; j < J; ++j) {
+      const float* df = dfeat + (j - 1) * 9;
+      if (glob_in) {
+        const int p = tb.parents[j];
+        float a[9], b[9];
+        m3_mul(G + p * 9, df, a);   // d/dG_j (G_p^T G_j) = G_p dF
+        m3_mult(G + j * 9, df, b);  // d/dG_p = G_j dF^T
+        for (int k = 0; k < 9; ++k) {
+          dG[j * 9 + k] += a[k];
+          dG[p * 9 + k] += b[k];
+        }
+      } else {
+        for (int k = 0; k < 9; ++k) dR[j * 9 + k] += df[k];
+      }
+    }
+  if (glob_in) {
+    if (g_glob)
+      for (int k = 0; k < J * 9; ++k) g_glob[k] = dG[k];
+    return;
+  }
+  // ---- rotations, reverse tree order: G_j = G_p R_j
+  for (int q = nfk - 1; q >= 0; --q) {
+    const int j = tb.fk_js[q], p = tb.parents[j];
+    float a[9], b[9];
+    m3_tmul(G + p * 9, dG + j * 9, a);   // dR_j += G_p^T dG_j
+    m3_mult(dG + j * 9, R + j * 9, b);   // dG_p += dG_j R_j^T
+    for (int k = 0; k < 9; ++k) {
+      dR[j * 9 + k] += a[k];
+      dG[p * 9 + k] += b[k];
+    }
+  }
+  for (int k = 0; k < 9; ++k) dR[k] += dG[k];
+  if (g_rel && rel_in)
+    for (int k = 0; k < J * 9; ++k) g_rel[k] = dR[k];
+  if (g_pose && pose_rotvecs)
+    for (int j = 0; j < J; ++j) rotvec2mat_vjp(pose_rotvecs + j * 3, dR + j * 9, g_pose + j * 3);
+}
+
 #undef SF_FOR
 
 }  // namespace sf

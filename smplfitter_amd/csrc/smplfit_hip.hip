@@ -13,6 +13,7 @@
 //   k_lbs_partsum          K5  vertices at the solved shape fused with the part sums of the next rotation pass
 //   k_refine_epilogue      K6  dependent rotation refinement + relative rotations + log map
 //   k_forward_joint, k_lbs_partsum<MODE 2>   BodyModel.forward;  k_scale_trans  known-shape alignment
+//   k_bwd_vertex, k_bwd_reduce, k_bwd_combine, k_bwd_joint   its backward (kernels_bwd.inc)
 // Batch-major kernels (LANE = INSTANCE; the default vertex block where they apply, see route_of): k_layout_targets,
 //   k_mean_finish, k_template_partsum_bm, k_residual_bm, k_pair_gram_bm, k_gram_combine_bm, k_lbs_partsum_bm,
 //   k_psum_combine, k_regress_joints_bm, k_transpose_targets (joint rows) — grid = (vertex group | unit chunk) x
@@ -420,6 +421,7 @@ __device__ __forceinline__ void st_stream(float* p, float v) {
 #include "kernels_wave.inc"
 #include "kernels_bm.inc"
 #include "kernels_gen.inc"
+#include "kernels_bwd.inc"
 
 // ------------------------------------------------------------------------------------------------
 // launch helpers
@@ -1183,12 +1185,14 @@ void launch_refine_bm(const smplfit_handle* h, RefineArgs ra, const ShareView& s
 //                                                                      pass; else k_refine_epilogue (+ k_gt_to_g first
 //                                                                      when k_rotations_bm ran)
 //   no weights in the solve, not general; bm or SHAPE_FORM=pair      -> pair-Gram form (not the scaled solve of bm)
+//   forward backward (smplfit_forward_backward_f32)                -> never bm: the instance-major kernels of
+//                                                                      kernels_bwd.inc serve every model
 //   flip (smplfit_flip_f32): the conversion's entry (kConvert, no    -> bm as a conversion; k_naive_flip, then the source
 //     target joints) with warm = true; not bm: no fused call           of the conversion with k_transfer_bm<true> and
 //                                                                      no k_template_partsum_bm (the first rotation pass
 //                                                                      reads the warm start's LBS rows, kShareLbsAll)
 // ------------------------------------------------------------------------------------------------
-enum class Entry { kFit, kConvert, kShapeSolve, kForward, kKnownShape };
+enum class Entry { kFit, kConvert, kShapeSolve, kForward, kKnownShape, kForwardBackward };
 struct CallShape {
   Entry entry = Entry::kFit;
   bool joints = true;                // target joints given
@@ -1221,6 +1225,7 @@ Route route_of(const smplfit_handle* h, int B, const CallShape& c) {
   const bool model_bm = tn.bm && (d.KW == 4 || d.KW == 8) && sf::bm_shape_count(d.S) && d.bm_tables && d.V >= 1024 &&
                         d.Vp > d.V && h->t.wsum_dev <= 1e-5f;
   const bool accum_w = d.S == 10 && d.KW == 4;  // what k_accum_w_bm is built for
+  if (c.entry == Entry::kForwardBackward) return r;
   const bool solves = c.entry != Entry::kForward && c.entry != Entry::kKnownShape;
   if (c.entry == Entry::kForward) r.bm = model_bm && tn.bm_forward;
   else if (c.entry == Entry::kKnownShape) r.bm = model_bm && (!c.vw || tn.bm_weighted) && tn.bm_known_shape;
@@ -2475,6 +2480,99 @@ int smplfit_forward_ex_f32(const smplfit_handle* h, const smplfit_forward_args* 
     launch_gemm(d, ws, batch, st);
     if (int rc = launch_lbs_any<2>(d, ws, batch, false, fa.nb, shape_betas, trans, vertices, st, kid_factor)) return rc;
   }
+  return post_launch_check();
+}
+
+// the forward's workspace, then BwdWorkspace
+size_t forward_backward_carve(const smplfit_handle* h, int B, char* base, Workspace* ws, BwdWorkspace* bw) {
+  const sf::HostTables& t = h->t;
+  size_t off = align_up(carve(t, B, base, ws), 256);
+  auto take = [&](size_t bytes) {
+    size_t o = off;
+    off = align_up(off + bytes, 256);
+    return base ? (float*)(base + o) : nullptr;
+  };
+  const size_t NC = (size_t)t.P + t.S;
+  bw->dvp = take((size_t)B * 3 * t.Vp * 4);
+  bw->dA = take((size_t)B * t.J * 12 * 4);
+  bw->dtv = take((size_t)B * 3 * 4);
+  bw->part = take((size_t)bwd_nsplit(t.Vp) * B * NC * 4);
+  bw->dfeat = take((size_t)B * NC * 4);
+  bw->jscr = take((size_t)B * sf::joint_bwd_scratch_floats(t.J) * 4);
+  return off;
+}
+
+size_t smplfit_forward_backward_workspace_bytes(const smplfit_handle* h, int batch) {
+  if (!h || batch <= 0) return 0;
+  Workspace ws;
+  BwdWorkspace bw;
+  return forward_backward_carve(h, batch, nullptr, &ws, &bw);
+}
+
+int smplfit_forward_backward_f32(const smplfit_handle* h, const smplfit_forward_backward_args* a) {
+  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_backward_f32: null arguments");
+  const int B = a->batch;
+  if (!h) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_backward_f32: null handle");
+  if (!h->has_device) return fail(SMPLFIT_ERR_HIP, "handle was created host-only (no device)");
+  if (B <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "batch must be positive");
+  if (!a->workspace || ((uintptr_t)a->workspace & 255))
+    return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
+  if (a->workspace_bytes < smplfit_forward_backward_workspace_bytes(h, B))
+    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (smplfit_forward_backward_workspace_bytes)");
+  if ((a->pose_rotvecs != nullptr) + (a->glob_rotmats != nullptr) + (a->rel_rotmats != nullptr) > 1)
+    return fail(SMPLFIT_ERR_BAD_ARG, "Only one rotation input may be provided");
+  const DevModel& d = h->d;
+  const int nb_max = d.S - d.jt.n_kid - d.jt.n_pad;
+  if (a->shape_betas && a->num_betas_given > nb_max)
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_backward_f32: more betas than the model holds; slice first");
+  if (a->kid_factor && !d.jt.n_kid)
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_backward_f32: kid_factor given to a handle without kid");
+  // (route_of: Entry::kForwardBackward is never batch-major; these kernels serve every model)
+  hipStream_t st = (hipStream_t)a->hip_stream;
+  Workspace ws;
+  BwdWorkspace bw;
+  forward_backward_carve(h, B, (char*)a->workspace, &ws, &bw);
+  const int nb = a->shape_betas ? std::max(0, a->num_betas_given) : 0;
+  const bool vertex = a->grad_vertices != nullptr;
+  if (vertex) {
+    // recompute: the joint block (G | t) and v_posed; then the vertex pass and the pose-feature / shape reduction
+    ForwardArgs fa{};
+    fa.pose = a->pose_rotvecs;
+    fa.glob = a->glob_rotmats;
+    fa.rel = a->rel_rotmats;
+    fa.betas = a->shape_betas;
+    fa.nb = nb;
+    fa.kid = a->kid_factor;
+    fa.trans = nullptr;
+    fa.joints = ws.rjoints;
+    fa.orient = nullptr;
+    launch_forward_joint(d, fa, ws, B, st);
+    if (int rc = launch_gemm(d, ws, B, st)) return rc;
+    const size_t lds = ((size_t)d.J * 9 + d.S + 4 * (size_t)d.J * 12 + 12) * 4;
+    hipLaunchKernelGGL(k_bwd_vertex, dim3(B), dim3(256), lds, st, d, ws, bw, B, nb, a->shape_betas, a->kid_factor,
+                       a->grad_vertices);
+    const int NC = d.P + d.S, nsplit = bwd_nsplit(d.Vp);
+    hipLaunchKernelGGL(k_bwd_reduce, dim3((NC + kBwdTile - 1) / kBwdTile, (B + kBwdTile - 1) / kBwdTile, nsplit),
+                       dim3(256), 0, st, d, bw, B);
+    hipLaunchKernelGGL(k_bwd_combine, dim3((unsigned)(((size_t)B * NC + 255) / 256)), dim3(256), 0, st, bw, B, NC, nsplit);
+  }
+  JointBwdArgs ja{};
+  ja.pose = a->pose_rotvecs;
+  ja.glob = a->glob_rotmats;
+  ja.rel = a->rel_rotmats;
+  ja.betas = a->shape_betas;
+  ja.kid = a->kid_factor;
+  ja.nb = nb;
+  ja.gjoints = a->grad_joints;
+  ja.gorient = a->grad_orientations;
+  ja.vertex = vertex;
+  ja.g_pose = a->grad_pose_rotvecs;
+  ja.g_glob = a->grad_glob_rotmats;
+  ja.g_rel = a->grad_rel_rotmats;
+  ja.g_betas = a->grad_shape_betas;
+  ja.g_trans = a->grad_trans;
+  ja.g_kid = a->grad_kid_factor;
+  hipLaunchKernelGGL(k_bwd_joint, dim3((B + 63) / 64), dim3(64), 0, st, d, bw, ja, B);
   return post_launch_check();
 }
 

@@ -11,6 +11,7 @@ from typing import Optional
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from .. import _lib, modelio
 
@@ -124,7 +125,14 @@ class BodyModel(nn.Module):
         glob_rotmats: Optional[torch.Tensor] = None,
         return_vertices: bool = True,
     ) -> dict[str, torch.Tensor]:
-        """Vertices, joints and global orientations for a batch (pt/bodymodel.py:121-307)."""
+        """Vertices, joints and global orientations for a batch (pt/bodymodel.py:121-307).
+
+        Differentiable: when gradients are enabled and a tensor input requires grad, the outputs carry a ``grad_fn``
+        whose backward is the HIP vector-Jacobian product (``smplfit_forward_backward_f32``) with respect to
+        ``pose_rotvecs`` / ``rel_rotmats`` / ``glob_rotmats``, ``shape_betas``, ``trans`` and ``kid_factor``.  The
+        model buffers are constants: they get no gradient.  Once differentiable (no double backward).  One
+        divergence from the reference: at a rotation vector of exactly zero the gradient is the true derivative of
+        the exponential map, not 0."""
         if torch.compiler.is_compiling():  # one opaque operator for torch.compile / export
             kid = kid_factor
             if kid is not None and not isinstance(kid, torch.Tensor):
@@ -136,8 +144,90 @@ class BodyModel(nn.Module):
             if return_vertices:
                 res['vertices'] = v
             return res
+        args = (pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)
+        if torch.is_grad_enabled() and any(isinstance(a, torch.Tensor) and a.requires_grad for a in args):
+            j, o, v = _ForwardFn.apply(self, return_vertices, *args)
+            res = dict(joints=j, orientations=o)
+            if return_vertices:
+                res['vertices'] = v
+            return res
         return self._forward_direct(pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats,
                                     glob_rotmats, return_vertices)
+
+    def _backward_direct(self, pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats,
+                         grad_joints=None, grad_orientations=None, grad_vertices=None):
+        """The C-ABI call behind ``forward``'s backward (``smplfit_forward_backward_f32``): the gradients of the six
+        inputs (None for an input not given), each in the caller's shape and dtype — broadcasts of ``trans`` (1, 3) and
+        of a one-element ``kid_factor`` summed over the batch, betas beyond the model's ``num_betas`` zero."""
+        device = self.v_template.device
+        J = self.num_joints
+        batch = 0
+        for arg in (pose_rotvecs, shape_betas, trans, rel_rotmats, glob_rotmats):
+            if arg is not None:
+                batch = arg.shape[0]
+                break
+        ins = (pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)
+        zeros = [None if a is None or not isinstance(a, torch.Tensor) else torch.zeros_like(a) for a in ins]
+        if batch == 0:
+            return zeros
+        prep = lambda t: None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        rel = prep(rel_rotmats.reshape(batch, J, 3, 3)) if rel_rotmats is not None else None
+        pose = prep(pose_rotvecs.reshape(batch, J * 3)) if pose_rotvecs is not None else None
+        glob = prep(glob_rotmats)
+        betas = prep(shape_betas)
+        nb = 0
+        if betas is not None:
+            nb = min(betas.shape[1], self.num_betas)
+            betas = betas[:, :nb].contiguous()
+            if nb == 0:
+                betas = None
+        kid = None
+        if isinstance(kid_factor, torch.Tensor):
+            kid = kid_factor.detach().to(device=device, dtype=torch.float32).reshape(-1)
+            kid = kid.expand(batch).contiguous() if kid.numel() == 1 else kid.contiguous()
+        elif kid_factor is not None:
+            kid = torch.full((batch,), float(kid_factor), dtype=torch.float32, device=device)
+        g = lambda t: None if t is None or t.numel() == 0 else prep(t)  # noqa: E731
+        gj, go, gv = g(grad_joints), g(grad_orientations), g(grad_vertices)
+        new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=device)  # noqa: E731
+        g_pose = new(batch, J * 3) if pose is not None else None
+        g_rel = new(batch, J, 3, 3) if rel is not None else None
+        g_glob = new(batch, J, 3, 3) if glob is not None else None
+        g_betas = new(batch, nb) if betas is not None else None
+        g_trans = new(batch, 3) if trans is not None else None
+        g_kid = new(batch) if isinstance(kid_factor, torch.Tensor) else None
+        h = self._native(device, kid=kid is not None)
+        ws = torch.empty(h.forward_backward_workspace_bytes(batch), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            args = _lib.ForwardBackwardArgs(
+                pose_rotvecs=p(pose), glob_rotmats=p(glob), rel_rotmats=p(rel), shape_betas=p(betas),
+                num_betas_given=nb, trans=None, kid_factor=p(kid), batch=batch, grad_vertices=p(gv),
+                grad_joints=p(gj), grad_orientations=p(go), grad_pose_rotvecs=p(g_pose),
+                grad_glob_rotmats=p(g_glob), grad_rel_rotmats=p(g_rel), grad_shape_betas=p(g_betas),
+                grad_trans=p(g_trans), grad_kid_factor=p(g_kid), workspace=ws.data_ptr(),
+                workspace_bytes=ws.numel(), hip_stream=stream)
+            _lib.check(_lib.load().smplfit_forward_backward_f32(h.ptr, C.byref(args)))
+        out = list(zeros)
+        if g_pose is not None:
+            out[0] = g_pose.reshape(pose_rotvecs.shape).to(pose_rotvecs.dtype)
+        if shape_betas is not None:
+            gb = torch.zeros(shape_betas.shape, dtype=torch.float32, device=device)
+            if g_betas is not None:
+                gb[:, :nb] = g_betas
+            out[1] = gb.to(shape_betas.dtype)
+        if g_trans is not None:
+            gt = g_trans if trans.shape[0] == batch else g_trans.sum(0, keepdim=True)
+            out[2] = gt.reshape(trans.shape).to(trans.dtype)
+        if g_kid is not None:
+            gk = g_kid.sum() if kid_factor.numel() == 1 and batch != 1 else g_kid
+            out[3] = gk.reshape(kid_factor.shape).to(kid_factor.dtype)
+        if g_rel is not None:
+            out[4] = g_rel.reshape(rel_rotmats.shape).to(rel_rotmats.dtype)
+        if g_glob is not None:
+            out[5] = g_glob.reshape(glob_rotmats.shape).to(glob_rotmats.dtype)
+        return out
 
     def _forward_direct(self, pose_rotvecs=None, shape_betas=None, trans=None, kid_factor=None,
                         rel_rotmats=None, glob_rotmats=None, return_vertices: bool = True):
@@ -229,3 +319,29 @@ class BodyModel(nn.Module):
         res = self.forward(u(pose_rotvecs), u(shape_betas), u(trans), kid_factor, u(rel_rotmats),
                            u(glob_rotmats), return_vertices)
         return {k: v.squeeze(0) for k, v in res.items()}
+
+
+class _ForwardFn(torch.autograd.Function):
+    """``BodyModel.forward`` under autograd: the forward is ``_forward_direct`` (bit for bit the no-grad result), the
+    backward ``_backward_direct`` on the current stream.  Only the inputs are saved."""
+
+    @staticmethod
+    def forward(ctx, model, return_vertices, pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats):
+        ins = (pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)
+        ctx.model = model
+        ctx.set_materialize_grads(False)  # an output the loss does not use: None, no zero-filled cotangent
+        ctx.tensor_mask = [isinstance(a, torch.Tensor) for a in ins]
+        ctx.others = [None if m else a for m, a in zip(ctx.tensor_mask, ins)]
+        ctx.save_for_backward(*[a for a in ins if isinstance(a, torch.Tensor)])
+        r = model._forward_direct(*ins, return_vertices)
+        v = r['vertices'] if return_vertices else r['joints'].new_empty((0,))
+        return r['joints'], r['orientations'], v
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_joints, g_orient, g_verts):
+        saved = iter(ctx.saved_tensors)
+        ins = [next(saved) if m else o for m, o in zip(ctx.tensor_mask, ctx.others)]
+        grads = ctx.model._backward_direct(*ins, g_joints, g_orient, g_verts)
+        grads = [gr if isinstance(a, torch.Tensor) and a.requires_grad else None for gr, a in zip(grads, ins)]
+        return (None, None, *grads)

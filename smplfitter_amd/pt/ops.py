@@ -6,7 +6,8 @@ compilable).  ``BodyFitter.fit`` and ``BodyModel.forward`` route through these o
 compiler is tracing and call the C-ABI directly otherwise.
 
 The operators take a ``model_id`` (an integer naming a live ``BodyModel``, see ``register_model``)
-because operator arguments must be tensors or scalars.  They are not differentiable, as the HIP path.
+because operator arguments must be tensors or scalars.  ``fit`` is not differentiable; ``forward`` is, through
+``smplfitter_amd::forward_backward`` (the HIP vector-Jacobian product, ``BodyModel._backward_direct``).
 """
 
 from __future__ import annotations
@@ -110,3 +111,47 @@ def _(model_id, pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_
     dev = _model_device(model_id)
     new = lambda *s: first.new_empty(s, dtype=torch.float32, device=dev)  # noqa: E731
     return [new(B, J, 3), new(B, J, 3, 3), new(B, V, 3) if return_vertices else new(0)]
+
+
+@custom_op('smplfitter_amd::forward_backward', mutates_args=())
+def forward_backward(
+    model_id: int, pose_rotvecs: Optional[torch.Tensor], shape_betas: Optional[torch.Tensor],
+    trans: Optional[torch.Tensor], kid_factor: Optional[torch.Tensor], rel_rotmats: Optional[torch.Tensor],
+    glob_rotmats: Optional[torch.Tensor], grad_joints: Optional[torch.Tensor],
+    grad_orientations: Optional[torch.Tensor], grad_vertices: Optional[torch.Tensor],
+) -> List[torch.Tensor]:
+    """Gradients of ``forward`` w.r.t. [pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats], each
+    in its input's shape (an empty tensor for an input not given)."""
+    ins = (pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)
+    gs = _model(model_id)._backward_direct(*ins, grad_joints, grad_orientations, grad_vertices)
+    dev = _model_device(model_id)
+    return [g if g is not None else torch.empty((0,), device=dev) for g in gs]
+
+
+@forward_backward.register_fake
+def _(model_id, pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats, grad_joints,
+      grad_orientations, grad_vertices):
+    dev = _model_device(model_id)
+    return [torch.empty_like(a) if a is not None else torch.empty((0,), device=dev)
+            for a in (pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)]
+
+
+def _forward_setup_context(ctx, inputs, output):
+    model_id, pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats, return_vertices = inputs
+    ctx.model_id = model_id
+    ctx.return_vertices = return_vertices
+    ins = (pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)
+    ctx.present = [a is not None for a in ins]
+    ctx.save_for_backward(*[a for a in ins if a is not None])
+
+
+def _forward_backward_formula(ctx, grads):
+    g_joints, g_orient, g_verts = grads
+    saved = iter(ctx.saved_tensors)
+    ins = [next(saved) if p else None for p in ctx.present]
+    gs = torch.ops.smplfitter_amd.forward_backward(
+        ctx.model_id, *ins, g_joints, g_orient, g_verts if ctx.return_vertices else None)
+    return (None, *[g if p else None for g, p in zip(gs, ctx.present)], None)
+
+
+forward.register_autograd(_forward_backward_formula, setup_context=_forward_setup_context)
