@@ -278,8 +278,9 @@ void ensure_max_lds(const void* fn) {
   std::lock_guard<std::mutex> lock(mu);
   for (const auto& e : done)
     if (e.first == dev_id && e.second == fn) return;
-  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  done.emplace_back(dev_id, fn);
+  // (a failed call is not recorded: the next launch of the kernel tries again)
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess)
+    done.emplace_back(dev_id, fn);
 }
 
 // Work units of k_pair_gram_bm (kernels_bm.inc): every joint twice + chunks of kPgPairs joint pairs; a workgroup of
@@ -528,20 +529,16 @@ void launch_template_partsum_bm(const smplfit_handle* h, const Workspace& ws, in
   if (combine) launch_psum_combine(d, sv, ws, B, Mp, st);  // (k_rotations_bm adds the rows itself)
 }
 
-// One-pass target layout of the batch-major path (k_layout_targets, k_mean_finish, k_template_partsum_bm):
-// ws.tT, ws.mean, ws.tjc and the template part sums ws.psum.  ws.resP serves as the slab-sum scratch.
-void launch_layout_bm(const smplfit_handle* h, const float* tv, const float* tj, const Workspace& ws, int B, hipStream_t st,
-                      const float* vw, bool template_sums, bool combine) {
-  const DevModel& d = h->d;
-  if (vw)  // vertex weights: their stream first (the template part sums below read it)
+// Target layout of the batch-major path (k_layout_weights, k_layout_targets): ws.wT, ws.tT and the slab sums in
+// ws.resP (scratch); launch_targets_in finishes them.  -> the slabs
+int launch_layout_bm(const DevModel& d, const float* tv, const float* vw, const Workspace& ws, int B, hipStream_t st) {
+  if (vw)  // vertex weights: their stream first (the template part sums read it)
     hipLaunchKernelGGL(k_layout_weights, dim3((d.V + 63) / 64 + 1, (int)align_up((size_t)B, 128) / 64), dim3(256), 0, st, d, vw,
                        ws.wT, B);
   const int Mp = (int)align_up((size_t)B, 128), nslab = (d.V + kSlabV - 1) / kSlabV;
   hipLaunchKernelGGL(k_layout_targets, dim3(nslab, Mp / 64), dim3(256), (size_t)64 * kSlabRow * 4, st, d, tv, ws.tT,
                      ws.resP, B, Mp);
-  hipLaunchKernelGGL(k_mean_finish, dim3(Mp / 64), dim3(64 * kMeanWaves), 0, st, d, tj, ws.resP, ws, B, Mp, nslab);
-  // (a warm-started fit takes its first part sums against the posed initial model instead)
-  if (template_sums) launch_template_partsum_bm(h, ws, B, st, vw != nullptr, combine);
+  return nslab;
 }
 
 // K3' + K3g + K3c of the batch-major path for 10 betas (S = 10) and 10 betas + the kid unknown (S = 11)
@@ -858,14 +855,39 @@ int launch_lbs_any(const DevModel& d, const Workspace& ws, int B, bool weighted,
 
 size_t chunked_workspace_bytes(const sf::HostTables& t, int batch, const sf::HostTables* tin = nullptr);
 
-int check_common(const smplfit_handle* h, int batch, void* workspace, size_t workspace_bytes) {
-  if (!h) return fail(SMPLFIT_ERR_BAD_ARG, "null handle");
+// Handle, batch and workspace of every entry point.  bwd: smplfit_forward_backward_f32, whose workspace has a size
+// function of its own and whose messages name it.
+int check_common(const smplfit_handle* h, int batch, void* workspace, size_t workspace_bytes, bool bwd = false) {
+  if (!h) return fail(SMPLFIT_ERR_BAD_ARG, bwd ? "smplfit_forward_backward_f32: null handle" : "null handle");
   if (!h->has_device) return fail(SMPLFIT_ERR_HIP, "handle was created host-only (no device)");
   if (batch <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "batch must be positive");
   if (!workspace || ((uintptr_t)workspace & 255))
     return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
-  if (workspace_bytes < chunked_workspace_bytes(h->t, batch))
+  if (bwd && workspace_bytes < smplfit_forward_backward_workspace_bytes(h, batch))
+    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (smplfit_forward_backward_workspace_bytes)");
+  if (!bwd && workspace_bytes < chunked_workspace_bytes(h->t, batch))
     return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (see smplfit_workspace_bytes)");
+  return 0;
+}
+
+// The scale / share options of a shape solve (smplfit_fit_ex_f32, smplfit_shape_solve_ex_f32)
+int check_scale_share(const char* who, int scale_mode, const float* scale_corr, int share_beta,
+                      smplfit_share_allreduce_fn share_allreduce) {
+  if (scale_mode < 0 || scale_mode > 2)
+    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": scale_mode must be 0, 1 (scale_target) or 2 (scale_fit)");
+  if (scale_mode && !scale_corr) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": a scale option needs the scale_corr output");
+  if (share_allreduce && !share_beta) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": share_allreduce without share_beta");
+  return 0;
+}
+
+// The inputs of a forward evaluation (smplfit_forward_ex_f32, smplfit_forward_backward_f32)
+int check_forward_inputs(const char* who, const DevModel& d, const float* pose, const float* glob, const float* rel,
+                         const float* betas, int num_betas_given, const float* kid) {
+  if ((pose != nullptr) + (glob != nullptr) + (rel != nullptr) > 1)
+    return fail(SMPLFIT_ERR_BAD_ARG, "Only one rotation input may be provided");
+  if (betas && num_betas_given > d.S - d.jt.n_kid - d.jt.n_pad)
+    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": more betas than the model holds; slice first");
+  if (kid && !d.jt.n_kid) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": kid_factor given to a handle without kid");
   return 0;
 }
 
@@ -1191,6 +1213,9 @@ void launch_refine_bm(const smplfit_handle* h, RefineArgs ra, const ShareView& s
 //     target joints) with warm = true; not bm: no fused call           of the conversion with k_transfer_bm<true> and
 //                                                                      no k_template_partsum_bm (the first rotation pass
 //                                                                      reads the warm start's LBS rows, kShareLbsAll)
+// The route is applied by the STEPS below (launch_targets_in, launch_posed_pass / launch_lbs_pass,
+// launch_normal_equations, launch_alignment: bm, general, jd_transpose, psum_combine*, pair_in, solve_bm's residual form),
+// by enqueue_solve (solve_bm, pair_in*) and by the stage launches of run_fit (prologue_bm, rot_*, refine_*, gt_to_g).
 // ------------------------------------------------------------------------------------------------
 enum class Entry { kFit, kConvert, kShapeSolve, kForward, kKnownShape, kForwardBackward };
 struct CallShape {
@@ -1264,29 +1289,50 @@ int post_launch_check() {
   return 0;
 }
 
-// Shared driver of fit / part_rotations / shape_solve.
-struct FitOptions {
-  int num_iter;
-  float beta_reg, beta_reg2, kid_reg;
-  int final_adjust;
-  int rotations_only;  // stop after the first rotation pass, write G to `orient`
-  // warm start (bodyfitter.py:363-382): the first rotation pass runs against the model posed with
-  // these values instead of the template, and the ridge pulls towards init_betas / init_kid
-  const float* init_pose = nullptr;   // (B,3J) or null (rest pose)
-  const float* init_betas = nullptr;  // (B,init_nb) or null
-  int init_nb = 0;
-  const float* init_kid = nullptr;    // (B) or null
-  int share_beta = 0;                 // one shape for the whole batch (pt/lstsq.py:24-26)
-  smplfit_share_allreduce_fn share_allreduce = nullptr;  // completes the sum over the ranks of a sharded batch
-  void* share_user = nullptr;
-  int scale_mode = 0;                 // 1 scale_target, 2 scale_fit: the last solve has a scale unknown
-  float scale_reg = 0.f;
-  float* scale_out = nullptr;         // (B) scale_corr
-  // fused conversion (smplfit_convert_f32): the targets are produced on the device — forward of the input model on
-  // the batch-major kernels, topology transfer straight into this fit's target stream — instead of being read
-  // from target_vertices
-  const struct ConvertSource* source = nullptr;
+// ------------------------------------------------------------------------------------------------
+// STEPS.  The launch sequences the entry points are made of.  Each is written once and is the one place that applies
+// the route (Route::bm, DevModel::general) to its sequence; the drivers below only put them in order.
+//   launch_targets_in         targets (+ weights) into the workspace, their mean, first part sums, regressed target joints
+//   launch_posed_pass         the model at the current parameters: forward joint stage, GEMM, joint-row transpose, then
+//   launch_lbs_pass           the LBS pass: part sums against the targets / the mesh alone (also to the caller: mesh out)
+//   launch_normal_equations   GEMM, joint-row transpose, the vertex block of one shape solve
+//   launch_alignment          scale and translation of a known-shape fit
+// and the rules that fill their arguments: solve_weights, set_joint_block, refine_args.
+// ------------------------------------------------------------------------------------------------
+
+// Which weights enter the shape solve and the alignment: both kinds only if both are given (with target joints), the
+// vertex weights alone without target joints (bodyfitter.py:1018-1028, :1640-1661)
+struct SolveWeights {
+  bool v, j;
 };
+SolveWeights solve_weights(bool joints, const float* vw, const float* jw) {
+  return {joints ? (vw && jw) : (vw != nullptr), joints && vw && jw};
+}
+
+// the joint block of the normal equations as the joint stage (or k_prologue_bm) takes it
+void set_joint_block(JointStageArgs* ja, const DevModel& d, bool joints, SolveWeights w) {
+  const bool gjr = gen_joint_rows(d) && joints;  // (the joints are rows of the vertex block: launch_normal_equations)
+  ja->joint_block = (joints && !gjr) ? 1 : 0;
+  ja->joint_block_weighted = w.j ? 1 : 0;
+  ja->vertex_sa_closed_form = (w.v || d.general) ? 0 : 1;  // (the general accumulate sums SA itself)
+}
+
+// the refinement + epilogue of a fit: the joints it aligns and the caller's outputs (betas / kid: null for a known shape)
+RefineArgs refine_args(const float* tj_rot, bool joints, const float* jw, int final_adjust, const Workspace& ws, float* pose,
+                       float* betas, float* trans, float* kid, float* orient, float* rel) {
+  RefineArgs ra{};
+  ra.tj = tj_rot;
+  ra.rj_term = joints ? ws.rjoints : ws.rjreg;
+  ra.jw = jw;
+  ra.final_adjust = final_adjust;
+  ra.pose = pose;
+  ra.betas = betas;
+  ra.trans = trans;
+  ra.kid = kid;
+  ra.orient = orient;
+  ra.rel = rel;
+  return ra;
+}
 
 struct ConvertSource {
   const smplfit_convert_plan* plan;
@@ -1295,8 +1341,196 @@ struct ConvertSource {
   int nb;
   Workspace wsi;  // forward-only workspace slice of the input model (carve(..., fwd_only))
 };
-int launch_convert_source(const ConvertSource& src, const Route& r, const Workspace& ws, int B, hipStream_t st,
-                          bool template_sums);
+int launch_convert_source(const ConvertSource& src, const Workspace& ws, int B, hipStream_t st);
+
+// STEP targets in.  The targets of a call in the form its route reads: centred and sorted by part (ws.tvs, ws.vws; the
+// template part sums come with them), or the batch-major streams (ws.tT, ws.wT) with their mean and — template_sums —
+// the template part sums behind them; regress: the target joints regressed from the centred vertices when none are
+// given (bodyfitter.py:1342-1344).  The joints the rotation stage then reads: rotation_targets().
+struct TargetsIn {
+  const float *tv, *tj;                  // (B,V,3); (B,J,3) or null
+  const float* vw;                       // (B,V) or null
+  const float* vw_stream;                // what the batch-major kernels of the call read of them: vw, or null where they
+                                         // take no part sums and the weights do not enter the solve
+  const ConvertSource* source = nullptr; // fused conversion: the third producer of the batch-major streams, instead of tv
+  bool template_sums = false;            // (a warm-started fit takes its first part sums against the posed initial model)
+  bool regress = false;
+};
+const float* rotation_targets(const Workspace& ws, bool joints) { return joints ? ws.tjc : ws.tjreg; }
+int launch_targets_in(const smplfit_handle* h, const Route& r, const TargetsIn& t, const Workspace& ws, int B, hipStream_t st) {
+  const DevModel& d = h->d;
+  if (t.regress && !t.tj && !h->t.has_regressor)
+    return fail(SMPLFIT_ERR_BAD_ARG, "target_joints omitted but the model has no J_regressor_post_lbs over its vertices");
+  if (!r.bm) {
+    launch_center_sort(d, t.tv, t.tj, t.vw, ws, B, st);
+    if (t.regress && !t.tj) hipLaunchKernelGGL(k_regress_joints, dim3(B), dim3(64), 0, st, d, ws.tvs, ws.tjreg);
+    return 0;
+  }
+  const int Mp = (int)align_up((size_t)B, 128);
+  int nslab;  // ws.resP holds the slab sums of either producer
+  if (t.source) {
+    if (int rc = launch_convert_source(*t.source, ws, B, st)) return rc;
+    nslab = t.source->plan->nslab;
+  } else {
+    nslab = launch_layout_bm(d, t.tv, t.vw_stream, ws, B, st);
+  }
+  hipLaunchKernelGGL(k_mean_finish, dim3(Mp / 64), dim3(64 * kMeanWaves), 0, st, d, t.tj, ws.resP, ws, B, Mp, nslab);
+  if (t.template_sums) launch_template_partsum_bm(h, ws, B, st, t.vw_stream != nullptr, r.psum_combine);
+  if (t.regress && !t.tj)
+    hipLaunchKernelGGL(k_regress_joints_bm<true>, dim3(Mp / 64, d.J), dim3(64), 0, st, d, ws.tT, ws.mean, ws.tjreg, B);
+  return 0;
+}
+
+// STEP LBS pass.  The mesh at the shape, translation and joint rows in the workspace, in one of two forms.
+//   kPartSums  the part sums of the next rotation pass (or of the refinement) against the targets; without target joints
+//              also the reference joints regressed from the posed mesh (ws.rjreg)
+//   kForward   the mesh alone: to the caller's (B, V, 3) — mesh out —, or left in ws.vpT (batch-major only)
+enum class Lbs { kNone, kPartSums, kForward };
+struct LbsPass {
+  Lbs form = Lbs::kNone;
+  // kPartSums
+  bool joints = true;         // target joints given
+  bool weighted = false;      // vertex weights enter the part sums
+  bool keep_mesh = false;     // the posed mesh stays in the workspace: the wave-per-instance pass in its MODE 1 (ws.rverts);
+                              // the batch-major pass writes it (ws.vpT) only where it is read: regressed joints, mesh_all
+  bool mesh_all = false;      // every posed vertex is read behind the pass (the alignment sums of a known-shape fit)
+  bool feeds_refine = false;  // the last pass of a fit: with target joints the refinement reads the adjustable parts
+                              // alone (launch_lbs_bm adj_only); Route::psum_combine_last
+  // kForward
+  const ForwardArgs* shape = nullptr;  // null: at ws.beta / ws.trans; else at the caller's betas / nb / kid / trans, which
+                                       // the batch-major path copies there first (launch_posed_pass)
+  float* out = nullptr;
+};
+LbsPass part_sums(bool joints, bool weighted, bool keep_mesh, bool mesh_all = false, bool feeds_refine = false) {
+  return {Lbs::kPartSums, joints, weighted, keep_mesh, mesh_all, feeds_refine};
+}
+LbsPass mesh_alone(const ForwardArgs* shape, float* out) { return {Lbs::kForward, true, false, false, false, false, shape, out}; }
+int launch_lbs_pass(const smplfit_handle* h, const Route& r, const LbsPass& p, const Workspace& ws, int B, hipStream_t st) {
+  const DevModel& d = h->d;
+  const int Mp = (int)align_up((size_t)B, 128);
+  if (p.form == Lbs::kNone) return 0;
+  if (p.form == Lbs::kForward) {
+    if (r.bm) {  // forward-only pass over every slot, then the inverse of the target layout
+      if (int rc = launch_lbs_fwd_bm(d, share_view(h, sf::kShareLbsAll, B), ws, B, Mp, st)) return rc;
+      if (p.out)
+        hipLaunchKernelGGL(k_unlayout_vertices, dim3((d.V + kSlabV - 1) / kSlabV, Mp / 64), dim3(256), (size_t)64 * kSlabRow * 4, st,
+                           d, ws.vpT, p.out, B);
+      return 0;
+    }
+    if (!p.out) return fail(SMPLFIT_ERR_UNSUPPORTED, "forward LBS pass: the mesh stays in the workspace on the batch-major path only");
+    if (p.shape) return launch_lbs_any<2>(d, ws, B, false, p.shape->nb, p.shape->betas, p.shape->trans, p.out, st, p.shape->kid);
+    return launch_lbs_any<2>(d, ws, B, false, d.S, ws.beta, ws.trans, p.out, st);
+  }
+  if (r.bm) {
+    const bool write_v = p.keep_mesh && (!p.joints || p.mesh_all);
+#define SF_CALL_LBS(S_, KW_)                                                                                          \
+  launch_lbs_bm<S_, KW_>(h, ws, B, st, p.feeds_refine ? r.psum_combine_last : r.psum_combine, write_v, p.feeds_refine && p.joints, \
+                         p.weighted, p.mesh_all, p.joints ? 0 : 1)
+    SF_DISPATCH_SKW(d, SF_CALL_LBS);
+#undef SF_CALL_LBS
+    return 0;
+  }
+  if (int rc = p.keep_mesh ? launch_lbs_any<1>(d, ws, B, p.weighted, d.S, ws.beta, ws.trans, nullptr, st)
+                           : launch_lbs_any<0>(d, ws, B, p.weighted, d.S, ws.beta, ws.trans, nullptr, st))
+    return rc;
+  if (!p.joints) hipLaunchKernelGGL(k_regress_joints, dim3(B), dim3(64), 0, st, d, ws.rverts, ws.rjreg);
+  return 0;
+}
+
+// STEP posed pass.  The model posed at the current parameters: the forward joint stage (fa; null: the joint rows the
+// last joint stage left), v_posed by the GEMM in the route's layout, the joint rows instance-innermost where the
+// batch-major kernels read them and an instance-major kernel wrote them (k_forward_joint; k_joint_stage without
+// k_prologue_bm: Route::jd_transpose), the LBS pass.
+struct PosedPass {
+  const ForwardArgs* fa = nullptr;
+  LbsPass lbs;
+};
+int launch_posed_pass(const smplfit_handle* h, const Route& r, const PosedPass& p, const Workspace& ws, int B, hipStream_t st) {
+  const DevModel& d = h->d;
+  if (p.fa) launch_forward_joint(d, *p.fa, ws, B, st);
+  if (r.bm && p.lbs.shape)  // the shape / translation rows the batch-major LBS kernel reads
+    hipLaunchKernelGGL(k_fill_shape, dim3((B + 255) / 256), dim3(256), 0, st, ws, B, d.S, d.jt.n_kid, p.lbs.shape->betas,
+                       p.lbs.shape->nb, p.lbs.shape->kid, p.lbs.shape->trans);
+  if (int rc = launch_gemm(d, ws, B, st, r.bm)) return rc;
+  if (r.bm && (p.fa || r.jd_transpose)) launch_jd_transpose(d, ws, B, st);
+  return launch_lbs_pass(h, r, p.lbs, ws, B, st);
+}
+
+// STEP normal equations of one shape solve (its vertex block; the joint block comes from the joint stage, see
+// set_joint_block).  Batch-major: one transposed GEMM feeds the residual pass and, after the solve, the LBS / part-sum
+// pass of the same iteration; residual pass + pair-Gram (unit weights; k_solve_bm adds the partial sums itself), or
+// the accumulate kernel (w.v: vertex weights in the solve; scaled: the solve has a scale unknown and needs the extra
+// sums).  Otherwise k_shape_accum / the general accumulate, which takes the target joints as rows (tj, jw).
+int launch_normal_equations(const smplfit_handle* h, const Route& r, bool joints, SolveWeights w, const float* tj, const float* jw,
+                            bool scaled, const Workspace& ws, int B, hipStream_t st) {
+  const DevModel& d = h->d;
+  if (int rc = launch_gemm(d, ws, B, st, r.bm)) return rc;
+  if (!r.bm) {
+    const bool gjr = gen_joint_rows(d) && joints;
+    return launch_accum_any(d, ws, B, w.v, r.pair_in, st, gjr ? tj : nullptr, gjr && w.j ? jw : nullptr, scaled);
+  }
+  // joint rows instance-innermost for the kernels below; AFTER the GEMM: in front of it the chunk's GEMM starts later
+  // and the chunks overlap worse (1.37 vs 1.40 M fits/s).  (Measured and not kept: k_joint_stage writing ws.jdT itself
+  // — 64 waves of one XCD completing every 256-byte row with one float each — instead of this 8 us launch: 2.54 ->
+  // 2.50 M fits/s, SMPL-X 1.31 -> 1.24: the scattered stores cost the latency-bound stage more than the transpose.)
+  if (r.jd_transpose) launch_jd_transpose(d, ws, B, st);
+  if (scaled) launch_accum_w_bm(h, ws, B, st, w.v, true);
+  else if (w.v) launch_accum_w_bm(h, ws, B, st);
+  else launch_residual_bm(h, ws, B, st, r.solve_bm ? 3 : 7);
+  return 0;
+}
+
+// STEP alignment of a known-shape fit (fit_scale_and_translation): k_scale_trans, or on the batch-major streams the
+// alignment sums + their finish, once for the translation (mode 1) and once more for the scale (mode 2).
+template <int MODE>
+void launch_align_partial(const DevModel& d, bool weighted, int nchunk, const Workspace& ws, int B, int Mp, hipStream_t st) {
+  const dim3 grid(Mp / 64, nchunk);
+  if (weighted) hipLaunchKernelGGL((k_align_partial_bm<MODE, true>), grid, dim3(64), 0, st, d, ws, B, Mp, nchunk);
+  else hipLaunchKernelGGL((k_align_partial_bm<MODE, false>), grid, dim3(64), 0, st, d, ws, B, Mp, nchunk);
+}
+void launch_alignment(const smplfit_handle* h, const Route& r, const ScaleTransArgs& sa, const Workspace& ws, int B, hipStream_t st) {
+  const DevModel& d = h->d;
+  if (!r.bm) {
+    hipLaunchKernelGGL(k_scale_trans, dim3(B), dim3(256), 0, st, d, sa, ws);
+    return;
+  }
+  const int Mp = (int)align_up((size_t)B, 128);
+  AlignArgs aa{};
+  aa.tj = sa.tj;
+  aa.jw = sa.jw;
+  aa.with_scale = sa.with_scale;
+  aa.regressed = sa.regressed;
+  aa.scale_out = sa.scale_out;
+  aa.nchunk = B <= sf::kFineMaxBatch ? 256 : 64;
+  for (aa.mode = 1; aa.mode <= (sa.with_scale ? 2 : 1); ++aa.mode) {
+    if (aa.mode == 1) launch_align_partial<1>(d, sa.weighted_v, aa.nchunk, ws, B, Mp, st);
+    else launch_align_partial<2>(d, sa.weighted_v, aa.nchunk, ws, B, Mp, st);
+    hipLaunchKernelGGL(k_align_finish, dim3(B), dim3(64), 0, st, d, aa, ws, B, Mp);
+  }
+}
+
+// The options of the shape solves of one call (enqueue_solve) and of the fit around them.
+struct FitOptions {
+  int num_iter;
+  float beta_reg, beta_reg2, kid_reg;
+  int final_adjust;
+  int rotations_only;  // stop after the first rotation pass, write G to the orientations
+  int share_beta = 0;                 // one shape for the whole batch (pt/lstsq.py:24-26)
+  smplfit_share_allreduce_fn share_allreduce = nullptr;  // completes the sum over the ranks of a sharded batch
+  void* share_user = nullptr;
+  int scale_mode = 0;                 // 1 scale_target, 2 scale_fit: the last solve has a scale unknown
+  float scale_reg = 0.f;
+};
+FitOptions fit_options(const smplfit_fit_args& a, bool rotations_only) {
+  FitOptions o{a.num_iter, a.beta_regularizer, a.beta_regularizer2, a.kid_regularizer, a.final_adjust_rots ? 1 : 0,
+               rotations_only ? 1 : 0};
+  o.share_beta = a.share_beta ? 1 : 0;
+  o.share_allreduce = a.share_allreduce;
+  o.share_user = a.share_user;
+  o.scale_mode = a.scale_mode;
+  o.scale_reg = a.scale_regularizer;
+  return o;
+}
 
 // The solve of one shape pass on the sums already in the workspace: the plain per-instance solve, the
 // scaled solve (one more unknown; extra vertex sums first) or the shared solve (assemble, sum over the
@@ -1325,7 +1559,7 @@ int share_sum(const DevModel& d, const Workspace& ws, int B, const FitOptions& o
 // workspace (the combine was not launched) and k_solve_bm takes them from there; otherwise the record is in ws.gramv.
 // The scaled solve of the bm path finds the extra sums of k_accum_w_bm in ws.vextra.
 int enqueue_solve(const smplfit_handle* h, const Route& r, const Workspace& ws, int B, const FitOptions& o, bool joints,
-                  bool eff_v, bool eff_j, const float* jw, int use_ref, bool scaled, hipStream_t st) {
+                  SolveWeights w, const float* jw, int use_ref, bool scaled, hipStream_t st) {
   const DevModel& d = h->d;
   const int pair_in = scaled ? r.pair_in_scaled : r.pair_in;
   const bool extras_done = r.bm && scaled;
@@ -1337,13 +1571,13 @@ int enqueue_solve(const smplfit_handle* h, const Route& r, const Workspace& ws, 
     // they are entries of the accumulate kernel's rank-k update — its target column — in ws.gvex, joints included)
 #define SF_CALL_EXTRAS(S_, KW_)                                                                       \
   hipLaunchKernelGGL((k_scale_extras<S_, KW_>), dim3(B), dim3(64),                                    \
-                     (size_t)d.J * sf::jd_stride(S_) * 4, st, d, ws, eff_v ? 1 : 0)
+                     (size_t)d.J * sf::jd_stride(S_) * 4, st, d, ws, w.v ? 1 : 0)
     if (!extras_done && !d.general) SF_DISPATCH_SKW(d, SF_CALL_EXTRAS);
 #undef SF_CALL_EXTRAS
     ScaledSolveArgs sa{};
     const bool joint_rows = gen_joint_rows(d) && joints;  // the joints' terms are in the records already
     sa.tj = (joints && !joint_rows) ? ws.tjc : nullptr;
-    sa.jw = eff_j ? jw : nullptr;
+    sa.jw = w.j ? jw : nullptr;
     sa.joint_block = (joints && !joint_rows) ? 1 : 0;
     sa.mode = o.scale_mode;
     sa.pair_form = pair_in;
@@ -1382,10 +1616,12 @@ int enqueue_solve(const smplfit_handle* h, const Route& r, const Workspace& ws, 
   return 0;
 }
 
-int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const float* vw,
-            const float* jw, int B, const FitOptions& o, float* pose, float* betas, float* trans,
-            float* kid, float* orient, float* rel, const Workspace& ws, hipStream_t st, int ph_lo = 0,
-            int ph_hi = 1 << 30) {
+// Shared driver of fit / part_rotations, on one chunk of the batch: `a` holds the chunk's rows (chunk_view), source
+// the chunk's input side of a fused conversion (smplfit_convert_f32: the targets are produced on the device — forward
+// of the input model on the batch-major kernels, topology transfer straight into this fit's target stream — instead
+// of being read from target_vertices).
+int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_only, const ConvertSource* source,
+            const Workspace& ws, hipStream_t st, int ph_lo = 0, int ph_hi = 1 << 30) {
   // PHASES.  The launches of a fit are numbered in phases — 0: the prologue up to the first rotation pass; 1 + 2 it:
   // the vertex block of iteration `it` up to the normal equations; 2 + 2 it: solve, vertices at the solution, next
   // rotation pass; 1 + 2 num_iter: refinement and epilogue — and a call enqueues the phases [ph_lo, ph_hi) only (the
@@ -1393,79 +1629,50 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
   // their streams, instead of one whole chunk after the other (fit_impl).
   const auto on = [&](int ph) { return ph >= ph_lo && ph < ph_hi; };
   const DevModel& d = h->d;
+  const int B = a.batch;
+  const float *tj = a.target_joints, *vw = a.vertex_weights, *jw = a.joint_weights;
   const bool joints = tj != nullptr;
-  if (!joints && !h->t.has_regressor)
-    return fail(SMPLFIT_ERR_BAD_ARG,
-                "target_joints omitted but the model has no J_regressor_post_lbs over its vertices");
   const bool vweighted = vw != nullptr;
-  // weights enter the shape solve only if both are given (with joints) or vertex weights without
-  // joints (bodyfitter.py:1018-1028)
-  const bool eff_v = joints ? (vw && jw) : (vw != nullptr);
-  const bool eff_j = joints && vw && jw;
-  const bool warm = o.init_pose || o.init_betas;
+  const SolveWeights w = solve_weights(joints, vw, jw);
+  const FitOptions o = fit_options(a, rotations_only);
+  // warm start (bodyfitter.py:363-382): the first rotation pass runs against the model posed with the initial values
+  // instead of the template — only when a pose or a shape is given —; the ridge references reach EVERY shape solve
+  // whenever they are given — also an initial_kid_factor on its own (:413-414, :448-449)
+  const bool warm = a.initial_pose_rotvecs || a.initial_shape_betas;
+  const int use_ref = (a.initial_shape_betas || a.initial_kid_factor) ? 1 : 0;
   // vertex weights on the batch-major path: the weight stream, weighted part sums, and — when the weights enter the
   // shape solve — the weighted accumulate.  scale_target / scale_fit: the LAST iteration's solve has one more unknown
   // and needs extra vertex sums — that iteration runs the accumulate kernel (with or without weights) in its EXTRAS form
-  const Route r = route_of(h, B, {o.source ? Entry::kConvert : Entry::kFit, joints, vweighted, eff_v, o.scale_mode,
+  const Route r = route_of(h, B, {source ? Entry::kConvert : Entry::kFit, joints, vweighted, w.v, o.scale_mode,
                                   o.share_beta != 0, o.rotations_only != 0, warm});
-  if (o.source && !r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "fused conversion: the batch-major path does not apply");
-  // (a warm-started fit evaluates its first part sums against the posed initial model: on the batch-major path with
-  // the LBS pass of the iterations — until round 4 with the wave-per-instance kernel over a second, sorted copy)
-  if (on(0) && !r.bm) launch_center_sort(d, tv, tj, vw, ws, B, st);
-  if (!on(0)) {
-  } else if (r.bm && o.source) {
-    if (int rc = launch_convert_source(*o.source, r, ws, B, st, !warm)) return rc;
-  } else if (r.bm) {
-    launch_layout_bm(h, tv, tj, ws, B, st, vw, !warm, r.psum_combine);
+  if (source && !r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "fused conversion: the batch-major path does not apply");
+  if (on(0)) {
+    TargetsIn t{a.target_vertices, tj, vw, vw, source, !warm, true};
+    if (int rc = launch_targets_in(h, r, t, ws, B, st)) return rc;
   }
-  const float* tj_rot = ws.tjc;
-  if (!joints) {  // regressed target joints from the centred vertices (bodyfitter.py:1342-1344)
-    if (!on(0)) {
-    } else if (r.bm)
-      hipLaunchKernelGGL(k_regress_joints_bm<true>, dim3((int)align_up((size_t)B, 128) / 64, d.J), dim3(64), 0, st, d,
-                         ws.tT, ws.mean, ws.tjreg, B);
-    else
-      hipLaunchKernelGGL(k_regress_joints, dim3(B), dim3(64), 0, st, d, ws.tvs, ws.tjreg);
-    tj_rot = ws.tjreg;
-  }
+  const float* tj_rot = rotation_targets(ws, joints);
   JointStageArgs ja{};
   ja.tj = tj_rot;
   ja.jw = jw;
-  const bool gjr = gen_joint_rows(d) && joints;
-  ja.joint_block = (joints && !gjr) ? 1 : 0;
-  ja.joint_block_weighted = eff_j ? 1 : 0;
-  ja.vertex_sa_closed_form = (eff_v || d.general) ? 0 : 1;  // (the general accumulate sums SA itself)
+  set_joint_block(&ja, d, joints, w);
   ja.do_prologue = o.rotations_only ? 0 : 1;
   ja.fit_rotations = 1;
   ja.Gprev = nullptr;
-  // bodyfitter.py:363-382: the first rotation pass runs against the posed model only when a pose or a
-  // shape is given; the ridge references reach EVERY shape solve whenever they are given — also an
-  // initial_kid_factor on its own (:413-414, :448-449)
-  const int use_ref = (o.init_betas || o.init_kid) ? 1 : 0;
   if (on(0) && (warm || use_ref))
-    hipLaunchKernelGGL(k_fill_shape, dim3((B + 255) / 256), dim3(256), 0, st, ws, B, d.S, d.jt.n_kid,
-                       o.init_betas, std::min(o.init_nb, d.S - d.jt.n_kid - d.jt.n_pad), o.init_kid);
+    hipLaunchKernelGGL(k_fill_shape, dim3((B + 255) / 256), dim3(256), 0, st, ws, B, d.S, d.jt.n_kid, a.initial_shape_betas,
+                       std::min(a.initial_shape_betas ? a.num_initial_betas : 0, d.S - d.jt.n_kid - d.jt.n_pad),
+                       a.initial_kid_factor);
   if (warm) {
+    // the first part sums against the posed initial model (the wave-per-instance pass has always kept the mesh here,
+    // with target joints as well)
     ForwardArgs fa{};
-    fa.pose = o.init_pose;
-    fa.betas = ws.beta;  // (B,S) incl. the kid column
+    fa.pose = a.initial_pose_rotvecs;  // null: rest pose
+    fa.betas = ws.beta;                // (B,S) incl. the kid column
     fa.nb = d.S;
     fa.joints = ws.rjoints;
     fa.orient = ws.G;
-    if (on(0) && r.bm) {
-      launch_forward_joint(d, fa, ws, B, st);
-      if (int rc = launch_gemm(d, ws, B, st, true)) return rc;
-      launch_jd_transpose(d, ws, B, st);
-#define SF_CALL_LBS(S_, KW_) launch_lbs_bm<S_, KW_>(h, ws, B, st, r.psum_combine, !joints, false, vweighted)
-      SF_DISPATCH_SKW(d, SF_CALL_LBS);
-#undef SF_CALL_LBS
-    } else if (on(0)) {
-      launch_forward_joint(d, fa, ws, B, st);
-      launch_gemm(d, ws, B, st);
-      if (int rc = launch_lbs_any<1>(d, ws, B, vweighted, d.S, ws.beta, ws.trans, nullptr, st)) return rc;
-      if (!joints)
-        hipLaunchKernelGGL(k_regress_joints, dim3(B), dim3(64), 0, st, d, ws.rverts, ws.rjreg);
-    }
+    if (on(0))
+      if (int rc = launch_posed_pass(h, r, {&fa, part_sums(joints, vweighted, true)}, ws, B, st)) return rc;
     ja.rj = joints ? ws.rjoints : ws.rjreg;
     ja.rj_shared = 0;
     ja.Gprev = ws.G;  // compose with the initial orientations
@@ -1482,51 +1689,21 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
   if (on(0))
     launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_first, ja.Gprev ? 2 : 0);
   if (o.rotations_only) {
-    if (on(0)) hipLaunchKernelGGL(k_copy, dim3(256), dim3(256), 0, st, ws.G, orient, (size_t)B * d.J * 9);
+    if (on(0)) hipLaunchKernelGGL(k_copy, dim3(256), dim3(256), 0, st, ws.G, a.orientations, (size_t)B * d.J * 9);
     return post_launch_check();
   }
   for (int it = 0; it < o.num_iter; ++it) {
-    const bool pa = on(1 + 2 * it), pb = on(2 + 2 * it);
-    if (!pa) {
-    } else if (r.bm) {
-      // batch-major vertex block: one transposed GEMM feeds the residual pass and, after the solve,
-      // the LBS / part-sum pass of this iteration
-      const int Mp = (int)align_up((size_t)B, 128);
-      launch_gemm(d, ws, B, st, true);
-      // joint rows instance-innermost for the three kernels below; AFTER the GEMM: in front of it the
-      // chunk's GEMM starts later and the chunks overlap worse (1.37 vs 1.40 M fits/s).  (Round 4, measured and
-      // not kept: k_joint_stage writing ws.jdT itself — 64 waves of one XCD completing every 256-byte row with
-      // one float each — instead of this 8 us launch: 2.54 -> 2.50 M fits/s, SMPL-X 1.31 -> 1.24: the scattered
-      // stores cost the latency-bound stage more than the transpose.)
-      if (r.jd_transpose) launch_jd_transpose(d, ws, B, st);
-      if (o.scale_mode && it + 1 == o.num_iter) launch_accum_w_bm(h, ws, B, st, eff_v, true);
-      else if (eff_v) launch_accum_w_bm(h, ws, B, st);
-      else launch_residual_bm(h, ws, B, st, r.solve_bm ? 3 : 7);  // (k_solve_bm adds the partial sums itself)
-    } else {
-      launch_gemm(d, ws, B, st);
-      if (int rc = launch_accum_any(d, ws, B, eff_v, r.pair_in, st, gjr ? tj_rot : nullptr, gjr && eff_j ? jw : nullptr,
-                                    o.scale_mode && it + 1 == o.num_iter))
-        return rc;
-    }
+    const bool pb = on(2 + 2 * it), last = it + 1 == o.num_iter;
+    const bool scaled_now = o.scale_mode && last;  // only the last solve (:434-455)
+    if (on(1 + 2 * it))
+      if (int rc = launch_normal_equations(h, r, joints, w, tj_rot, jw, scaled_now, ws, B, st)) return rc;
     // K4 stays its own launch: fused into the prologue of the LBS kernel (template flag SOLVE) its
     // ~40 serial barriers stall all four waves of the workgroup and the kernel ran 230 us longer
-    const bool scaled_now = o.scale_mode && it + 1 == o.num_iter;  // only the last solve (:434-455)
     if (pb)
-      if (int rc = enqueue_solve(h, r, ws, B, o, joints, eff_v, eff_j, jw, use_ref, scaled_now, st)) return rc;
-    const bool last = it + 1 == o.num_iter;
+      if (int rc = enqueue_solve(h, r, ws, B, o, joints, w, jw, use_ref, scaled_now, st)) return rc;
     if (last && !o.final_adjust) break;  // nothing consumes the re-evaluated mesh
-    if (!pb) {
-    } else if (r.bm) {
-#define SF_CALL_LBS(S_, KW_) \
-  launch_lbs_bm<S_, KW_>(h, ws, B, st, last ? r.psum_combine_last : r.psum_combine, !joints, last && joints, vweighted)
-      SF_DISPATCH_SKW(d, SF_CALL_LBS);
-#undef SF_CALL_LBS
-    } else if (joints) {
-      if (int rc = launch_lbs_any<0>(d, ws, B, vweighted, d.S, ws.beta, ws.trans, nullptr, st)) return rc;
-    } else {
-      if (int rc = launch_lbs_any<1>(d, ws, B, vweighted, d.S, ws.beta, ws.trans, nullptr, st)) return rc;
-      hipLaunchKernelGGL(k_regress_joints, dim3(B), dim3(64), 0, st, d, ws.rverts, ws.rjreg);
-    }
+    if (pb)
+      if (int rc = launch_lbs_pass(h, r, part_sums(joints, vweighted, !joints, false, last), ws, B, st)) return rc;
     if (last) break;
     ja.rj = joints ? ws.rjoints : ws.rjreg;
     ja.rj_shared = 0;
@@ -1534,24 +1711,15 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
     if (pb) launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_next, 1);
   }
   if (!on(1 + 2 * o.num_iter)) return post_launch_check();
-  RefineArgs ra{};
-  ra.tj = tj_rot;
-  ra.rj_term = joints ? ws.rjoints : ws.rjreg;
-  ra.jw = jw;
-  ra.final_adjust = o.final_adjust;
-  ra.pose = pose;
-  ra.betas = betas;
-  ra.trans = trans;
-  ra.kid = kid;
-  ra.orient = orient;
-  ra.rel = rel;
+  RefineArgs ra = refine_args(tj_rot, joints, jw, o.final_adjust, ws, a.pose_rotvecs, a.shape_betas, a.trans, a.kid_factor,
+                              a.orientations, a.relative_orientations);
   if (o.scale_mode) {
     hipLaunchKernelGGL(k_scale_refs, dim3(B), dim3(64), 0, st, d, ws, tj_rot, o.scale_mode,
                        o.final_adjust ? 1 : 0, joints ? 0 : 1);
     if (o.scale_mode == 1 && o.final_adjust) ra.tj = ws.tjs;  // target joints times the scale
     ra.scaled = o.scale_mode == 2 ? 1 : 0;                      // rest joints times the scale (:1449-1450)
-    if (o.scale_out)
-      hipLaunchKernelGGL(k_copy, dim3(16), dim3(256), 0, st, ws.scale, o.scale_out, (size_t)B);
+    if (a.scale_corr)
+      hipLaunchKernelGGL(k_copy, dim3(16), dim3(256), 0, st, ws.scale, a.scale_corr, (size_t)B);
   }
   if (r.refine_bm) {
     launch_refine_bm(h, ra, share_view(h, r.refine_kind, B), ws, B, st);
@@ -1564,9 +1732,9 @@ int run_fit(const smplfit_handle* h, const float* tv, const float* tj, const flo
 }
 
 // fit_with_known_shape (bodyfitter.py:655-838): pose and translation (optionally a scale) for given
-// shape parameters.  Alternates the LBS forward at the current rotations (forward joint stage, GEMM,
-// K5 with the part sums against the target) with the part-rotation stage; then the alignment stage
-// and the dependent refinement.  num_iter rotation passes, num_iter + 1 forward passes.
+// shape parameters.  Alternates the posed pass at the current rotations (forward joint stage, GEMM, the
+// part sums against the target) with the part-rotation stage; then the alignment stage
+// and the dependent refinement.  num_iter rotation passes, num_iter + 1 posed passes.
 struct KnownShapeOptions {
   int num_iter, final_adjust, scale_fit;
 };
@@ -1577,28 +1745,10 @@ int run_fit_known_shape(const smplfit_handle* h, const float* betas, int nb, con
                         float* scale_out, float* orient, float* rel, const Workspace& ws, hipStream_t st) {
   const DevModel& d = h->d;
   const bool joints = tj != nullptr;
-  if (!joints && !h->t.has_regressor)
-    return fail(SMPLFIT_ERR_BAD_ARG,
-                "target_joints omitted but the model has no J_regressor_post_lbs over its vertices");
   const bool vweighted = vw != nullptr;
-  // the batch-major vertex kernels (round 4): target (+ weight) streams, transposed GEMM, part sums with lane =
-  // instance (the LAST pass leaves the posed vertices in ws.vpT), alignment sums over the streams
   const Route r = route_of(h, B, {Entry::kKnownShape, joints, vweighted});
-  const int Mp = (int)align_up((size_t)B, 128);
-  const float* tj_rot = ws.tjc;
-  if (r.bm) {
-    launch_layout_bm(h, tv, tj, ws, B, st, vw, false, r.psum_combine);
-    if (!joints) {
-      hipLaunchKernelGGL(k_regress_joints_bm<true>, dim3(Mp / 64, d.J), dim3(64), 0, st, d, ws.tT, ws.mean, ws.tjreg, B);
-      tj_rot = ws.tjreg;
-    }
-  } else {
-    launch_center_sort(d, tv, tj, vw, ws, B, st);
-    if (!joints) {
-      hipLaunchKernelGGL(k_regress_joints, dim3(B), dim3(64), 0, st, d, ws.tvs, ws.tjreg);
-      tj_rot = ws.tjreg;
-    }
-  }
+  if (int rc = launch_targets_in(h, r, {tv, tj, vw, vw, nullptr, false, true}, ws, B, st)) return rc;
+  const float* tj_rot = rotation_targets(ws, joints);
   hipLaunchKernelGGL(k_fill_shape, dim3((B + 255) / 256), dim3(256), 0, st, ws, B, d.S, d.jt.n_kid, betas,
                      std::min(nb, d.S - d.jt.n_kid - d.jt.n_pad), kid);
   ForwardArgs fa{};
@@ -1614,85 +1764,37 @@ int run_fit_known_shape(const smplfit_handle* h, const float* betas, int nb, con
   ja.do_prologue = 0;
   ja.rj_shared = 0;
   ja.Gprev = ws.G;
+  // the posed mesh is kept where it is read: regressed joints, and the alignment sums behind the last pass
   for (int it = 0; it <= o.num_iter; ++it) {
-    launch_forward_joint(d, fa, ws, B, st);
-    if (r.bm) {
-      if (int rc = launch_gemm(d, ws, B, st, true)) return rc;
-      if (r.jd_transpose) launch_jd_transpose(d, ws, B, st);
-      // the posed mesh is kept (in place, ws.vpT) where it is read: regressed joints, and the alignment sums behind the
-      // last pass
-#define SF_CALL_LBS(S_, KW_) \
-  launch_lbs_bm<S_, KW_>(h, ws, B, st, r.psum_combine, !joints || it == o.num_iter, false, vweighted, it == o.num_iter, joints ? 0 : 1)
-      SF_DISPATCH_SKW(d, SF_CALL_LBS);
-#undef SF_CALL_LBS
-    } else {
-      launch_gemm(d, ws, B, st);
-      // MODE 1: the posed mesh is kept (regressed joints, alignment sums) next to the part sums
-      if (int rc = launch_lbs_any<1>(d, ws, B, vweighted, d.S, ws.beta, ws.trans, nullptr, st)) return rc;
-      if (!joints)
-        hipLaunchKernelGGL(k_regress_joints, dim3(B), dim3(64), 0, st, d, ws.rverts, ws.rjreg);
-    }
+    if (int rc = launch_posed_pass(h, r, {&fa, part_sums(joints, vweighted, true, it == o.num_iter)}, ws, B, st)) return rc;
     if (it == o.num_iter) break;
     ja.rj = joints ? ws.rjoints : ws.rjreg;
     launch_joint_stage(d, ja, ws, B, st);
     fa.pose = nullptr;
     fa.glob = ws.G;
   }
+  const SolveWeights w = solve_weights(joints, vw, jw);
   ScaleTransArgs sa{};
   sa.tj = joints ? ws.tjc : nullptr;
-  // weights enter only if both are given (with joints) / vertex weights alone without joints (:1640-1661)
-  sa.weighted_v = joints ? (vw && jw) : (vw != nullptr);
-  sa.jw = (joints && vw && jw) ? jw : nullptr;
+  sa.weighted_v = w.v;
+  sa.jw = w.j ? jw : nullptr;
   sa.with_scale = o.scale_fit;
   sa.regressed = joints ? 0 : 1;
   sa.scale_out = o.scale_fit ? scale_out : nullptr;
-  if (r.bm) {
-    AlignArgs aa{};
-    aa.tj = sa.tj;
-    aa.jw = sa.jw;
-    aa.with_scale = o.scale_fit;
-    aa.regressed = sa.regressed;
-    aa.scale_out = sa.scale_out;
-    aa.nchunk = B <= sf::kFineMaxBatch ? 256 : 64;
-    const dim3 grid(Mp / 64, aa.nchunk);
-    if (sa.weighted_v) hipLaunchKernelGGL((k_align_partial_bm<1, true>), grid, dim3(64), 0, st, d, ws, B, Mp, aa.nchunk);
-    else hipLaunchKernelGGL((k_align_partial_bm<1, false>), grid, dim3(64), 0, st, d, ws, B, Mp, aa.nchunk);
-    aa.mode = 1;
-    hipLaunchKernelGGL(k_align_finish, dim3(B), dim3(64), 0, st, d, aa, ws, B, Mp);
-    if (o.scale_fit) {
-      if (sa.weighted_v) hipLaunchKernelGGL((k_align_partial_bm<2, true>), grid, dim3(64), 0, st, d, ws, B, Mp, aa.nchunk);
-      else hipLaunchKernelGGL((k_align_partial_bm<2, false>), grid, dim3(64), 0, st, d, ws, B, Mp, aa.nchunk);
-      aa.mode = 2;
-      hipLaunchKernelGGL(k_align_finish, dim3(B), dim3(64), 0, st, d, aa, ws, B, Mp);
-    }
-  } else {
-    hipLaunchKernelGGL(k_scale_trans, dim3(B), dim3(256), 0, st, d, sa, ws);
-  }
-  RefineArgs ra{};
-  ra.tj = tj_rot;
-  ra.rj_term = joints ? ws.rjoints : ws.rjreg;
-  ra.jw = jw;
-  ra.final_adjust = o.final_adjust;
-  ra.pose = pose;
-  ra.betas = nullptr;
-  ra.trans = trans;
-  ra.kid = nullptr;
-  ra.orient = orient;
-  ra.rel = rel;
+  launch_alignment(h, r, sa, ws, B, st);
+  RefineArgs ra = refine_args(tj_rot, joints, jw, o.final_adjust, ws, pose, nullptr, trans, nullptr, orient, rel);
   ra.scaled = o.scale_fit;
   launch_refine(d, ra, ws, B, st);
   return post_launch_check();
 }
 
 // The target stream of a fused conversion (smplfit_convert_f32), per chunk:
-//   forward of the INPUT model on the batch-major kernels (k_forward_joint, transposed GEMM, joint-row transpose,
-//   forward-only LBS pass: the posed vertices stay in the input model's instance-innermost buffer),
-//   k_transfer_bm into the OUTPUT model's target stream + slab sums, then the tail of launch_layout_bm.
-// r: the route of the fit the targets feed; template_sums: as launch_layout_bm's (a warm-started fit — the flip —
-// takes its first part sums against the posed initial model instead).  src.kid: the flip's input mesh is evaluated
-// with the kid factor (the input handle is then the kid handle); the conversion passes none.
-int launch_convert_source(const ConvertSource& src, const Route& r, const Workspace& ws, int B, hipStream_t st,
-                          bool template_sums) {
+//   the posed pass of the INPUT model on the batch-major kernels, forward only (the posed vertices stay in the input
+//   model's instance-innermost buffer), then k_transfer_bm into the OUTPUT model's target stream + slab sums;
+//   launch_targets_in finishes them as it does the layout pass's.
+// src.kid: the flip's input mesh is evaluated with the kid factor (the input handle is then the kid handle); the
+// conversion passes none.
+int launch_convert_source(const ConvertSource& src, const Workspace& ws, int B, hipStream_t st) {
   const smplfit_convert_plan& pl = *src.plan;
   const DevModel& d = pl.out->d;
   const DevModel& di = pl.in->d;
@@ -1705,18 +1807,14 @@ int launch_convert_source(const ConvertSource& src, const Route& r, const Worksp
   fa.betas = wi.beta;  // (B,S) rows, zero beyond the given betas
   fa.nb = di.S;
   fa.joints = wi.rjoints;
-  launch_forward_joint(di, fa, wi, B, st);
-  if (int rc = launch_gemm(di, wi, B, st, true)) return rc;
-  launch_jd_transpose(di, wi, B, st);
-  if (int rc_f = launch_lbs_fwd_bm(di, share_view(pl.in, sf::kShareLbsAll, B), wi, B, Mp, st)) return rc_f;
+  Route ri;  // (the entry points have checked that the batch-major path serves the input model)
+  ri.bm = true;
+  if (int rc = launch_posed_pass(pl.in, ri, {&fa, mesh_alone(nullptr, nullptr)}, wi, B, st)) return rc;
   TransferTabs tt{pl.d_oslot, pl.d_start, pl.d_islot, pl.d_w, d.V};
   if (pl.negate_x)
     hipLaunchKernelGGL(k_transfer_bm<true>, dim3(pl.nslab, Mp / 64), dim3(256), 0, st, tt, wi.vpT, di.Vp, ws.tT, d.Vp, ws.resP, Mp);
   else
     hipLaunchKernelGGL(k_transfer_bm<false>, dim3(pl.nslab, Mp / 64), dim3(256), 0, st, tt, wi.vpT, di.Vp, ws.tT, d.Vp, ws.resP, Mp);
-  hipLaunchKernelGGL(k_mean_finish, dim3(Mp / 64), dim3(64 * kMeanWaves), 0, st, d, (const float*)nullptr, ws.resP, ws, B, Mp,
-                     pl.nslab);
-  if (template_sums) launch_template_partsum_bm(pl.out, ws, B, st, false, r.psum_combine);
   return 0;
 }
 
@@ -1778,52 +1876,51 @@ struct ConvertJob {
   int nb;
   const float* kid;  // (B) or null
 };
-int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const ConvertJob* job);
+
+// The rows [b0, b0 + nb) of a fit call as a call of their own: every per-instance array offset, batch = nb.
+smplfit_fit_args chunk_view(const smplfit_fit_args& a, const sf::HostTables& t, int b0, int nb) {
+  smplfit_fit_args v = a;
+  const auto rows = [b0](auto*& p, size_t width) {
+    if (p) p += (size_t)b0 * width;
+  };
+  const size_t J = t.J, V = t.V;
+  rows(v.target_vertices, V * 3);
+  rows(v.target_joints, J * 3);
+  rows(v.vertex_weights, V);
+  rows(v.joint_weights, J);
+  rows(v.initial_pose_rotvecs, J * 3);
+  rows(v.initial_shape_betas, (size_t)a.num_initial_betas);
+  rows(v.initial_kid_factor, 1);
+  rows(v.pose_rotvecs, J * 3);
+  rows(v.shape_betas, (size_t)t.num_betas());
+  rows(v.trans, 3);
+  rows(v.kid_factor, 1);
+  rows(v.orientations, J * 9);
+  rows(v.relative_orientations, J * 9);
+  rows(v.scale_corr, 1);
+  v.batch = nb;
+  return v;
+}
 
 int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const ConvertJob* job) {
-  const float *target_vertices = args->target_vertices, *target_joints = args->target_joints,
-              *vertex_weights = args->vertex_weights, *joint_weights = args->joint_weights,
-              *initial_pose_rotvecs = args->initial_pose_rotvecs,
-              *initial_shape_betas = args->initial_shape_betas, *initial_kid_factor = args->initial_kid_factor;
-  const int batch = args->batch, num_iter = args->num_iter, final_adjust_rots = args->final_adjust_rots,
-            num_initial_betas = args->num_initial_betas;
-  const float beta_regularizer = args->beta_regularizer, beta_regularizer2 = args->beta_regularizer2,
-              kid_regularizer = args->kid_regularizer;
-  float *pose_rotvecs = args->pose_rotvecs, *shape_betas = args->shape_betas, *trans = args->trans,
-        *kid_factor = args->kid_factor, *orientations = args->orientations,
-        *relative_orientations = args->relative_orientations;
-  void *workspace = args->workspace, *hip_stream = args->hip_stream;
-  const size_t workspace_bytes = args->workspace_bytes;
-  int rc = check_common(h, batch, workspace, job ? (size_t)-1 : workspace_bytes);
+  const smplfit_fit_args& a = *args;
+  const int batch = a.batch;
+  int rc = check_common(h, batch, a.workspace, job ? (size_t)-1 : a.workspace_bytes);
   if (rc) return rc;
-  if (job && workspace_bytes < chunked_workspace_bytes(h->t, batch, &job->plan->in->t))
+  if (job && a.workspace_bytes < chunked_workspace_bytes(h->t, batch, &job->plan->in->t))
     return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (see smplfit_convert_workspace_bytes)");
-  if ((!target_vertices && !job) || !pose_rotvecs || !shape_betas || !trans)
+  if ((!a.target_vertices && !job) || !a.pose_rotvecs || !a.shape_betas || !a.trans)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_f32: null input/output pointer");
-  if (num_iter < 1) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_f32: num_iter must be >= 1");
-  if (initial_kid_factor && !h->t.n_kid)
+  if (a.num_iter < 1) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_f32: num_iter must be >= 1");
+  if (a.initial_kid_factor && !h->t.n_kid)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_warm_f32: initial_kid_factor given to a handle without kid");
-  if (initial_shape_betas && (num_initial_betas < 0 || num_initial_betas > h->t.num_betas()))
+  if (a.initial_shape_betas && (a.num_initial_betas < 0 || a.num_initial_betas > h->t.num_betas()))
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_warm_f32: num_initial_betas must lie in [0, the model's betas]; slice first");
-  const int inb = initial_shape_betas ? num_initial_betas : 0;
-  FitOptions o{num_iter, beta_regularizer, beta_regularizer2, kid_regularizer,
-               final_adjust_rots ? 1 : 0, 0};
-  o.share_beta = args->share_beta ? 1 : 0;
-  if (args->scale_mode < 0 || args->scale_mode > 2)
-    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_ex_f32: scale_mode must be 0, 1 (scale_target) or 2 (scale_fit)");
-  if (args->scale_mode && !args->scale_corr)
-    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_ex_f32: a scale option needs the scale_corr output");
-  if (args->share_allreduce && !o.share_beta)
-    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_ex_f32: share_allreduce without share_beta");
-  o.share_allreduce = args->share_allreduce;
-  o.share_user = args->share_user;
-  o.scale_mode = args->scale_mode;
-  o.scale_reg = args->scale_regularizer;
-  hipStream_t st = (hipStream_t)hip_stream;
+  if ((rc = check_scale_share("smplfit_fit_ex_f32", a.scale_mode, a.scale_corr, a.share_beta, a.share_allreduce))) return rc;
+  hipStream_t st = (hipStream_t)a.hip_stream;
   int sizes[kMaxChunks];
   // share_beta couples all instances in every shape solve: one chunk
-  const int nchunk = (h->have_streams && !o.share_beta) ? chunk_plan(h->t, batch, sizes) : 1;
-  const int J = h->t.J, V = h->t.V, Sb = h->t.num_betas();
+  const int nchunk = (h->have_streams && !a.share_beta) ? chunk_plan(h->t, batch, sizes) : 1;
   const int Jin = job ? job->plan->in->t.J : 0;
   auto chunk_bytes = [&](int nb) {
     return carve(h->t, nb, nullptr, nullptr) + (job ? carve(job->plan->in->t, nb, nullptr, nullptr, true) : 0);
@@ -1831,7 +1928,6 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
   auto run_chunk = [&](int b0, int nb, char* wsbase, hipStream_t cs, int ph_lo, int ph_hi) -> int {
     Workspace ws;
     const size_t own = carve(h->t, nb, wsbase, &ws);
-    FitOptions oc = o;
     ConvertSource src{};
     if (job) {
       src.plan = job->plan;
@@ -1841,23 +1937,10 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
       src.nb = job->nb;
       src.kid = job->kid ? job->kid + b0 : nullptr;
       carve(job->plan->in->t, nb, wsbase + own, &src.wsi, true);
-      oc.source = &src;
     }
-    oc.init_pose = initial_pose_rotvecs ? initial_pose_rotvecs + (size_t)b0 * J * 3 : nullptr;
-    oc.init_betas = initial_shape_betas ? initial_shape_betas + (size_t)b0 * inb : nullptr;
-    oc.init_nb = inb;
-    oc.init_kid = initial_kid_factor ? initial_kid_factor + b0 : nullptr;
-    oc.scale_out = args->scale_corr ? args->scale_corr + b0 : nullptr;
-    return run_fit(h, target_vertices ? target_vertices + (size_t)b0 * V * 3 : nullptr,
-                   target_joints ? target_joints + (size_t)b0 * J * 3 : nullptr,
-                   vertex_weights ? vertex_weights + (size_t)b0 * V : nullptr,
-                   joint_weights ? joint_weights + (size_t)b0 * J : nullptr, nb, oc,
-                   pose_rotvecs + (size_t)b0 * J * 3, shape_betas + (size_t)b0 * Sb,
-                   trans + (size_t)b0 * 3, kid_factor ? kid_factor + b0 : nullptr,
-                   orientations ? orientations + (size_t)b0 * J * 9 : nullptr,
-                   relative_orientations ? relative_orientations + (size_t)b0 * J * 9 : nullptr, ws, cs, ph_lo, ph_hi);
+    return run_fit(h, chunk_view(a, h->t, b0, nb), false, job ? &src : nullptr, ws, cs, ph_lo, ph_hi);
   };
-  if (nchunk <= 1) return run_chunk(0, batch, (char*)workspace, st, 0, 1 << 30);
+  if (nchunk <= 1) return run_chunk(0, batch, (char*)a.workspace, st, 0, 1 << 30);
   // fork: every chunk is an independent fit with its own workspace slice; chunk 0 stays on the
   // caller's stream, the others go to the handle's side streams and are joined back by events
   // (stream-ordered with respect to the caller, hipGraph-capturable).  The handle's streams and
@@ -1873,11 +1956,11 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
   // cross-queue event wait costs ~25 us of idle queue, twelve of them per fit.)
   std::lock_guard<std::mutex> lock(h->mu);
   SF_HIP_TRY(hipEventRecord(h->ev_fork, st));
-  const int nphase = 2 + 2 * num_iter;
+  const int nphase = 2 + 2 * a.num_iter;
   int b0s[kMaxChunks], first_error = 0;
   char* wsps[kMaxChunks];
   {
-    char* wsp = (char*)workspace;
+    char* wsp = (char*)a.workspace;
     int b0 = 0;
     for (int c = 0; c < nchunk; ++c) {
       b0s[c] = b0;
@@ -1917,6 +2000,26 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
     }
   if (first_error) return fail(first_error, first_msg);
   return SMPLFIT_OK;
+}
+
+// the fit behind a fused conversion / flip: its options and outputs (A: smplfit_convert_args, smplfit_flip_args)
+template <class A>
+smplfit_fit_args fused_fit_args(const A& a) {
+  smplfit_fit_args f{};
+  f.batch = a.batch;
+  f.num_iter = a.num_iter;
+  f.beta_regularizer = a.beta_regularizer;
+  f.beta_regularizer2 = a.beta_regularizer2;
+  f.kid_regularizer = a.kid_regularizer;
+  f.final_adjust_rots = a.final_adjust_rots;
+  f.pose_rotvecs = a.out_pose_rotvecs;
+  f.shape_betas = a.out_shape_betas;
+  f.trans = a.out_trans;
+  f.kid_factor = a.out_kid_factor;
+  f.orientations = a.out_orientations;
+  f.relative_orientations = a.out_relative_orientations;
+  f.hip_stream = a.hip_stream;
+  return f;
 }
 
 // smplfit_transfer_f32: the staged form where the input rows fit the LDS
@@ -2416,9 +2519,12 @@ int smplfit_part_rotations_f32(const smplfit_handle* h, const float* target_vert
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_part_rotations_f32: null pointer");
   Workspace ws;
   carve(h->t, batch, (char*)workspace, &ws);
-  FitOptions o{1, 0.f, 0.f, 0.f, 0, 1};
-  return run_fit(h, target_vertices, target_joints, vertex_weights, joint_weights, batch, o, nullptr,
-                 nullptr, nullptr, nullptr, glob_rotmats, nullptr, ws, (hipStream_t)hip_stream);
+  smplfit_fit_args a{};  // one rotation pass; the rotations go to the orientations
+  a.target_vertices = target_vertices; a.target_joints = target_joints;
+  a.vertex_weights = vertex_weights; a.joint_weights = joint_weights;
+  a.batch = batch; a.num_iter = 1;
+  a.orientations = glob_rotmats;
+  return run_fit(h, a, true, nullptr, ws, (hipStream_t)hip_stream);
 }
 
 int smplfit_forward_f32(const smplfit_handle* h, const float* pose_rotvecs,
@@ -2441,10 +2547,11 @@ int smplfit_forward_ex_f32(const smplfit_handle* h, const smplfit_forward_args* 
   float *vertices = args->vertices, *joints = args->joints;
   int rc = check_common(h, batch, args->workspace, args->workspace_bytes);
   if (rc) return rc;
-  if ((args->pose_rotvecs != nullptr) + (args->glob_rotmats != nullptr) + (args->rel_rotmats != nullptr) > 1)
-    return fail(SMPLFIT_ERR_BAD_ARG, "Only one rotation input may be provided");
-  if (!joints) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_f32: joints output is required");
   const DevModel& d = h->d;
+  if ((rc = check_forward_inputs("smplfit_forward_f32", d, args->pose_rotvecs, args->glob_rotmats, args->rel_rotmats, shape_betas,
+                                 num_betas_given, kid_factor)))
+    return rc;
+  if (!joints) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_f32: joints output is required");
   hipStream_t st = (hipStream_t)args->hip_stream;
   Workspace ws;
   carve(h->t, batch, (char*)args->workspace, &ws);
@@ -2454,32 +2561,13 @@ int smplfit_forward_ex_f32(const smplfit_handle* h, const smplfit_forward_args* 
   fa.rel = args->rel_rotmats;
   fa.betas = shape_betas;
   fa.nb = shape_betas ? std::min(num_betas_given, d.S - d.jt.n_kid - d.jt.n_pad) : 0;
-  if (kid_factor && !d.jt.n_kid)
-    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_f32: kid_factor given to a handle without kid");
   fa.kid = kid_factor;
-  if (shape_betas && num_betas_given > d.S - d.jt.n_kid - d.jt.n_pad)
-    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_f32: more betas than the model holds; slice first");
   fa.trans = trans;
   fa.joints = joints;
   fa.orient = args->orientations;
   launch_forward_joint(d, fa, ws, batch, st);
-  if (vertices && route_of(h, batch, {Entry::kForward}).bm) {
-    // the batch-major kernels (round 4; what the input side of a fused conversion runs): shape / translation rows, the
-    // transposed GEMM, the forward-only LBS pass over every slot (posed vertices in place in ws.vpT), and the inverse
-    // of the target layout into the caller's (B, V, 3)
-    const int Mp = (int)align_up((size_t)batch, 128);
-    hipLaunchKernelGGL(k_fill_shape, dim3((batch + 255) / 256), dim3(256), 0, st, ws, batch, d.S, d.jt.n_kid, shape_betas, fa.nb,
-                       kid_factor, trans);
-    if (int rc2 = launch_gemm(d, ws, batch, st, true)) return rc2;
-    launch_jd_transpose(d, ws, batch, st);
-    const ShareView sv = share_view(h, sf::kShareLbsAll, batch);
-    if (int rc_f = launch_lbs_fwd_bm(d, sv, ws, batch, Mp, st)) return rc_f;
-    hipLaunchKernelGGL(k_unlayout_vertices, dim3((d.V + kSlabV - 1) / kSlabV, Mp / 64), dim3(256), (size_t)64 * kSlabRow * 4, st, d,
-                       ws.vpT, vertices, batch);
-  } else if (vertices) {
-    launch_gemm(d, ws, batch, st);
-    if (int rc = launch_lbs_any<2>(d, ws, batch, false, fa.nb, shape_betas, trans, vertices, st, kid_factor)) return rc;
-  }
+  if (vertices)  // the mesh at the same inputs, to the caller's (B, V, 3)
+    if ((rc = launch_posed_pass(h, route_of(h, batch, {Entry::kForward}), {nullptr, mesh_alone(&fa, vertices)}, ws, batch, st))) return rc;
   return post_launch_check();
 }
 
@@ -2512,21 +2600,11 @@ size_t smplfit_forward_backward_workspace_bytes(const smplfit_handle* h, int bat
 int smplfit_forward_backward_f32(const smplfit_handle* h, const smplfit_forward_backward_args* a) {
   if (!a) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_backward_f32: null arguments");
   const int B = a->batch;
-  if (!h) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_backward_f32: null handle");
-  if (!h->has_device) return fail(SMPLFIT_ERR_HIP, "handle was created host-only (no device)");
-  if (B <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "batch must be positive");
-  if (!a->workspace || ((uintptr_t)a->workspace & 255))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
-  if (a->workspace_bytes < smplfit_forward_backward_workspace_bytes(h, B))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (smplfit_forward_backward_workspace_bytes)");
-  if ((a->pose_rotvecs != nullptr) + (a->glob_rotmats != nullptr) + (a->rel_rotmats != nullptr) > 1)
-    return fail(SMPLFIT_ERR_BAD_ARG, "Only one rotation input may be provided");
+  if (int rc = check_common(h, B, a->workspace, a->workspace_bytes, true)) return rc;
   const DevModel& d = h->d;
-  const int nb_max = d.S - d.jt.n_kid - d.jt.n_pad;
-  if (a->shape_betas && a->num_betas_given > nb_max)
-    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_backward_f32: more betas than the model holds; slice first");
-  if (a->kid_factor && !d.jt.n_kid)
-    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_backward_f32: kid_factor given to a handle without kid");
+  if (int rc = check_forward_inputs("smplfit_forward_backward_f32", d, a->pose_rotvecs, a->glob_rotmats, a->rel_rotmats,
+                                    a->shape_betas, a->num_betas_given, a->kid_factor))
+    return rc;
   // (route_of: Entry::kForwardBackward is never batch-major; these kernels serve every model)
   hipStream_t st = (hipStream_t)a->hip_stream;
   Workspace ws;
@@ -2546,8 +2624,7 @@ int smplfit_forward_backward_f32(const smplfit_handle* h, const smplfit_forward_
     fa.trans = nullptr;
     fa.joints = ws.rjoints;
     fa.orient = nullptr;
-    launch_forward_joint(d, fa, ws, B, st);
-    if (int rc = launch_gemm(d, ws, B, st)) return rc;
+    if (int rc = launch_posed_pass(h, route_of(h, B, {Entry::kForwardBackward}), {&fa, {}}, ws, B, st)) return rc;
     const size_t lds = ((size_t)d.J * 9 + d.S + 4 * (size_t)d.J * 12 + 12) * 4;
     hipLaunchKernelGGL(k_bwd_vertex, dim3(B), dim3(256), lds, st, d, ws, bw, B, nb, a->shape_betas, a->kid_factor,
                        a->grad_vertices);
@@ -2601,14 +2678,10 @@ int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solv
   if (rc) return rc;
   if (!args->glob_rotmats || !args->target_vertices || !args->shape_betas || !args->trans)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_shape_solve_f32: null pointer");
-  if (args->scale_mode < 0 || args->scale_mode > 2)
-    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_shape_solve_ex_f32: scale_mode must be 0, 1 (scale_target) or 2 (scale_fit)");
-  if (args->scale_mode && !args->scale_corr)
-    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_shape_solve_ex_f32: a scale option needs the scale_corr output");
+  if ((rc = check_scale_share("smplfit_shape_solve_ex_f32", args->scale_mode, args->scale_corr, args->share_beta, args->share_allreduce)))
+    return rc;
   if (args->scale_mode && (args->vertices_out || args->joints_out))
     return fail(SMPLFIT_ERR_UNSUPPORTED, "smplfit_shape_solve_ex_f32: no mesh outputs with a scale unknown");
-  if (args->share_allreduce && !args->share_beta)
-    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_shape_solve_ex_f32: share_allreduce without share_beta");
   if (args->kid_regularizer_reference && !h->t.n_kid)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_shape_solve_ex_f32: kid_regularizer_reference given to a handle without kid");
   if (args->beta_regularizer_reference && (args->num_reference_betas < 0 || args->num_reference_betas > h->t.num_betas()))
@@ -2620,8 +2693,7 @@ int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solv
   Workspace ws;
   carve(h->t, batch, (char*)args->workspace, &ws);
   const bool joints = args->target_joints != nullptr;
-  const bool eff_v = joints ? (vertex_weights && joint_weights) : (vertex_weights != nullptr);
-  const bool eff_j = joints && vertex_weights && joint_weights;
+  const SolveWeights w = solve_weights(joints, vertex_weights, joint_weights);
   FitOptions o{1, args->beta_regularizer, args->beta_regularizer2, args->kid_regularizer, 0, 0};
   o.share_beta = args->share_beta ? 1 : 0;
   o.share_allreduce = args->share_allreduce;
@@ -2634,43 +2706,25 @@ int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solv
                        args->beta_regularizer_reference,
                        args->beta_regularizer_reference ? std::min(args->num_reference_betas, d.S - d.jt.n_kid - d.jt.n_pad) : 0,
                        args->kid_regularizer_reference);
-  // the batch-major vertex kernels (round 4): streams, transposed GEMM, residual pass + pair-Gram (unit weights) or the
-  // accumulate kernel (vertex weights in the solve / a scale unknown), as one iteration of fit()
+  // one iteration of fit() at given rotations: targets in, joint stage (prologue only), normal equations, solve
   const bool scaled = o.scale_mode != 0;
-  const Route r = route_of(h, batch, {Entry::kShapeSolve, joints, vertex_weights != nullptr, eff_v, o.scale_mode, o.share_beta != 0});
-  const int Mp = (int)align_up((size_t)batch, 128);
-  if (r.bm) {  // (the weight stream only where the weights enter the solve)
-    launch_layout_bm(h, args->target_vertices, args->target_joints, ws, batch, st, eff_v ? vertex_weights : nullptr, false, true);
-  } else {
-    launch_center_sort(d, args->target_vertices, args->target_joints, vertex_weights, ws, batch, st);
-  }
+  const Route r = route_of(h, batch, {Entry::kShapeSolve, joints, vertex_weights != nullptr, w.v, o.scale_mode, o.share_beta != 0});
+  // (batch-major: the weight stream only where the weights enter the solve)
+  const TargetsIn t{args->target_vertices, args->target_joints, vertex_weights, w.v ? vertex_weights : nullptr};
+  if ((rc = launch_targets_in(h, r, t, ws, batch, st))) return rc;
   JointStageArgs ja{};
-  ja.tj = joints ? ws.tjc : ws.tjreg;  // unused without the joint block
+  ja.tj = rotation_targets(ws, joints);  // unused without the joint block
   ja.rj = nullptr;
   ja.rj_shared = 1;
   ja.Gprev = args->glob_rotmats;
   ja.jw = joint_weights;
   ja.fit_rotations = 0;
   ja.do_prologue = 1;
-  const bool gjr = gen_joint_rows(d) && joints;
-  ja.joint_block = (joints && !gjr) ? 1 : 0;
-  ja.joint_block_weighted = eff_j ? 1 : 0;
-  ja.vertex_sa_closed_form = (eff_v || d.general) ? 0 : 1;  // (the general accumulate sums SA itself)
+  set_joint_block(&ja, d, joints, w);
   if (!joints) hipMemsetAsync(ws.tjreg, 0, (size_t)batch * d.J * 3 * 4, st);
   launch_joint_stage(d, ja, ws, batch, st);
-  if (r.bm) {
-    if (int rc2 = launch_gemm(d, ws, batch, st, true)) return rc2;
-    if (r.jd_transpose) launch_jd_transpose(d, ws, batch, st);
-    if (scaled) launch_accum_w_bm(h, ws, batch, st, eff_v, true);
-    else if (eff_v) launch_accum_w_bm(h, ws, batch, st);
-    else launch_residual_bm(h, ws, batch, st, r.solve_bm ? 3 : 7);
-  } else {
-    launch_gemm(d, ws, batch, st);
-    if (int rc = launch_accum_any(d, ws, batch, eff_v, r.pair_in, st, gjr ? ja.tj : nullptr, gjr && eff_j ? joint_weights : nullptr,
-                                  scaled))
-      return rc;
-  }
-  rc = enqueue_solve(h, r, ws, batch, o, joints, eff_v, eff_j, joint_weights, use_ref, scaled, st);
+  if ((rc = launch_normal_equations(h, r, joints, w, ja.tj, joint_weights, scaled, ws, batch, st))) return rc;
+  rc = enqueue_solve(h, r, ws, batch, o, joints, w, joint_weights, use_ref, scaled, st);
   if (rc) return rc;
   // a scaled solve leaves the shape as the reference returns it (undivided, :1277-1283) in beta_out
   hipLaunchKernelGGL(k_emit_solution, dim3((batch + 255) / 256), dim3(256), 0, st, ws,
@@ -2681,15 +2735,8 @@ int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solv
   if (args->joints_out)
     hipLaunchKernelGGL(k_copy, dim3(64), dim3(256), 0, st, ws.rjoints, args->joints_out,
                        (size_t)batch * d.J * 3);
-  if (args->vertices_out && r.bm) {  // the mesh at the solution: forward-only LBS pass + the inverse of the target layout
-    const ShareView sv = share_view(h, sf::kShareLbsAll, batch);
-    if (int rc_f = launch_lbs_fwd_bm(d, sv, ws, batch, Mp, st)) return rc_f;
-    hipLaunchKernelGGL(k_unlayout_vertices, dim3((d.V + kSlabV - 1) / kSlabV, Mp / 64), dim3(256), (size_t)64 * kSlabRow * 4, st, d,
-                       ws.vpT, args->vertices_out, batch);
-  } else if (args->vertices_out) {
-    float* vertices_out = args->vertices_out;
-    if (int rc = launch_lbs_any<2>(d, ws, batch, false, d.S, ws.beta, ws.trans, vertices_out, st)) return rc;
-  }
+  if (args->vertices_out)  // the mesh at the solution
+    if ((rc = launch_lbs_pass(h, r, mesh_alone(nullptr, args->vertices_out), ws, batch, st))) return rc;
   return post_launch_check();
 }
 
@@ -2798,22 +2845,9 @@ int smplfit_convert_f32(const smplfit_convert_plan* p, const smplfit_convert_arg
   const CallShape conv{Entry::kConvert, false};
   if (!route_of(p->in, 1, conv).bm || !route_of(p->out, a->batch, conv).bm)
     return fail(SMPLFIT_ERR_UNSUPPORTED, "smplfit_convert_f32: the batch-major path is switched off");
-  smplfit_fit_args f{};
-  f.batch = a->batch;
-  f.num_iter = a->num_iter;
-  f.beta_regularizer = a->beta_regularizer;
-  f.beta_regularizer2 = a->beta_regularizer2;
-  f.kid_regularizer = a->kid_regularizer;
-  f.final_adjust_rots = a->final_adjust_rots;
-  f.pose_rotvecs = a->out_pose_rotvecs;
-  f.shape_betas = a->out_shape_betas;
-  f.trans = a->out_trans;
-  f.kid_factor = a->out_kid_factor;
-  f.orientations = a->out_orientations;
-  f.relative_orientations = a->out_relative_orientations;
+  smplfit_fit_args f = fused_fit_args(*a);
   f.workspace = a->workspace;
   f.workspace_bytes = a->workspace_bytes;
-  f.hip_stream = a->hip_stream;
   ConvertJob job{p, a->pose_rotvecs, a->shape_betas, a->trans, a->shape_betas ? a->num_betas_given : 0, nullptr};
   return fit_impl(p->out, &f, &job);
 }
@@ -2887,25 +2921,12 @@ int smplfit_flip_f32(const smplfit_flip_plan* p, const smplfit_flip_args* a) {
   const size_t pose_bytes = flip_pose_bytes(h, B);
   float* init_pose = (float*)a->workspace;
   hipLaunchKernelGGL(k_naive_flip, dim3((B + 255) / 256), dim3(256), 0, st, a->pose_rotvecs, p->d_perm, init_pose, B, h->t.J);
-  smplfit_fit_args f{};
-  f.batch = B;
-  f.num_iter = a->num_iter;
-  f.beta_regularizer = a->beta_regularizer;
-  f.beta_regularizer2 = a->beta_regularizer2;
-  f.kid_regularizer = a->kid_regularizer;
-  f.final_adjust_rots = a->final_adjust_rots;
+  smplfit_fit_args f = fused_fit_args(*a);
   f.initial_pose_rotvecs = init_pose;
   f.initial_shape_betas = a->shape_betas;
   f.num_initial_betas = a->shape_betas ? a->num_betas_given : 0;
-  f.pose_rotvecs = a->out_pose_rotvecs;
-  f.shape_betas = a->out_shape_betas;
-  f.trans = a->out_trans;
-  f.kid_factor = a->out_kid_factor;
-  f.orientations = a->out_orientations;
-  f.relative_orientations = a->out_relative_orientations;
   f.workspace = (char*)a->workspace + pose_bytes;
   f.workspace_bytes = a->workspace_bytes - pose_bytes;
-  f.hip_stream = a->hip_stream;
   ConvertJob job{&p->conv, a->pose_rotvecs, a->shape_betas, a->trans, a->shape_betas ? a->num_betas_given : 0,
                  a->kid_factor};
   return fit_impl(h, &f, &job);

@@ -3,7 +3,8 @@
 // The device code keeps its arithmetic in headers shared with this file (csrc/sf_math.h,
 // csrc/sf_stages.h, csrc/sf_tables.cpp): the joint-level stages run here with a one-lane context
 // (lane = 0, n = 1, sync = no-op) and the per-vertex bodies run in plain loops in the same order of
-// kernels as run_fit() in csrc/smplfit_hip.hip.  This lets the build container (no GPU) check the
+// kernels as run_fit() and its steps (launch_targets_in, launch_normal_equations, launch_lbs_pass) in
+// csrc/smplfit_hip.hip.  This lets the build container (no GPU) check the
 // table builder, the stage logic and the orchestration against the oracle and the golden vectors
 // before any GPU minute is spent; wave reductions / LDS staging / MFMA remain GPU-only code that the
 // -m gpu parity tests cover.  Built by tests/test_hostemu.py with g++.
@@ -410,7 +411,7 @@ int fit_impl(const sf::HostTables& t, const float* tv, const float* tj, const fl
       };
       if (!e.share_beta) {
         for (int b = 0; b < B; ++b) stage(b, 0, nullptr);
-      } else {  // shared shape, own scale: mirrors the three launches of enqueue_solve
+      } else {  // shared shape, own scale: mirrors the three launches of enqueue_solve (smplfit_hip.hip)
         const int NC = S * S + S;
         std::vector<double> cen((size_t)(B + 1) * NC, 0.0);
         for (int b = 0; b < B; ++b) stage(b, 1, cen.data() + (size_t)b * NC);
@@ -475,7 +476,7 @@ int fit_impl(const sf::HostTables& t, const float* tv, const float* tj, const fl
   return 0;
 }
 
-// mirrors run_fit_known_shape (smplfit_hip.hip)
+// mirrors run_fit_known_shape (smplfit_hip.hip): launch_targets_in, launch_posed_pass per rotation pass, launch_alignment
 template <int S, int KW>
 int known_shape_impl(const sf::HostTables& t, const float* betas, int nb, const float* kid,
                      const float* init_pose, const float* tv, const float* tj, const float* vw,
