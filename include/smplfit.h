@@ -227,6 +227,41 @@ typedef struct smplfit_forward_backward_args {
 } smplfit_forward_backward_args;
 int smplfit_forward_backward_f32(const smplfit_handle* h, const smplfit_forward_backward_args* args);
 
+/* Value and gradient of the mesh-distance objective in one call (a refinement step of BodyFlipperOpt):
+ *   loss[b] = scale * sum_v w_bv |v_bv - t_bv|,   L = sum_b loss[b],
+ * v = the vertices of smplfit_forward_ex_f32 at the inputs (trans included), t = target_vertices, w = vertex_weights
+ * (NULL: 1).  Outputs: loss (B, required) and the gradients of L, each may be NULL (= not wanted): the gradient of the
+ * rotation form given, grad_shape_betas (B,num_betas_given), grad_trans (B,3), grad_kid_factor (B).  The cotangent of
+ * a vertex is scale * w * (v - t) / |v - t|, exactly 0 where |v - t| == 0.  The skinned vertex and its cotangent are
+ * formed in registers by the vertex pass of the backward: neither reaches memory, and the joint stage and the
+ * posedirs product run once.  Rotation vectors at r = 0 and determinism: as smplfit_forward_backward_f32.
+ * Serves every model.  Workspace: smplfit_mesh_objective_workspace_bytes.  Zero-initialise. */
+size_t smplfit_mesh_objective_workspace_bytes(const smplfit_handle* h, int batch);
+typedef struct smplfit_mesh_objective_args {
+  const float* pose_rotvecs;       /* (B,3J) or NULL */
+  const float* glob_rotmats;       /* (B,J,3,3) or NULL */
+  const float* rel_rotmats;        /* (B,J,3,3) or NULL */
+  const float* shape_betas;        /* (B,num_betas_given) or NULL */
+  int32_t num_betas_given;
+  const float* trans;              /* (B,3) or NULL */
+  const float* kid_factor;         /* (B) or NULL (kid handles only) */
+  int32_t batch;
+  const float* target_vertices;    /* (B,V,3) */
+  const float* vertex_weights;     /* (B,V) or NULL */
+  float scale;
+  float* loss;                     /* out (B) */
+  float* grad_pose_rotvecs;        /* out (B,3J) or NULL */
+  float* grad_glob_rotmats;        /* out (B,J,3,3) or NULL */
+  float* grad_rel_rotmats;         /* out (B,J,3,3) or NULL */
+  float* grad_shape_betas;         /* out (B,num_betas_given) or NULL */
+  float* grad_trans;               /* out (B,3) or NULL */
+  float* grad_kid_factor;          /* out (B) or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  void* hip_stream;
+} smplfit_mesh_objective_args;
+int smplfit_mesh_objective_f32(const smplfit_handle* h, const smplfit_mesh_objective_args* args);
+
 /* BodyFitter.fit with a warm start (pt/bodyfitter.py:363-382): smplfit_fit_f32 plus
  *   initial_pose_rotvecs (B,3J) or NULL, initial_shape_betas (B,num_initial_betas) or NULL,
  *   initial_kid_factor (B) or NULL (enable_kid handles only).

@@ -5,6 +5,8 @@
 //   k_bwd_vertex      grid B, block 256: per instance, one read of grad_vertices; dv_posed = (sum_k w_vk G_k)^T g_v in
 //                     slot order, dA_k = sum_v w_vk g_v (x) [v_posed_v, 1] and sum_v g_v.  Per-joint sums: each wave
 //                     owns a row of LDS sums that it adds to in segment order; the four rows are added in wave order.
+//   k_obj_vertex      the same pass for smplfit_mesh_objective_f32: g_v is not read but computed from the skinned vertex
+//                     and the target (the vertex and its cotangent stay in registers), plus the instance's loss
 //   k_bwd_reduce      split-K over workgroups: [dfeat | dshape] (B, P + S) = dv_posed (B, 3 Vp) . [posedirs | shapedirs]^T,
 //                     partial rows per K chunk; k_bwd_combine adds the chunks in chunk order
 //   k_bwd_joint       lane = instance: sf::forward_joint_backward (reverse FK chain, J_shapedirs, Rodrigues)
@@ -26,10 +28,28 @@ struct BwdWorkspace {
 
 inline int bwd_nsplit(int Vp) { return (3 * Vp + kBwdKChunk - 1) / kBwdKChunk; }
 
-// grid B, block 256 (4 waves; a wave walks the part-aligned 64-slot tiles segall[w], segall[w + 4], ...)
-__global__ __launch_bounds__(256) void k_bwd_vertex(DevModel m, Workspace ws, BwdWorkspace bw, int B, int nb,
-                                                    const float* __restrict__ beta_in, const float* __restrict__ kid_in,
-                                                    const float* __restrict__ gv) {
+// The mesh-distance objective of k_obj_vertex (smplfit_mesh_objective_f32)
+struct ObjArgs {
+  const float* target;  // (B, V, 3)
+  const float* vw;      // (B, V) or NULL
+  const float* trans;   // (B, 3) or NULL
+  float scale;
+  float* loss;          // (B)
+};
+
+inline size_t bwd_vertex_lds_bytes(const DevModel& d, bool obj) {
+  return ((size_t)d.J * 9 + d.S + 4 * (size_t)d.J * 12 + 12 + (obj ? 4 + (size_t)d.J * 3 : 0)) * 4;
+}
+
+// The vertex pass of one instance (a workgroup of 4 waves; a wave walks the part-aligned 64-slot tiles segall[w],
+// segall[w + 4], ...).  OBJ = false: the cotangent g_v is read from gv (B, V, 3).  OBJ = true: it is computed: the
+// skinned vertex M x + sum_k w_k T_k + trans is built here from the blended rotation, the rest vertex and the joint
+// translations (jd floats 9..11, sf_stages.h), compared with the target, and sf::mesh_objective_vertex gives the loss
+// term and g_v; the instance's loss is summed per wave in segment order, the four waves in wave order.
+template <bool OBJ>
+__device__ __forceinline__ void bwd_vertex_body(const DevModel& m, const Workspace& ws, const BwdWorkspace& bw, int nb,
+                                                const float* __restrict__ beta_in, const float* __restrict__ kid_in,
+                                                const float* __restrict__ gv, const ObjArgs& oa) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int S = m.S, J = m.J, Vp = m.Vp, V = m.V, KW = m.KW;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -38,7 +58,11 @@ __global__ __launch_bounds__(256) void k_bwd_vertex(DevModel m, Workspace ws, Bw
   float* sbeta = sG + J * 9;     // [S]
   float* acc = sbeta + S;        // [4][J][12]
   float* acct = acc + 4 * J * 12;  // [4][3]
+  float* accl = acct + 12;         // [4] loss per wave        (OBJ)
+  float* sT = accl + 4;            // [J][3] joint translations (OBJ)
   for (int k = tid; k < J * 9; k += 256) sG[k] = ws.jd[((size_t)b * J + k / 9) * stride + k % 9];
+  if constexpr (OBJ)
+    for (int k = tid; k < J * 3; k += 256) sT[k] = ws.jd[((size_t)b * J + k / 3) * stride + 9 + k % 3];
   for (int s = tid; s < S; s += 256) {
     float v = (beta_in && s < nb) ? beta_in[(size_t)b * nb + s] : 0.f;
     if (kid_in && m.jt.n_kid && s == S - 1) v = kid_in[b];
@@ -51,6 +75,10 @@ __global__ __launch_bounds__(256) void k_bwd_vertex(DevModel m, Workspace ws, Bw
   const float* vps = ws.vposed + (size_t)b * 3 * Vp;
   float* aw = acc + wave * J * 12;
   float tsum[3] = {0.f, 0.f, 0.f};
+  float lsum = 0.f, tr[3] = {0.f, 0.f, 0.f};
+  if constexpr (OBJ)
+    if (oa.trans)
+      for (int c = 0; c < 3; ++c) tr[c] = oa.trans[(size_t)b * 3 + c];
   for (int sg = wave; sg < m.nsegall; sg += 4) {
     const int start = m.segall[sg * 3], count = m.segall[sg * 3 + 1];
     const bool live = lane < count;
@@ -63,12 +91,14 @@ __global__ __launch_bounds__(256) void k_bwd_vertex(DevModel m, Workspace ws, Bw
       x[2] += m.sd[(size_t)(2 * S + s) * Vp + i] * bs;
     }
     float g[3] = {0.f, 0.f, 0.f};
-    if (live) {
-      const int o = m.perm[i];
-      for (int c = 0; c < 3; ++c) g[c] = gv[((size_t)b * V + o) * 3 + c];
-    }
+    if constexpr (!OBJ)
+      if (live) {
+        const int o = m.perm[i];
+        for (int c = 0; c < 3; ++c) g[c] = gv[((size_t)b * V + o) * 3 + c];
+      }
     // blended rotation and the joints this tile touches (64-bit mask, OR over the wave)
     float M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float Tb[3] = {0.f, 0.f, 0.f};
     uint64_t mask = 0;
     for (int k = 0; k < KW; ++k) {
       const int j = (m.widx[(size_t)(k >> 2) * Vp + i] >> (8 * (k & 3))) & 0xff;
@@ -76,7 +106,21 @@ __global__ __launch_bounds__(256) void k_bwd_vertex(DevModel m, Workspace ws, Bw
       if (w != 0.f) mask |= (uint64_t)1 << j;
 #pragma unroll
       for (int e = 0; e < 9; ++e) M[e] += w * sG[j * 9 + e];
+      if constexpr (OBJ)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Tb[c] += w * sT[j * 3 + c];
     }
+    if constexpr (OBJ)
+      if (live) {
+        const size_t o = (size_t)b * V + m.perm[i];
+        float v[3], t[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          v[c] = (M[c * 3] * x[0] + M[c * 3 + 1] * x[1] + M[c * 3 + 2] * x[2]) + Tb[c] + tr[c];
+          t[c] = oa.target[o * 3 + c];
+        }
+        lsum += sf::mesh_objective_vertex(v, t, oa.vw ? oa.scale * oa.vw[o] : oa.scale, g);
+      }
     for (int o = 32; o > 0; o >>= 1) {
       const uint32_t lo = __shfl_xor((uint32_t)mask, o, 64), hi = __shfl_xor((uint32_t)(mask >> 32), o, 64);
       mask |= ((uint64_t)hi << 32) | lo;
@@ -113,10 +157,30 @@ __global__ __launch_bounds__(256) void k_bwd_vertex(DevModel m, Workspace ws, Bw
   for (int c = 0; c < 3; ++c) tsum[c] = wave_sum(tsum[c]);
   if (lane == 0)
     for (int c = 0; c < 3; ++c) acct[wave * 3 + c] = tsum[c];
+  if constexpr (OBJ) {
+    lsum = wave_sum(lsum);
+    if (lane == 0) accl[wave] = lsum;
+  }
   __syncthreads();
   for (int k = tid; k < J * 12; k += 256)
     bw.dA[(size_t)b * J * 12 + k] = ((acc[k] + acc[J * 12 + k]) + acc[2 * J * 12 + k]) + acc[3 * J * 12 + k];
   if (tid < 3) bw.dtv[b * 3 + tid] = ((acct[tid] + acct[3 + tid]) + acct[6 + tid]) + acct[9 + tid];
+  if constexpr (OBJ)
+    if (tid == 0) oa.loss[b] = ((accl[0] + accl[1]) + accl[2]) + accl[3];
+}
+
+// grid B, block 256
+__global__ __launch_bounds__(256) void k_bwd_vertex(DevModel m, Workspace ws, BwdWorkspace bw, int B, int nb,
+                                                    const float* __restrict__ beta_in, const float* __restrict__ kid_in,
+                                                    const float* __restrict__ gv) {
+  bwd_vertex_body<false>(m, ws, bw, nb, beta_in, kid_in, gv, ObjArgs{});
+}
+
+// grid B, block 256: the same pass with the cotangent of the mesh-distance objective computed in registers
+__global__ __launch_bounds__(256) void k_obj_vertex(DevModel m, Workspace ws, BwdWorkspace bw, int B, int nb,
+                                                    const float* __restrict__ beta_in, const float* __restrict__ kid_in,
+                                                    ObjArgs oa) {
+  bwd_vertex_body<true>(m, ws, bw, nb, beta_in, kid_in, nullptr, oa);
 }
 
 // grid (ceil(NC / 64), ceil(B / 64), nsplit), block 256: a 64 x 64 tile of the partial product of K chunk z, 4 x 4

@@ -1697,6 +1697,19 @@ SF_HD void forward_joint_backward(const JointTabs& tb, const float* pose_rotvecs
     for (int j = 0; j < J; ++j) rotvec2mat_vjp(pose_rotvecs + j * 3, dR + j * 9, g_pose + j * 3);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Mesh-distance objective (smplfit_mesh_objective_f32), one vertex: the term sw |v - t| of the loss (sw = scale * w)
+// and its cotangent g = sw (v - t) / |v - t|, exactly 0 where |v - t| == 0 (torch.linalg.norm's backward) and where
+// sw == 0.
+// ---------------------------------------------------------------------------------------------
+SF_HD float mesh_objective_vertex(const float* v, const float* t, float sw, float* g) {
+  const float r[3] = {v[0] - t[0], v[1] - t[1], v[2] - t[2]};
+  const float d = sqrtf(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  const float k = sw * (d > 0.f ? 1.f / d : 0.f);
+  for (int c = 0; c < 3; ++c) g[c] = k * r[c];
+  return sw * d;
+}
+
 #undef SF_FOR
 
 }  // namespace sf

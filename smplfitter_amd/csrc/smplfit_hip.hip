@@ -14,6 +14,7 @@
 //   k_refine_epilogue      K6  dependent rotation refinement + relative rotations + log map
 //   k_forward_joint, k_lbs_partsum<MODE 2>   BodyModel.forward;  k_scale_trans  known-shape alignment
 //   k_bwd_vertex, k_bwd_reduce, k_bwd_combine, k_bwd_joint   its backward (kernels_bwd.inc)
+//   k_obj_vertex                                           value + gradient of the mesh-distance objective (same file)
 // Batch-major kernels (LANE = INSTANCE; the default vertex block where they apply, see route_of): k_layout_targets,
 //   k_mean_finish, k_template_partsum_bm, k_residual_bm, k_pair_gram_bm, k_gram_combine_bm, k_lbs_partsum_bm,
 //   k_psum_combine, k_regress_joints_bm, k_transpose_targets (joint rows) — grid = (vertex group | unit chunk) x
@@ -2590,6 +2591,14 @@ size_t forward_backward_carve(const smplfit_handle* h, int B, char* base, Worksp
   return off;
 }
 
+// [dfeat | dshape] = dv_posed . [posedirs | shapedirs]^T: the split-K partial products, then their sum in chunk order
+void launch_bwd_reduce(const DevModel& d, const BwdWorkspace& bw, int B, hipStream_t st) {
+  const int NC = d.P + d.S, nsplit = bwd_nsplit(d.Vp);
+  hipLaunchKernelGGL(k_bwd_reduce, dim3((NC + kBwdTile - 1) / kBwdTile, (B + kBwdTile - 1) / kBwdTile, nsplit),
+                     dim3(256), 0, st, d, bw, B);
+  hipLaunchKernelGGL(k_bwd_combine, dim3((unsigned)(((size_t)B * NC + 255) / 256)), dim3(256), 0, st, bw, B, NC, nsplit);
+}
+
 size_t smplfit_forward_backward_workspace_bytes(const smplfit_handle* h, int batch) {
   if (!h || batch <= 0) return 0;
   Workspace ws;
@@ -2625,13 +2634,9 @@ int smplfit_forward_backward_f32(const smplfit_handle* h, const smplfit_forward_
     fa.joints = ws.rjoints;
     fa.orient = nullptr;
     if (int rc = launch_posed_pass(h, route_of(h, B, {Entry::kForwardBackward}), {&fa, {}}, ws, B, st)) return rc;
-    const size_t lds = ((size_t)d.J * 9 + d.S + 4 * (size_t)d.J * 12 + 12) * 4;
-    hipLaunchKernelGGL(k_bwd_vertex, dim3(B), dim3(256), lds, st, d, ws, bw, B, nb, a->shape_betas, a->kid_factor,
-                       a->grad_vertices);
-    const int NC = d.P + d.S, nsplit = bwd_nsplit(d.Vp);
-    hipLaunchKernelGGL(k_bwd_reduce, dim3((NC + kBwdTile - 1) / kBwdTile, (B + kBwdTile - 1) / kBwdTile, nsplit),
-                       dim3(256), 0, st, d, bw, B);
-    hipLaunchKernelGGL(k_bwd_combine, dim3((unsigned)(((size_t)B * NC + 255) / 256)), dim3(256), 0, st, bw, B, NC, nsplit);
+    hipLaunchKernelGGL(k_bwd_vertex, dim3(B), dim3(256), bwd_vertex_lds_bytes(d, false), st, d, ws, bw, B, nb,
+                       a->shape_betas, a->kid_factor, a->grad_vertices);
+    launch_bwd_reduce(d, bw, B, st);
   }
   JointBwdArgs ja{};
   ja.pose = a->pose_rotvecs;
@@ -2643,6 +2648,67 @@ int smplfit_forward_backward_f32(const smplfit_handle* h, const smplfit_forward_
   ja.gjoints = a->grad_joints;
   ja.gorient = a->grad_orientations;
   ja.vertex = vertex;
+  ja.g_pose = a->grad_pose_rotvecs;
+  ja.g_glob = a->grad_glob_rotmats;
+  ja.g_rel = a->grad_rel_rotmats;
+  ja.g_betas = a->grad_shape_betas;
+  ja.g_trans = a->grad_trans;
+  ja.g_kid = a->grad_kid_factor;
+  hipLaunchKernelGGL(k_bwd_joint, dim3((B + 63) / 64), dim3(64), 0, st, d, bw, ja, B);
+  return post_launch_check();
+}
+
+// The loss sums live in LDS (k_obj_vertex): the workspace is the backward's.
+size_t smplfit_mesh_objective_workspace_bytes(const smplfit_handle* h, int batch) {
+  return smplfit_forward_backward_workspace_bytes(h, batch);
+}
+
+int smplfit_mesh_objective_f32(const smplfit_handle* h, const smplfit_mesh_objective_args* a) {
+  const char* who = "smplfit_mesh_objective_f32";
+  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
+  if (!h) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null handle");
+  if (!h->has_device) return fail(SMPLFIT_ERR_HIP, "handle was created host-only (no device)");
+  const int B = a->batch;
+  if (B <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "batch must be positive");
+  if (!a->workspace || ((uintptr_t)a->workspace & 255))
+    return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
+  if (a->workspace_bytes < smplfit_mesh_objective_workspace_bytes(h, B))
+    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (smplfit_mesh_objective_workspace_bytes)");
+  const DevModel& d = h->d;
+  if (int rc = check_forward_inputs(who, d, a->pose_rotvecs, a->glob_rotmats, a->rel_rotmats, a->shape_betas,
+                                    a->num_betas_given, a->kid_factor))
+    return rc;
+  if (!a->target_vertices) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": target_vertices is required");
+  if (!a->loss) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": loss output is required");
+  hipStream_t st = (hipStream_t)a->hip_stream;
+  Workspace ws;
+  BwdWorkspace bw;
+  forward_backward_carve(h, B, (char*)a->workspace, &ws, &bw);
+  const int nb = a->shape_betas ? std::max(0, a->num_betas_given) : 0;
+  // the posed pass of the backward: the joint block (G | t) without trans (k_obj_vertex adds it) and v_posed
+  ForwardArgs fa{};
+  fa.pose = a->pose_rotvecs;
+  fa.glob = a->glob_rotmats;
+  fa.rel = a->rel_rotmats;
+  fa.betas = a->shape_betas;
+  fa.nb = nb;
+  fa.kid = a->kid_factor;
+  fa.trans = nullptr;
+  fa.joints = ws.rjoints;
+  fa.orient = nullptr;
+  if (int rc = launch_posed_pass(h, route_of(h, B, {Entry::kForwardBackward}), {&fa, {}}, ws, B, st)) return rc;
+  const ObjArgs oa{a->target_vertices, a->vertex_weights, a->trans, a->scale, a->loss};
+  hipLaunchKernelGGL(k_obj_vertex, dim3(B), dim3(256), bwd_vertex_lds_bytes(d, true), st, d, ws, bw, B, nb,
+                     a->shape_betas, a->kid_factor, oa);
+  launch_bwd_reduce(d, bw, B, st);
+  JointBwdArgs ja{};
+  ja.pose = a->pose_rotvecs;
+  ja.glob = a->glob_rotmats;
+  ja.rel = a->rel_rotmats;
+  ja.betas = a->shape_betas;
+  ja.kid = a->kid_factor;
+  ja.nb = nb;
+  ja.vertex = true;
   ja.g_pose = a->grad_pose_rotvecs;
   ja.g_glob = a->grad_glob_rotmats;
   ja.g_rel = a->grad_rel_rotmats;

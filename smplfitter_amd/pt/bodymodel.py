@@ -154,22 +154,11 @@ class BodyModel(nn.Module):
         return self._forward_direct(pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats,
                                     glob_rotmats, return_vertices)
 
-    def _backward_direct(self, pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats,
-                         grad_joints=None, grad_orientations=None, grad_vertices=None):
-        """The C-ABI call behind ``forward``'s backward (``smplfit_forward_backward_f32``): the gradients of the six
-        inputs (None for an input not given), each in the caller's shape and dtype — broadcasts of ``trans`` (1, 3) and
-        of a one-element ``kid_factor`` summed over the batch, betas beyond the model's ``num_betas`` zero."""
+    def _grad_inputs(self, batch, pose_rotvecs, shape_betas, kid_factor, rel_rotmats, glob_rotmats):
+        """The inputs of the gradient calls as detached contiguous fp32 tensors on the model's device: (pose, glob, rel,
+        betas cut to the model's ``num_betas``, their count, kid_factor expanded to the batch)."""
         device = self.v_template.device
         J = self.num_joints
-        batch = 0
-        for arg in (pose_rotvecs, shape_betas, trans, rel_rotmats, glob_rotmats):
-            if arg is not None:
-                batch = arg.shape[0]
-                break
-        ins = (pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)
-        zeros = [None if a is None or not isinstance(a, torch.Tensor) else torch.zeros_like(a) for a in ins]
-        if batch == 0:
-            return zeros
         prep = lambda t: None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
         rel = prep(rel_rotmats.reshape(batch, J, 3, 3)) if rel_rotmats is not None else None
         pose = prep(pose_rotvecs.reshape(batch, J * 3)) if pose_rotvecs is not None else None
@@ -187,6 +176,27 @@ class BodyModel(nn.Module):
             kid = kid.expand(batch).contiguous() if kid.numel() == 1 else kid.contiguous()
         elif kid_factor is not None:
             kid = torch.full((batch,), float(kid_factor), dtype=torch.float32, device=device)
+        return pose, glob, rel, betas, nb, kid
+
+    def _backward_direct(self, pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats,
+                         grad_joints=None, grad_orientations=None, grad_vertices=None):
+        """The C-ABI call behind ``forward``'s backward (``smplfit_forward_backward_f32``): the gradients of the six
+        inputs (None for an input not given), each in the caller's shape and dtype — broadcasts of ``trans`` (1, 3) and
+        of a one-element ``kid_factor`` summed over the batch, betas beyond the model's ``num_betas`` zero."""
+        device = self.v_template.device
+        J = self.num_joints
+        batch = 0
+        for arg in (pose_rotvecs, shape_betas, trans, rel_rotmats, glob_rotmats):
+            if arg is not None:
+                batch = arg.shape[0]
+                break
+        ins = (pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)
+        zeros = [None if a is None or not isinstance(a, torch.Tensor) else torch.zeros_like(a) for a in ins]
+        if batch == 0:
+            return zeros
+        prep = lambda t: None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        pose, glob, rel, betas, nb, kid = self._grad_inputs(batch, pose_rotvecs, shape_betas, kid_factor, rel_rotmats,
+                                                            glob_rotmats)
         g = lambda t: None if t is None or t.numel() == 0 else prep(t)  # noqa: E731
         gj, go, gv = g(grad_joints), g(grad_orientations), g(grad_vertices)
         new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=device)  # noqa: E731
@@ -209,11 +219,16 @@ class BodyModel(nn.Module):
                 grad_trans=p(g_trans), grad_kid_factor=p(g_kid), workspace=ws.data_ptr(),
                 workspace_bytes=ws.numel(), hip_stream=stream)
             _lib.check(_lib.load().smplfit_forward_backward_f32(h.ptr, C.byref(args)))
+        return self._grad_outputs(ins, zeros, batch, nb, g_pose, g_betas, g_trans, g_kid, g_rel, g_glob)
+
+    def _grad_outputs(self, ins, zeros, batch, nb, g_pose, g_betas, g_trans, g_kid, g_rel, g_glob):
+        """The native gradients in the callers' shapes and dtypes (``_backward_direct``)."""
+        pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats = ins
         out = list(zeros)
         if g_pose is not None:
             out[0] = g_pose.reshape(pose_rotvecs.shape).to(pose_rotvecs.dtype)
         if shape_betas is not None:
-            gb = torch.zeros(shape_betas.shape, dtype=torch.float32, device=device)
+            gb = torch.zeros(shape_betas.shape, dtype=torch.float32, device=self.v_template.device)
             if g_betas is not None:
                 gb[:, :nb] = g_betas
             out[1] = gb.to(shape_betas.dtype)
@@ -228,6 +243,57 @@ class BodyModel(nn.Module):
         if g_glob is not None:
             out[5] = g_glob.reshape(glob_rotmats.shape).to(glob_rotmats.dtype)
         return out
+
+    def _objective_direct(self, target_vertices, pose_rotvecs=None, shape_betas=None, trans=None, kid_factor=None,
+                          rel_rotmats=None, glob_rotmats=None, vertex_weights=None, scale: float = 1.0):
+        """Value and gradient of the mesh-distance objective in one C-ABI call (``smplfit_mesh_objective_f32``):
+        ``loss`` (B) with ``loss[b] = scale * sum_v w_bv |forward(inputs).vertices_bv - target_bv|``, and the gradients
+        of ``loss.sum()`` with respect to the six inputs, prepared and returned as ``_backward_direct`` does (a
+        broadcast ``trans`` / ``kid_factor`` is expanded on the way in and its gradient summed on the way out).  The
+        vertices and their cotangent are never written to memory.  Returns ``(loss, grads)``."""
+        device = self.v_template.device
+        J, V = self.num_joints, self.num_vertices
+        batch = target_vertices.shape[0]
+        if tuple(target_vertices.shape) != (batch, V, 3):
+            raise ValueError(f'target_vertices must have shape (batch, {V}, 3), got {tuple(target_vertices.shape)}')
+        ins = (pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)
+        if sum(x is not None for x in (pose_rotvecs, rel_rotmats, glob_rotmats)) > 1:
+            raise ValueError('Only one rotation input may be provided (pose_rotvecs, rel_rotmats, or glob_rotmats).')
+        zeros = [None if a is None or not isinstance(a, torch.Tensor) else torch.zeros_like(a) for a in ins]
+        loss = torch.zeros(batch, dtype=torch.float32, device=device)
+        if batch == 0:
+            return loss, zeros
+        prep = lambda t: None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        pose, glob, rel, betas, nb, kid = self._grad_inputs(batch, pose_rotvecs, shape_betas, kid_factor, rel_rotmats,
+                                                            glob_rotmats)
+        tr = prep(trans)
+        if tr is not None and tr.shape[0] != batch:
+            tr = tr.expand(batch, 3).contiguous()
+        target = prep(target_vertices)
+        vw = prep(vertex_weights)
+        if vw is not None and tuple(vw.shape) != (batch, V):
+            raise ValueError(f'vertex_weights must have shape (batch, {V}), got {tuple(vw.shape)}')
+        new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=device)  # noqa: E731
+        g_pose = new(batch, J * 3) if pose is not None else None
+        g_rel = new(batch, J, 3, 3) if rel is not None else None
+        g_glob = new(batch, J, 3, 3) if glob is not None else None
+        g_betas = new(batch, nb) if betas is not None else None
+        g_trans = new(batch, 3) if trans is not None else None
+        g_kid = new(batch) if isinstance(kid_factor, torch.Tensor) else None
+        h = self._native(device, kid=kid is not None)
+        ws = torch.empty(h.mesh_objective_workspace_bytes(batch), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            args = _lib.MeshObjectiveArgs(
+                pose_rotvecs=p(pose), glob_rotmats=p(glob), rel_rotmats=p(rel), shape_betas=p(betas),
+                num_betas_given=nb, trans=p(tr), kid_factor=p(kid), batch=batch, target_vertices=p(target),
+                vertex_weights=p(vw), scale=float(scale), loss=p(loss), grad_pose_rotvecs=p(g_pose),
+                grad_glob_rotmats=p(g_glob), grad_rel_rotmats=p(g_rel), grad_shape_betas=p(g_betas),
+                grad_trans=p(g_trans), grad_kid_factor=p(g_kid), workspace=ws.data_ptr(),
+                workspace_bytes=ws.numel(), hip_stream=stream)
+            _lib.check(_lib.load().smplfit_mesh_objective_f32(h.ptr, C.byref(args)))
+        return loss, self._grad_outputs(ins, zeros, batch, nb, g_pose, g_betas, g_trans, g_kid, g_rel, g_glob)
 
     def _forward_direct(self, pose_rotvecs=None, shape_betas=None, trans=None, kid_factor=None,
                         rel_rotmats=None, glob_rotmats=None, return_vertices: bool = True):
