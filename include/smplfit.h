@@ -262,6 +262,43 @@ typedef struct smplfit_mesh_objective_args {
 } smplfit_mesh_objective_args;
 int smplfit_mesh_objective_f32(const smplfit_handle* h, const smplfit_mesh_objective_args* args);
 
+/* The mesh-distance objective with a joint term (a refinement step of BodyFitterOpt):
+ *   loss[b] = scale * sum_v w_bv |v_bv - t_bv|  +  joint_scale * sum_j u_bj |p_bj - q_bj|,   L = sum_b loss[b],
+ * v, t, w as in smplfit_mesh_objective_f32; p = the joints of smplfit_forward_ex_f32 at the inputs (trans included),
+ * q = target_joints (B,J,3) or NULL, u = joint_weights (B,J) or NULL (= 1; refused without target_joints).  The
+ * cotangent of a joint is joint_scale * u * (p - q) / |p - q|, exactly 0 where |p - q| == 0 or u == 0; the joint terms
+ * of an instance are added in joint order.  Outputs and every other field: as smplfit_mesh_objective_f32.  With
+ * target_joints NULL the call makes the launches of smplfit_mesh_objective_f32 and returns its bits.
+ * Workspace: smplfit_fit_objective_workspace_bytes (the backward's plus a (B,J,3) cotangent).  Zero-initialise. */
+size_t smplfit_fit_objective_workspace_bytes(const smplfit_handle* h, int batch);
+typedef struct smplfit_fit_objective_args {
+  const float* pose_rotvecs;       /* (B,3J) or NULL */
+  const float* glob_rotmats;       /* (B,J,3,3) or NULL */
+  const float* rel_rotmats;        /* (B,J,3,3) or NULL */
+  const float* shape_betas;        /* (B,num_betas_given) or NULL */
+  int32_t num_betas_given;
+  const float* trans;              /* (B,3) or NULL */
+  const float* kid_factor;         /* (B) or NULL (kid handles only) */
+  int32_t batch;
+  const float* target_vertices;    /* (B,V,3) */
+  const float* vertex_weights;     /* (B,V) or NULL */
+  float scale;
+  const float* target_joints;      /* (B,J,3) or NULL */
+  const float* joint_weights;      /* (B,J) or NULL */
+  float joint_scale;
+  float* loss;                     /* out (B) */
+  float* grad_pose_rotvecs;        /* out (B,3J) or NULL */
+  float* grad_glob_rotmats;        /* out (B,J,3,3) or NULL */
+  float* grad_rel_rotmats;         /* out (B,J,3,3) or NULL */
+  float* grad_shape_betas;         /* out (B,num_betas_given) or NULL */
+  float* grad_trans;               /* out (B,3) or NULL */
+  float* grad_kid_factor;          /* out (B) or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  void* hip_stream;
+} smplfit_fit_objective_args;
+int smplfit_fit_objective_f32(const smplfit_handle* h, const smplfit_fit_objective_args* args);
+
 /* BodyFitter.fit with a warm start (pt/bodyfitter.py:363-382): smplfit_fit_f32 plus
  *   initial_pose_rotvecs (B,3J) or NULL, initial_shape_betas (B,num_initial_betas) or NULL,
  *   initial_kid_factor (B) or NULL (enable_kid handles only).

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     'smplfit_flip_f32', 'smplfit_reload_options', 'smplfit_get_share_table', 'smplfit_pick_share_mult',
     'smplfit_abi_version', 'smplfit_forward_backward_workspace_bytes', 'smplfit_forward_backward_f32',
     'smplfit_mesh_objective_workspace_bytes', 'smplfit_mesh_objective_f32',
+    'smplfit_fit_objective_workspace_bytes', 'smplfit_fit_objective_f32',
 ]  # fmt: skip
 
 _fp = C.POINTER(C.c_float)
@@ -120,6 +121,20 @@ class MeshObjectiveArgs(C.Structure):
         ('shape_betas', C.c_void_p), ('num_betas_given', C.c_int32), ('trans', C.c_void_p),
         ('kid_factor', C.c_void_p), ('batch', C.c_int32), ('target_vertices', C.c_void_p),
         ('vertex_weights', C.c_void_p), ('scale', C.c_float), ('loss', C.c_void_p),
+        ('grad_pose_rotvecs', C.c_void_p), ('grad_glob_rotmats', C.c_void_p), ('grad_rel_rotmats', C.c_void_p),
+        ('grad_shape_betas', C.c_void_p), ('grad_trans', C.c_void_p), ('grad_kid_factor', C.c_void_p),
+        ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('hip_stream', C.c_void_p),
+    ]
+
+
+class FitObjectiveArgs(C.Structure):
+    """smplfit_fit_objective_args (include/smplfit.h)."""
+    _fields_ = [
+        ('pose_rotvecs', C.c_void_p), ('glob_rotmats', C.c_void_p), ('rel_rotmats', C.c_void_p),
+        ('shape_betas', C.c_void_p), ('num_betas_given', C.c_int32), ('trans', C.c_void_p),
+        ('kid_factor', C.c_void_p), ('batch', C.c_int32), ('target_vertices', C.c_void_p),
+        ('vertex_weights', C.c_void_p), ('scale', C.c_float), ('target_joints', C.c_void_p),
+        ('joint_weights', C.c_void_p), ('joint_scale', C.c_float), ('loss', C.c_void_p),
         ('grad_pose_rotvecs', C.c_void_p), ('grad_glob_rotmats', C.c_void_p), ('grad_rel_rotmats', C.c_void_p),
         ('grad_shape_betas', C.c_void_p), ('grad_trans', C.c_void_p), ('grad_kid_factor', C.c_void_p),
         ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('hip_stream', C.c_void_p),
@@ -250,6 +265,10 @@ def load():
     lib.smplfit_mesh_objective_workspace_bytes.restype = sz
     lib.smplfit_mesh_objective_f32.argtypes = [vp, C.POINTER(MeshObjectiveArgs)]
     lib.smplfit_mesh_objective_f32.restype = i32
+    lib.smplfit_fit_objective_workspace_bytes.argtypes = [vp, i32]
+    lib.smplfit_fit_objective_workspace_bytes.restype = sz
+    lib.smplfit_fit_objective_f32.argtypes = [vp, C.POINTER(FitObjectiveArgs)]
+    lib.smplfit_fit_objective_f32.restype = i32
     lib.smplfit_transfer_create.argtypes = [i32, i32, _ip, _ip, _fp, i32, C.POINTER(vp)]
     lib.smplfit_transfer_create.restype = i32
     lib.smplfit_transfer_destroy.argtypes = [vp]
@@ -385,6 +404,9 @@ class Handle:
 
     def mesh_objective_workspace_bytes(self, batch: int) -> int:
         return int(load().smplfit_mesh_objective_workspace_bytes(self._h, int(batch)))
+
+    def fit_objective_workspace_bytes(self, batch: int) -> int:
+        return int(load().smplfit_fit_objective_workspace_bytes(self._h, int(batch)))
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h.value:

@@ -9,6 +9,8 @@
 //                     and the target (the vertex and its cotangent stay in registers), plus the instance's loss
 //   k_bwd_reduce      split-K over workgroups: [dfeat | dshape] (B, P + S) = dv_posed (B, 3 Vp) . [posedirs | shapedirs]^T,
 //                     partial rows per K chunk; k_bwd_combine adds the chunks in chunk order
+//   k_obj_joint       lane = instance, smplfit_fit_objective_f32 only: the joint term of the objective from the posed
+//                     pass's joints, its (B, J, 3) cotangent for k_bwd_joint, the instance's joint loss added to loss[b]
 //   k_bwd_joint       lane = instance: sf::forward_joint_backward (reverse FK chain, J_shapedirs, Rodrigues)
 // No float atomics: every sum has a fixed order, the results are bitwise run-to-run deterministic.
 
@@ -246,6 +248,62 @@ __global__ __launch_bounds__(256) void k_bwd_combine(BwdWorkspace bw, int B, int
   float s = 0.f;
   for (int z = 0; z < nsplit; ++z) s += bw.part[(size_t)z * n + e];
   bw.dfeat[e] = s;
+}
+
+// The joint term of smplfit_fit_objective_f32 (k_obj_joint)
+struct ObjJointArgs {
+  const float* rjoints;  // (B, J, 3) joints of the posed pass, without trans (ws.rjoints)
+  const float* trans;    // (B, 3) or NULL
+  const float* target;   // (B, J, 3)
+  const float* jw;       // (B, J) or NULL
+  float scale;
+  float* gjoints;        // out (B, J, 3): the joint cotangent k_bwd_joint reads
+  float* loss;           // (B): written by k_obj_vertex earlier on the stream; the joint loss is added
+};
+
+constexpr int kObjJointChunk = 16;  // joints per LDS stage of k_obj_joint
+
+// grid ceil(B / 64), block 64: one lane per instance (the grid of k_bwd_joint).  The 64 instances of a block own one
+// contiguous slab of every (B, J, 3) array.  It moves in stages of kObjJointChunk joints: consecutive lanes read and
+// write consecutive floats of an instance's run (192 B) into LDS rows of odd stride, then lane r walks row r without
+// bank conflicts.  p = joint + trans is formed on the way in (the forward's own single addition), the cotangent
+// replaces p in place and leaves by the same pattern.  The loss terms of an instance are added in joint order in one
+// register; no cross-lane sum, no atomics.
+__global__ __launch_bounds__(64) void k_obj_joint(ObjJointArgs a, int B, int J) {
+  constexpr int JC = kObjJointChunk, W = 3 * JC + 1, WU = JC + 1;
+  __shared__ float sp[64 * W];   // joints, then their cotangents
+  __shared__ float sq[64 * W];   // target joints
+  __shared__ float su[64 * WU];  // scale * weight
+  const int lane = threadIdx.x, b0 = blockIdx.x * 64, nrow = min(64, B - b0);
+  float lsum = 0.f;
+  for (int j0 = 0; j0 < J; j0 += JC) {
+    const int nj = min(JC, J - j0), n3 = nj * 3;
+    for (int e = lane; e < nrow * n3; e += 64) {
+      const int r = e / n3, k = e - r * n3;
+      const size_t o = ((size_t)(b0 + r) * J + j0) * 3 + k;
+      sp[r * W + k] = a.rjoints[o] + (a.trans ? a.trans[(size_t)(b0 + r) * 3 + k % 3] : 0.f);
+      sq[r * W + k] = a.target[o];
+    }
+    for (int e = lane; e < nrow * nj; e += 64) {
+      const int r = e / nj, k = e - r * nj;
+      su[r * WU + k] = a.jw ? a.scale * a.jw[(size_t)(b0 + r) * J + j0 + k] : a.scale;
+    }
+    __syncthreads();
+    if (lane < nrow)
+      for (int k = 0; k < nj; ++k) {
+        float* p = sp + lane * W + k * 3;
+        float g[3];
+        lsum += sf::mesh_objective_vertex(p, sq + lane * W + k * 3, su[lane * WU + k], g);
+        p[0] = g[0], p[1] = g[1], p[2] = g[2];
+      }
+    __syncthreads();
+    for (int e = lane; e < nrow * n3; e += 64) {
+      const int r = e / n3, k = e - r * n3;
+      a.gjoints[((size_t)(b0 + r) * J + j0) * 3 + k] = sp[r * W + k];
+    }
+    __syncthreads();
+  }
+  if (lane < nrow) a.loss[b0 + lane] += lsum;
 }
 
 struct JointBwdArgs {

@@ -2663,27 +2663,51 @@ size_t smplfit_mesh_objective_workspace_bytes(const smplfit_handle* h, int batch
   return smplfit_forward_backward_workspace_bytes(h, batch);
 }
 
-int smplfit_mesh_objective_f32(const smplfit_handle* h, const smplfit_mesh_objective_args* a) {
-  const char* who = "smplfit_mesh_objective_f32";
-  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
-  if (!h) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null handle");
+// the backward's workspace, then the (B, J, 3) joint cotangent of k_obj_joint
+size_t fit_objective_carve(const smplfit_handle* h, int B, char* base, Workspace* ws, BwdWorkspace* bw, float** gjoints) {
+  const size_t off = align_up(forward_backward_carve(h, B, base, ws, bw), 256);
+  *gjoints = base ? (float*)(base + off) : nullptr;
+  return align_up(off + (size_t)B * h->t.J * 3 * 4, 256);
+}
+
+size_t smplfit_fit_objective_workspace_bytes(const smplfit_handle* h, int batch) {
+  if (!h || batch <= 0) return 0;
+  Workspace ws;
+  BwdWorkspace bw;
+  float* gj;
+  return fit_objective_carve(h, batch, nullptr, &ws, &bw, &gj);
+}
+
+// Both objective entry points: `a` carries the fields of either struct; `joints` = the call is
+// smplfit_fit_objective_f32 (its own workspace size; the joint term runs when target_joints is given).
+static int objective_impl(const smplfit_handle* h, const smplfit_fit_objective_args* a, bool joints) {
+  const std::string who = joints ? "smplfit_fit_objective_f32" : "smplfit_mesh_objective_f32";
+  if (!h) return fail(SMPLFIT_ERR_BAD_ARG, who + ": null handle");
   if (!h->has_device) return fail(SMPLFIT_ERR_HIP, "handle was created host-only (no device)");
   const int B = a->batch;
   if (B <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "batch must be positive");
   if (!a->workspace || ((uintptr_t)a->workspace & 255))
     return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
-  if (a->workspace_bytes < smplfit_mesh_objective_workspace_bytes(h, B))
+  if (joints) {
+    if (a->workspace_bytes < smplfit_fit_objective_workspace_bytes(h, B))
+      return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (smplfit_fit_objective_workspace_bytes)");
+  } else if (a->workspace_bytes < smplfit_mesh_objective_workspace_bytes(h, B)) {
     return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (smplfit_mesh_objective_workspace_bytes)");
+  }
   const DevModel& d = h->d;
-  if (int rc = check_forward_inputs(who, d, a->pose_rotvecs, a->glob_rotmats, a->rel_rotmats, a->shape_betas,
+  if (int rc = check_forward_inputs(who.c_str(), d, a->pose_rotvecs, a->glob_rotmats, a->rel_rotmats, a->shape_betas,
                                     a->num_betas_given, a->kid_factor))
     return rc;
-  if (!a->target_vertices) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": target_vertices is required");
-  if (!a->loss) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": loss output is required");
+  if (!a->target_vertices) return fail(SMPLFIT_ERR_BAD_ARG, who + ": target_vertices is required");
+  if (a->joint_weights && !a->target_joints)
+    return fail(SMPLFIT_ERR_BAD_ARG, who + ": joint_weights without target_joints");
+  if (!a->loss) return fail(SMPLFIT_ERR_BAD_ARG, who + ": loss output is required");
   hipStream_t st = (hipStream_t)a->hip_stream;
   Workspace ws;
   BwdWorkspace bw;
-  forward_backward_carve(h, B, (char*)a->workspace, &ws, &bw);
+  float* gjoints = nullptr;
+  if (joints) fit_objective_carve(h, B, (char*)a->workspace, &ws, &bw, &gjoints);
+  else forward_backward_carve(h, B, (char*)a->workspace, &ws, &bw);
   const int nb = a->shape_betas ? std::max(0, a->num_betas_given) : 0;
   // the posed pass of the backward: the joint block (G | t) without trans (k_obj_vertex adds it) and v_posed
   ForwardArgs fa{};
@@ -2702,6 +2726,12 @@ int smplfit_mesh_objective_f32(const smplfit_handle* h, const smplfit_mesh_objec
                      a->shape_betas, a->kid_factor, oa);
   launch_bwd_reduce(d, bw, B, st);
   JointBwdArgs ja{};
+  if (a->target_joints) {
+    // the joint term: cotangent to the workspace, loss added behind k_obj_vertex's (stream order)
+    const ObjJointArgs oj{ws.rjoints, a->trans, a->target_joints, a->joint_weights, a->joint_scale, gjoints, a->loss};
+    hipLaunchKernelGGL(k_obj_joint, dim3((B + 63) / 64), dim3(64), 0, st, oj, B, d.J);
+    ja.gjoints = gjoints;
+  }
   ja.pose = a->pose_rotvecs;
   ja.glob = a->glob_rotmats;
   ja.rel = a->rel_rotmats;
@@ -2717,6 +2747,25 @@ int smplfit_mesh_objective_f32(const smplfit_handle* h, const smplfit_mesh_objec
   ja.g_kid = a->grad_kid_factor;
   hipLaunchKernelGGL(k_bwd_joint, dim3((B + 63) / 64), dim3(64), 0, st, d, bw, ja, B);
   return post_launch_check();
+}
+
+int smplfit_mesh_objective_f32(const smplfit_handle* h, const smplfit_mesh_objective_args* a) {
+  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_mesh_objective_f32: null arguments");
+  smplfit_fit_objective_args f{};
+  f.pose_rotvecs = a->pose_rotvecs; f.glob_rotmats = a->glob_rotmats; f.rel_rotmats = a->rel_rotmats;
+  f.shape_betas = a->shape_betas; f.num_betas_given = a->num_betas_given; f.trans = a->trans;
+  f.kid_factor = a->kid_factor; f.batch = a->batch; f.target_vertices = a->target_vertices;
+  f.vertex_weights = a->vertex_weights; f.scale = a->scale; f.loss = a->loss;
+  f.grad_pose_rotvecs = a->grad_pose_rotvecs; f.grad_glob_rotmats = a->grad_glob_rotmats;
+  f.grad_rel_rotmats = a->grad_rel_rotmats; f.grad_shape_betas = a->grad_shape_betas; f.grad_trans = a->grad_trans;
+  f.grad_kid_factor = a->grad_kid_factor;
+  f.workspace = a->workspace; f.workspace_bytes = a->workspace_bytes; f.hip_stream = a->hip_stream;
+  return objective_impl(h, &f, false);
+}
+
+int smplfit_fit_objective_f32(const smplfit_handle* h, const smplfit_fit_objective_args* a) {
+  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_objective_f32: null arguments");
+  return objective_impl(h, a, true);
 }
 
 int smplfit_shape_solve_f32(const smplfit_handle* h, const float* glob_rotmats,

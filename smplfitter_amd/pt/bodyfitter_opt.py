@@ -5,13 +5,19 @@ The closed-form ``BodyFitter.fit`` gives the start.  With ``refine_steps > 0`` t
 global rotations (6D form: the first two columns of each matrix, orthonormalised by Gram-Schmidt), the betas, the
 translation and the kid factor, minimising the mean vertex (and joint) distance plus a ridge on the betas from the third
 on.  The learning rate rises linearly over the first ``warmup_ratio`` of the steps, then follows a half cosine to zero.
-Every step runs ``BodyModel.forward`` and its HIP backward (``smplfit_forward_backward_f32``).  The result is returned
-as relative rotation vectors, as the closed-form fit returns it.
+The result is returned as relative rotation vectors, as the closed-form fit returns it.
+
+The optimizer, the 6D map and the beta ridge run in PyTorch, on a few hundred floats per instance.  The vertex- and
+joint-sized work of a step is one native call (``smplfit_fit_objective_f32``, or ``smplfit_mesh_objective_f32`` without
+target joints, through ``BodyModel._objective_direct``): the loss and its gradient with respect to the global rotation
+matrices, betas, translation and kid factor, with neither the mesh nor its cotangent written to memory.
+``fused_objective=False`` runs the same loop through ``BodyModel.forward`` and its HIP backward
+(``smplfit_forward_backward_f32``) with the loss in PyTorch operators (the yardstick of the tests and of
+tools/bench_fitter_opt.py).
 """
 
 from __future__ import annotations
 
-import math
 from typing import Optional
 
 import torch
@@ -36,12 +42,13 @@ def _six(rot: torch.Tensor) -> torch.Tensor:
 
 
 class BodyFitterOpt(nn.Module):
-    """Closed-form fit, optionally refined by Adam through the differentiable ``BodyModel.forward``."""
+    """Closed-form fit, optionally refined by Adam on the mean vertex (and joint) distance."""
 
-    def __init__(self, body_model, enable_kid: bool = False):
+    def __init__(self, body_model, enable_kid: bool = False, fused_objective: bool = True):
         super().__init__()
         self.body_model = body_model
         self.enable_kid = enable_kid
+        self.fused_objective = fused_objective
         self.fitter = BodyFitter(body_model, enable_kid=enable_kid)
 
     def fit(
@@ -62,29 +69,27 @@ class BodyFitterOpt(nn.Module):
         warmup_ratio: float = 0.5,
     ) -> dict[str, torch.Tensor]:
         """``pose_rotvecs``, ``shape_betas``, ``trans`` (and ``kid_factor`` with ``enable_kid``).  ``refine_steps=0``
-        returns the closed-form fit unchanged; otherwise the fit runs without its final rotation adjustment and is
-        refined (module docstring)."""
+        (and an empty batch) returns the closed-form fit unchanged; otherwise the fit runs without its final rotation
+        adjustment and is refined (module docstring).  A refinement while ``torch.compile`` is tracing raises
+        ``NotImplementedError``."""
+        if refine_steps > 0 and torch.compiler.is_compiling():
+            raise NotImplementedError('the refinement (an optimizer loop) cannot be traced; call it outside torch.compile')
         start = self.fitter.fit(
             target_vertices, target_joints=target_joints, vertex_weights=vertex_weights, joint_weights=joint_weights,
             num_iter=num_iter, beta_regularizer=beta_regularizer, beta_regularizer2=beta_regularizer2,
             share_beta=share_beta, final_adjust_rots=final_adjust_rots if refine_steps == 0 else False,
             scale_target=scale_target, scale_fit=scale_fit, requested_keys=['pose_rotvecs', 'shape_betas', 'trans'])
-        if refine_steps == 0:
+        if refine_steps == 0 or target_vertices.shape[0] == 0:
             return start
         return self._refine(target_vertices, target_joints, vertex_weights, joint_weights, start, beta_regularizer,
                             refine_steps, refine_lr, warmup_ratio)
 
-    def _lr(self, step: int, steps: int, lr: float, warmup_ratio: float) -> float:
-        warm = int(steps * warmup_ratio)
-        if step < warm:
-            return lr * (step + 1) / warm
-        frac = (step - warm) / max(1, steps - warm)
-        return lr * 0.5 * (1.0 + math.cos(math.pi * frac))
-
     def _refine(self, target_vertices, target_joints, vertex_weights, joint_weights, start, beta_regularizer, steps,
                 lr, warmup_ratio):
+        from .bodyflipper_opt import refine_lr_at  # (that module imports this one's 6D helpers)
+
         m = self.body_model
-        J, parents = m.num_joints, m.kintree_parents
+        J, V, parents = m.num_joints, m.num_vertices, m.kintree_parents
         B = target_vertices.shape[0]
         with torch.no_grad():
             rel = rotvec2mat(start['pose_rotvecs'].reshape(B, J, 3))
@@ -106,17 +111,33 @@ class BodyFitterOpt(nn.Module):
             d = torch.linalg.norm(pred - target, dim=-1)
             return torch.mean(d if weights is None else weights * d)
 
+        ridge = beta_regularizer > 0 and betas.shape[1] > 2
         for step in range(steps):
             for group in opt.param_groups:
-                group['lr'] = self._lr(step, steps, lr, warmup_ratio)
+                group['lr'] = refine_lr_at(step, steps, lr, warmup_ratio)
             opt.zero_grad()
-            out = m(glob_rotmats=_gram_schmidt(six), shape_betas=betas, trans=trans, kid_factor=kid)
-            loss = mean_dist(out['vertices'], target_vertices, vertex_weights)
-            if target_joints is not None:
-                loss = loss + mean_dist(out['joints'], target_joints, joint_weights)
-            if beta_regularizer > 0 and betas.shape[1] > 2:
-                loss = loss + beta_regularizer * torch.mean(betas[:, 2:] ** 2)
-            loss.backward()
+            rot = _gram_schmidt(six)
+            if self.fused_objective:
+                # the means over all B * V vertex and B * J joint distances
+                _, g = m._objective_direct(
+                    target_vertices, glob_rotmats=rot.detach(), shape_betas=betas, trans=trans, kid_factor=kid,
+                    vertex_weights=vertex_weights, scale=1.0 / (B * V), target_joints=target_joints,
+                    joint_weights=joint_weights, joint_scale=1.0 / (B * J))
+                rot.backward(g[5])
+                betas.grad, trans.grad = g[1], g[2]
+                if kid is not None:
+                    kid.grad = g[3]
+                if ridge:
+                    with torch.no_grad():  # d/dbetas of beta_regularizer * mean(betas[:, 2:] ** 2)
+                        betas.grad[:, 2:] += (2.0 * beta_regularizer / betas[:, 2:].numel()) * betas[:, 2:]
+            else:
+                out = m(glob_rotmats=rot, shape_betas=betas, trans=trans, kid_factor=kid)
+                loss = mean_dist(out['vertices'], target_vertices, vertex_weights)
+                if target_joints is not None:
+                    loss = loss + mean_dist(out['joints'], target_joints, joint_weights)
+                if ridge:
+                    loss = loss + beta_regularizer * torch.mean(betas[:, 2:] ** 2)
+                loss.backward()
             opt.step()
         with torch.no_grad():
             glob = _gram_schmidt(six)

@@ -245,12 +245,15 @@ class BodyModel(nn.Module):
         return out
 
     def _objective_direct(self, target_vertices, pose_rotvecs=None, shape_betas=None, trans=None, kid_factor=None,
-                          rel_rotmats=None, glob_rotmats=None, vertex_weights=None, scale: float = 1.0):
+                          rel_rotmats=None, glob_rotmats=None, vertex_weights=None, scale: float = 1.0,
+                          target_joints=None, joint_weights=None, joint_scale: float = 1.0):
         """Value and gradient of the mesh-distance objective in one C-ABI call (``smplfit_mesh_objective_f32``):
         ``loss`` (B) with ``loss[b] = scale * sum_v w_bv |forward(inputs).vertices_bv - target_bv|``, and the gradients
         of ``loss.sum()`` with respect to the six inputs, prepared and returned as ``_backward_direct`` does (a
         broadcast ``trans`` / ``kid_factor`` is expanded on the way in and its gradient summed on the way out).  The
-        vertices and their cotangent are never written to memory.  Returns ``(loss, grads)``."""
+        vertices and their cotangent are never written to memory.  With ``target_joints`` (B, J, 3) the call is
+        ``smplfit_fit_objective_f32`` and the loss gains ``joint_scale * sum_j u_bj |forward(inputs).joints_bj -
+        target_joints_bj|``, ``u`` = ``joint_weights`` (B, J) or 1.  Returns ``(loss, grads)``."""
         device = self.v_template.device
         J, V = self.num_joints, self.num_vertices
         batch = target_vertices.shape[0]
@@ -273,6 +276,13 @@ class BodyModel(nn.Module):
         vw = prep(vertex_weights)
         if vw is not None and tuple(vw.shape) != (batch, V):
             raise ValueError(f'vertex_weights must have shape (batch, {V}), got {tuple(vw.shape)}')
+        tj, jw = prep(target_joints), prep(joint_weights)
+        if tj is not None and tuple(tj.shape) != (batch, J, 3):
+            raise ValueError(f'target_joints must have shape (batch, {J}, 3), got {tuple(tj.shape)}')
+        if jw is not None and tuple(jw.shape) != (batch, J):
+            raise ValueError(f'joint_weights must have shape (batch, {J}), got {tuple(jw.shape)}')
+        if jw is not None and tj is None:
+            raise ValueError('joint_weights without target_joints')
         new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=device)  # noqa: E731
         g_pose = new(batch, J * 3) if pose is not None else None
         g_rel = new(batch, J, 3, 3) if rel is not None else None
@@ -281,18 +291,25 @@ class BodyModel(nn.Module):
         g_trans = new(batch, 3) if trans is not None else None
         g_kid = new(batch) if isinstance(kid_factor, torch.Tensor) else None
         h = self._native(device, kid=kid is not None)
-        ws = torch.empty(h.mesh_objective_workspace_bytes(batch), dtype=torch.uint8, device=device)
+        nws = h.mesh_objective_workspace_bytes(batch) if tj is None else h.fit_objective_workspace_bytes(batch)
+        ws = torch.empty(nws, dtype=torch.uint8, device=device)
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
             p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            args = _lib.MeshObjectiveArgs(
+            common = dict(
                 pose_rotvecs=p(pose), glob_rotmats=p(glob), rel_rotmats=p(rel), shape_betas=p(betas),
                 num_betas_given=nb, trans=p(tr), kid_factor=p(kid), batch=batch, target_vertices=p(target),
                 vertex_weights=p(vw), scale=float(scale), loss=p(loss), grad_pose_rotvecs=p(g_pose),
                 grad_glob_rotmats=p(g_glob), grad_rel_rotmats=p(g_rel), grad_shape_betas=p(g_betas),
                 grad_trans=p(g_trans), grad_kid_factor=p(g_kid), workspace=ws.data_ptr(),
                 workspace_bytes=ws.numel(), hip_stream=stream)
-            _lib.check(_lib.load().smplfit_mesh_objective_f32(h.ptr, C.byref(args)))
+            if tj is None:
+                args = _lib.MeshObjectiveArgs(**common)
+                _lib.check(_lib.load().smplfit_mesh_objective_f32(h.ptr, C.byref(args)))
+            else:
+                args = _lib.FitObjectiveArgs(target_joints=p(tj), joint_weights=p(jw), joint_scale=float(joint_scale),
+                                             **common)
+                _lib.check(_lib.load().smplfit_fit_objective_f32(h.ptr, C.byref(args)))
         return loss, self._grad_outputs(ins, zeros, batch, nb, g_pose, g_betas, g_trans, g_kid, g_rel, g_glob)
 
     def _forward_direct(self, pose_rotvecs=None, shape_betas=None, trans=None, kid_factor=None,
