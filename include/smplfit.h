@@ -551,6 +551,48 @@ typedef struct smplfit_flip_args {
 } smplfit_flip_args;
 int smplfit_flip_f32(const smplfit_flip_plan* plan, const smplfit_flip_args* args);
 
+/*
+ * HandReplacer.replace_hand (pt/handreplacer.py:61-74) as ONE call: the vertex-weighted fit of the model to the input
+ * meshes (no target joints, no warm start), the fitted relative rotations of a joint range overwritten with constant
+ * replacement rotations, the forward of the edited parameters, and the blend with the input mesh,
+ *   out[b,v] = in[b,v] + (new[b,v] - in[b,v]) * mix[v],
+ * exactly in[b,v] where mix[v] == 0.  The weights of the fit are ONE (V) vector for the whole batch, read as such: no
+ * (B,V) weight tensor exists.  The fit runs on the route its model and call take (a weighted fit with more than 10
+ * betas: the wave-per-instance kernels); the forward runs on the batch-major kernels from the relative rotation
+ * matrices, and the new mesh is blended where it is written: no (B,V,3) intermediate.  Nothing synchronises.
+ *   smplfit_replace_hands_plan_create(h, fit_weights, mix_weights, num_vertices, first_joint, num_joints, rotvecs,
+ *   num_rotvec_values, &plan): `h` = handle WITHOUT the kid unknown; fit_weights / mix_weights (num_vertices = V) and
+ *   rotvecs (num_rotvec_values = 3 num_joints: the rotation vectors of the joints [first_joint, first_joint +
+ *   num_joints)) are HOST pointers.  SMPLFIT_ERR_BAD_ARG for a length that does not match or a range outside [0, J);
+ *   SMPLFIT_ERR_UNSUPPORTED where the batch-major kernels do not take the model's forward, for a kid handle and for a
+ *   model without its joint regressor — the caller then runs smplfit_fit_f32 + smplfit_forward_f32 and blends.  The plan
+ *   borrows the handle (keep it alive) and owns device copies of the three vectors.
+ *   smplfit_replace_hands_f32: vertices (B,V,3) in, out_vertices (B,V,3) out (may be the same buffer); the fit options
+ *   of smplfit_fit_f32 (the reference passes num_iter = 3, beta_regularizer = 0, final_adjust_rots = 0);
+ *   out_pose_rotvecs / out_shape_betas / out_trans: the EDITED parameters, each may be NULL.
+ *   Workspace: smplfit_replace_hands_workspace_bytes(plan, batch).  Zero-initialise the struct.
+ */
+typedef struct smplfit_replace_hands_plan smplfit_replace_hands_plan;
+int smplfit_replace_hands_plan_create(const smplfit_handle* h, const float* fit_weights, const float* mix_weights,
+                                      int32_t num_vertices, int32_t first_joint, int32_t num_joints, const float* rotvecs,
+                                      int32_t num_rotvec_values, smplfit_replace_hands_plan** plan);
+void smplfit_replace_hands_plan_destroy(smplfit_replace_hands_plan* plan);
+size_t smplfit_replace_hands_workspace_bytes(const smplfit_replace_hands_plan* plan, int batch);
+typedef struct smplfit_replace_hands_args {
+  const float* vertices;             /* (B,V,3) */
+  int32_t batch, num_iter;
+  float beta_regularizer, beta_regularizer2;
+  int32_t final_adjust_rots;
+  float* out_vertices;               /* (B,V,3) */
+  float* out_pose_rotvecs;           /* (B,3J) or NULL */
+  float* out_shape_betas;            /* (B,S) or NULL */
+  float* out_trans;                  /* (B,3) or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  void* hip_stream;
+} smplfit_replace_hands_args;
+int smplfit_replace_hands_f32(const smplfit_replace_hands_plan* plan, const smplfit_replace_hands_args* args);
+
 /* Re-reads the SMPLFIT_* tuning variables (INTEGRATION.md lists them).  They are read once, at first use; tests and
  * the A/B tools that switch kernel paths inside one process call this after changing the environment.  Not to be
  * called while other threads are inside the library. */

@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = [
     'smplfit_abi_version', 'smplfit_forward_backward_workspace_bytes', 'smplfit_forward_backward_f32',
     'smplfit_mesh_objective_workspace_bytes', 'smplfit_mesh_objective_f32',
     'smplfit_fit_objective_workspace_bytes', 'smplfit_fit_objective_f32',
+    'smplfit_replace_hands_plan_create', 'smplfit_replace_hands_plan_destroy',
+    'smplfit_replace_hands_workspace_bytes', 'smplfit_replace_hands_f32',
 ]  # fmt: skip
 
 _fp = C.POINTER(C.c_float)
@@ -164,6 +166,16 @@ class FlipArgs(C.Structure):
         ('out_trans', C.c_void_p), ('out_kid_factor', C.c_void_p), ('out_orientations', C.c_void_p),
         ('out_relative_orientations', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
         ('hip_stream', C.c_void_p),
+    ]
+
+
+class ReplaceHandsArgs(C.Structure):
+    """smplfit_replace_hands_args (include/smplfit.h)."""
+    _fields_ = [
+        ('vertices', C.c_void_p), ('batch', C.c_int32), ('num_iter', C.c_int32), ('beta_regularizer', C.c_float),
+        ('beta_regularizer2', C.c_float), ('final_adjust_rots', C.c_int32), ('out_vertices', C.c_void_p),
+        ('out_pose_rotvecs', C.c_void_p), ('out_shape_betas', C.c_void_p), ('out_trans', C.c_void_p),
+        ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('hip_stream', C.c_void_p),
     ]
 
 
@@ -291,6 +303,15 @@ def load():
     lib.smplfit_flip_workspace_bytes.restype = sz
     lib.smplfit_flip_f32.argtypes = [vp, C.POINTER(FlipArgs)]
     lib.smplfit_flip_f32.restype = i32
+    lib.smplfit_replace_hands_plan_create.argtypes = [vp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32,
+                                                      C.POINTER(vp)]
+    lib.smplfit_replace_hands_plan_create.restype = i32
+    lib.smplfit_replace_hands_plan_destroy.argtypes = [vp]
+    lib.smplfit_replace_hands_plan_destroy.restype = None
+    lib.smplfit_replace_hands_workspace_bytes.argtypes = [vp, i32]
+    lib.smplfit_replace_hands_workspace_bytes.restype = sz
+    lib.smplfit_replace_hands_f32.argtypes = [vp, C.POINTER(ReplaceHandsArgs)]
+    lib.smplfit_replace_hands_f32.restype = i32
     lib.smplfit_reload_options.argtypes = []
     lib.smplfit_reload_options.restype = i32
     if os.environ.get('SMPLFIT_LIB') and not hasattr(lib, 'smplfit_abi_version'):
@@ -511,6 +532,43 @@ class FlipPlan:
     def close(self):
         if getattr(self, '_p', None) is not None and self._p.value:
             load().smplfit_flip_plan_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ReplaceHandsPlan:
+    """Owns a ``smplfit_replace_hands_plan*`` and keeps the handle it borrows alive: the (V) fit weights, the (V) mix
+    weights and the rotation vectors written over the joints ``[first_joint, first_joint + num_joints)``.  Raises
+    ``ValueError`` for vectors of the wrong length or a joint range outside the model, ``NotImplementedError`` when the
+    fused call does not apply to the model."""
+
+    def __init__(self, h: Handle, fit_weights, mix_weights, first_joint: int, num_joints: int, rotvecs):
+        fw = np.ascontiguousarray(fit_weights, dtype=np.float32).reshape(-1)
+        mw = np.ascontiguousarray(mix_weights, dtype=np.float32).reshape(-1)
+        rv = np.ascontiguousarray(rotvecs, dtype=np.float32).reshape(-1)
+        if fw.shape != mw.shape:
+            raise ValueError('ReplaceHandsPlan: fit_weights and mix_weights must have one length')
+        self._keep = (h,)
+        self._p = C.c_void_p()
+        check(load().smplfit_replace_hands_plan_create(
+            h.ptr, fw.ctypes.data_as(_fp), mw.ctypes.data_as(_fp), fw.shape[0], int(first_joint), int(num_joints),
+            rv.ctypes.data_as(_fp), rv.shape[0], C.byref(self._p)))
+
+    @property
+    def ptr(self):
+        return self._p
+
+    def workspace_bytes(self, batch: int) -> int:
+        return int(load().smplfit_replace_hands_workspace_bytes(self._p, int(batch)))
+
+    def close(self):
+        if getattr(self, '_p', None) is not None and self._p.value:
+            load().smplfit_replace_hands_plan_destroy(self._p)
             self._p = C.c_void_p()
 
     def __del__(self):

@@ -119,12 +119,37 @@ __global__ __launch_bounds__(256) void k_layout_targets(DevModel m, const float*
 // LBS pass left in the instance-innermost stream (sorted slots) -> (B, V, 3) rows in the caller's vertex order.  The same
 // tile: 64 instances x kSlabV original vertices, rows read at the vertices' sorted slots (256 bytes each), turned in LDS,
 // written as 12 kSlabV contiguous bytes per instance.  grid (ceil(V/kSlabV), Mp/64), block 256.
-__global__ __launch_bounds__(256) void k_unlayout_vertices(DevModel m, const float* __restrict__ vT, float* __restrict__ out, int B) {
+// BLEND (smplfit_replace_hands_f32; <false> is the plain kernel: in / mix unused): the store loop writes
+// out = in + (new - in) * mix[v] instead, the input read at the address the result goes to, so the new mesh never reaches
+// memory as (B, V, 3).  Product and sum are rounded separately, as the reference's two elementwise operations are; where
+// mix[v] == 0 the input is copied (the reference's arithmetic gives in + 0), and a slab whose mix is 0 throughout — for a
+// body most of them — does not read the stream at all (workgroup-uniform, in front of the barrier).  `in` may be `out`:
+// an element is read by the thread that writes it.
+template <bool BLEND>
+__global__ __launch_bounds__(256) void k_unlayout_vertices(DevModel m, const float* __restrict__ vT, float* out, int B,
+                                                           const float* in = nullptr, const float* __restrict__ mix = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float smem[];  // [64][kSlabRow]
   const int slab = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int V = m.V, Vp = m.Vp;
   const int v0 = slab * kSlabV, nf = 3 * min(kSlabV, V - v0);
+  float* dst = out + ((size_t)blk * 64 * V + v0) * 3;
+  constexpr int NL = 64 * kSlabF / 256;
+  if constexpr (BLEND) {
+    bool any = false;
+    for (int vl = 0; 3 * vl < nf; ++vl) any |= mix[v0 + vl] != 0.f;
+    if (!any) {  // the input as it is
+      const float* srcv = in + ((size_t)blk * 64 * V + v0) * 3;
+      if (in != out) {
+#pragma unroll 8
+        for (int i = 0; i < NL; ++i) {
+          const int e = tid + 256 * i, inst = e / kSlabF, f = e - inst * kSlabF;
+          if (f < nf && blk * 64 + inst < B) dst[(size_t)inst * V * 3 + f] = srcv[(size_t)inst * V * 3 + f];
+        }
+      }
+      return;
+    }
+  }
   const float* src = vT + (size_t)blk * 3 * Vp * 64 + lane;
   // all requests of a batch first, then the LDS stores (a load-store loop runs one memory latency after the other)
   constexpr int NR = kSlabF / 4, UB = NR % 12 == 0 ? 12 : 8;
@@ -144,12 +169,17 @@ __global__ __launch_bounds__(256) void k_unlayout_vertices(DevModel m, const flo
     }
   }
   __syncthreads();
-  float* dst = out + ((size_t)blk * 64 * V + v0) * 3;
-  constexpr int NL = 64 * kSlabF / 256;
 #pragma unroll 8
   for (int i = 0; i < NL; ++i) {
     const int e = tid + 256 * i, inst = e / kSlabF, f = e - inst * kSlabF;
-    if (f < nf && blk * 64 + inst < B) st_stream<8>(dst + (size_t)inst * V * 3 + f, smem[inst * kSlabRow + f]);
+    if (f < nf && blk * 64 + inst < B) {
+      if constexpr (BLEND) {
+        const float a = in[((size_t)blk * 64 * V + v0) * 3 + (size_t)inst * V * 3 + f], w = mix[v0 + f / 3];
+        dst[(size_t)inst * V * 3 + f] = w == 0.f ? a : __fadd_rn(a, __fmul_rn(__fsub_rn(smem[inst * kSlabRow + f], a), w));
+      } else {
+        st_stream<8>(dst + (size_t)inst * V * 3 + f, smem[inst * kSlabRow + f]);
+      }
+    }
   }
 }
 
@@ -2655,6 +2685,8 @@ __device__ __forceinline__ float sum_rows_split(const float* __restrict__ buf, i
 //                      [cell][NE + 1][Mp] in the layout of the solve stage's record, so k_accum_combine is a sum over
 //                      cells in table order.  grid (Mp/64, ncells / mult), block 64, dynamic LDS accum_w_lds<S>() = 37 KB.
 // ------------------------------------------------------------------------------------------------
+// VW_SHARED: vw is ONE (V) row every instance of the batch reads (smplfit_replace_hands_f32), not (B, V)
+template <bool VW_SHARED = false>
 __global__ __launch_bounds__(256) void k_layout_weights(DevModel m, const float* __restrict__ vw, float* __restrict__ wT,
                                                         int B) {
   __shared__ float tile[64][65];
@@ -2669,7 +2701,7 @@ __global__ __launch_bounds__(256) void k_layout_weights(DevModel m, const float*
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const int inst = wave + 4 * i;
-    x[i] = (v0 + lane < V && blk * 64 + inst < B) ? ld_stream<4>(vw + (size_t)(blk * 64 + inst) * V + v0 + lane) : 0.f;
+    x[i] = (v0 + lane < V && blk * 64 + inst < B) ? (VW_SHARED ? vw[v0 + lane] : ld_stream<4>(vw + (size_t)(blk * 64 + inst) * V + v0 + lane)) : 0.f;
   }
 #pragma unroll
   for (int i = 0; i < 16; ++i) tile[wave + 4 * i][lane] = x[i];
@@ -3257,4 +3289,37 @@ __global__ __launch_bounds__(256) void k_naive_flip(const float* __restrict__ po
     dst[3 * j + 1] = -src[3 * k + 1];
     dst[3 * j + 2] = -src[3 * k + 2];
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// smplfit_replace_hands_f32 (HandReplacer.replace_hand, reference pt/handreplacer.py:48-74).
+//   k_rotvecs_to_mats     once per plan: the n replacement rotation vectors as rotation matrices, by the arithmetic the
+//                         forward's joint stage runs on rotation vectors (sf::rotvec2mat on the device).
+//   k_replace_rotations   the fitted relative rotations of the joints [j0, j0 + n) of every instance overwritten with those
+//                         matrices — the form the forward's joint stage consumes (ForwardArgs::rel), so the edited pose
+//                         never goes through (B, 3J) rotation vectors — and, when pose is given, the same joints of the
+//                         fit's rotation vectors with the replacement vectors.  One element per thread, consecutive
+//                         threads write consecutive floats of an instance's run (9 n / 3 n floats).  grid
+//                         ceil(B 9 n / 256), block 256; j0 + n <= J (checked when the plan is made).
+//   (the blend itself is the BLEND form of k_unlayout_vertices, above)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_rotvecs_to_mats(const float* __restrict__ rv, float* __restrict__ mats, int n) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= n) return;
+  const float r[3] = {rv[3 * k], rv[3 * k + 1], rv[3 * k + 2]};
+  float m[9];
+  sf::rotvec2mat(r, m);
+#pragma unroll
+  for (int e = 0; e < 9; ++e) mats[9 * k + e] = m[e];
+}
+
+__global__ __launch_bounds__(256) void k_replace_rotations(const float* __restrict__ mats, const float* __restrict__ rv,
+                                                           float* __restrict__ rel, float* __restrict__ pose, int B, int J,
+                                                           int j0, int n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t run = (size_t)9 * n;
+  if (i >= (size_t)B * run) return;
+  const size_t b = i / run, e = i - b * run;
+  rel[(b * J + j0) * 9 + e] = mats[e];
+  if (pose && e < (size_t)3 * n) pose[(b * J + j0) * 3 + e] = rv[e];
 }

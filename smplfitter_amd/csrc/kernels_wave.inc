@@ -6,7 +6,8 @@
 // reference: fit() centring bodyfitter.py:355-361; _part_sums :235-280 against default_mesh_tf.
 // dynamic LDS: 4 waves x J x 16 floats + 20 (no static LDS: keeps the dynamic base 16-B aligned).
 // ------------------------------------------------------------------------------------------------
-template <bool WEIGHTED>
+// VW_SHARED: vw is ONE (V) row every instance reads (smplfit_replace_hands_f32), not (B, V)
+template <bool WEIGHTED, bool VW_SHARED = false>
 __global__ __launch_bounds__(256) void k_center_sort_partsum(DevModel m, const float* __restrict__ tv,
                                                              const float* __restrict__ tj,
                                                              const float* __restrict__ vw,
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(256) void k_center_sort_partsum(DevModel m, const f
       const float a[3] = {m.dm[i], m.dm[Vp + i], m.dm[2 * Vp + i]};
       float w = 1.f;
       if (WEIGHTED) {
-        w = vw[(size_t)b * V + o];
+        w = vw[(VW_SHARED ? (size_t)0 : (size_t)b * V) + o];
         vws[i] = w;
       }
       sf::partsum_vertex(t, a, w, WEIGHTED, acc);
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(256) void k_center_sort_partsum(DevModel m, const f
       t0 = tvb[o * 3] - m0;
       t1 = tvb[o * 3 + 1] - m1;
       t2 = tvb[o * 3 + 2] - m2;
-      if (WEIGHTED) w = vw[(size_t)b * V + o];
+      if (WEIGHTED) w = vw[(VW_SHARED ? (size_t)0 : (size_t)b * V) + o];
     }
     st_stream<16>(tvs + i, t0);
     st_stream<16>(tvs + Vp + i, t1);
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void k_center_sort_partsum(DevModel m, const f
 // 1.5 % of the row from L2 in the gather lets TWO workgroups share a CU, so one loads while the other
 // gathers / sums.
 // ------------------------------------------------------------------------------------------------
-template <bool WEIGHTED>
+template <bool WEIGHTED, bool VW_SHARED = false>
 __global__ __launch_bounds__(1024) void k_center_sort_partsum_lds(DevModel m, const float* __restrict__ tv,
                                                                  const float* __restrict__ tj,
                                                                  const float* __restrict__ vw,
@@ -228,7 +229,7 @@ __global__ __launch_bounds__(1024) void k_center_sort_partsum_lds(DevModel m, co
         t0 = at(o * 3) - m0;
         t1 = at(o * 3 + 1) - m1;
         t2 = at(o * 3 + 2) - m2;
-        if (WEIGHTED) w = vw[(size_t)b * V + o];
+        if (WEIGHTED) w = vw[(VW_SHARED ? (size_t)0 : (size_t)b * V) + o];
       }
       st_stream<16>(tvs + i, t0);
       st_stream<16>(tvs + Vp + i, t1);
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(1024) void k_center_sort_partsum_lds(DevModel m, co
       const float a[3] = {m.dm[i], m.dm[Vp + i], m.dm[2 * Vp + i]};
       if (lane < count) {
         const float t[3] = {at(o * 3) - m0, at(o * 3 + 1) - m1, at(o * 3 + 2) - m2};
-        sf::partsum_vertex(t, a, WEIGHTED ? vw[(size_t)b * V + o] : 1.f, WEIGHTED, acc);
+        sf::partsum_vertex(t, a, WEIGHTED ? vw[(VW_SHARED ? (size_t)0 : (size_t)b * V) + o] : 1.f, WEIGHTED, acc);
       }
     }
 #pragma unroll

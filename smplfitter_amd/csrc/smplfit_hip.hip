@@ -162,6 +162,16 @@ struct smplfit_flip_plan {
   int32_t* d_perm = nullptr;  // (J)
 };
 
+// Fused hand replacement plan (smplfit_replace_hands_f32): the constants of HandReplacer on the device.
+struct smplfit_replace_hands_plan {
+  const smplfit_handle* h = nullptr;
+  int j0 = 0, n = 0;          // the joints [j0, j0 + n) are overwritten
+  float* d_fitw = nullptr;    // (V) vertex weights of the fit, one row for the whole batch
+  float* d_mix = nullptr;     // (V) blend weight of the new mesh
+  float* d_rv = nullptr;      // (3 n) replacement rotation vectors
+  float* d_mats = nullptr;    // (n, 9) the same as rotation matrices (k_rotvecs_to_mats)
+};
+
 namespace {
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -532,10 +542,14 @@ void launch_template_partsum_bm(const smplfit_handle* h, const Workspace& ws, in
 
 // Target layout of the batch-major path (k_layout_weights, k_layout_targets): ws.wT, ws.tT and the slab sums in
 // ws.resP (scratch); launch_targets_in finishes them.  -> the slabs
-int launch_layout_bm(const DevModel& d, const float* tv, const float* vw, const Workspace& ws, int B, hipStream_t st) {
-  if (vw)  // vertex weights: their stream first (the template part sums read it)
-    hipLaunchKernelGGL(k_layout_weights, dim3((d.V + 63) / 64 + 1, (int)align_up((size_t)B, 128) / 64), dim3(256), 0, st, d, vw,
-                       ws.wT, B);
+// vw_shared: vw is one (V) row for the whole batch (TargetsIn::vw_shared)
+int launch_layout_bm(const DevModel& d, const float* tv, const float* vw, const Workspace& ws, int B, hipStream_t st,
+                     bool vw_shared = false) {
+  if (vw) {  // vertex weights: their stream first (the template part sums read it)
+    const dim3 grid((d.V + 63) / 64 + 1, (int)align_up((size_t)B, 128) / 64);
+    if (vw_shared) hipLaunchKernelGGL(k_layout_weights<true>, grid, dim3(256), 0, st, d, vw, ws.wT, B);
+    else hipLaunchKernelGGL(k_layout_weights<false>, grid, dim3(256), 0, st, d, vw, ws.wT, B);
+  }
   const int Mp = (int)align_up((size_t)B, 128), nslab = (d.V + kSlabV - 1) / kSlabV;
   hipLaunchKernelGGL(k_layout_targets, dim3(nslab, Mp / 64), dim3(256), (size_t)64 * kSlabRow * 4, st, d, tv, ws.tT,
                      ws.resP, B, Mp);
@@ -700,8 +714,9 @@ void launch_lbs(const DevModel& d, const Workspace& ws, int B, bool weighted, in
 }
 
 // K0 dispatch: LDS-staged form when the (V,3) row fits in LDS, gather form otherwise.
+// vw_shared: vw is one (V) row for the whole batch (TargetsIn::vw_shared)
 void launch_center_sort(const DevModel& d, const float* tv, const float* tj, const float* vw,
-                        const Workspace& ws, int B, hipStream_t st) {
+                        const Workspace& ws, int B, hipStream_t st, bool vw_shared = false) {
   // vertices staged in LDS: the whole row, or — when that leaves room for one workgroup per CU only but
   // an 80 KB slice covers >= 15/16 of the row — the slice that lets two workgroups share the CU
   int VL = d.V;
@@ -715,14 +730,19 @@ void launch_center_sort(const DevModel& d, const float* tv, const float* tj, con
     // set again whenever the current device changes; idempotent, so racing threads are harmless)
     ensure_max_lds(reinterpret_cast<const void*>(&k_center_sort_partsum_lds<true>));
     ensure_max_lds(reinterpret_cast<const void*>(&k_center_sort_partsum_lds<false>));
-    if (vw)
+    if (vw && vw_shared) {
+      ensure_max_lds(reinterpret_cast<const void*>(&k_center_sort_partsum_lds<true, true>));
+      hipLaunchKernelGGL((k_center_sort_partsum_lds<true, true>), dim3(B), dim3(1024), lds_row, st, d, tv, tj, vw, ws, VL);
+    } else if (vw)
       hipLaunchKernelGGL((k_center_sort_partsum_lds<true>), dim3(B), dim3(1024), lds_row, st, d, tv, tj, vw, ws, VL);
     else
       hipLaunchKernelGGL((k_center_sort_partsum_lds<false>), dim3(B), dim3(1024), lds_row, st, d, tv, tj, vw, ws, VL);
     return;
   }
   const size_t lds0 = ((size_t)4 * d.J * sf::kPsum + 20) * 4;
-  if (vw)
+  if (vw && vw_shared)
+    hipLaunchKernelGGL((k_center_sort_partsum<true, true>), dim3(B), dim3(256), lds0, st, d, tv, tj, vw, ws);
+  else if (vw)
     hipLaunchKernelGGL((k_center_sort_partsum<true>), dim3(B), dim3(256), lds0, st, d, tv, tj, vw, ws);
   else
     hipLaunchKernelGGL((k_center_sort_partsum<false>), dim3(B), dim3(256), lds0, st, d, tv, tj, vw, ws);
@@ -1356,6 +1376,7 @@ struct TargetsIn {
   const ConvertSource* source = nullptr; // fused conversion: the third producer of the batch-major streams, instead of tv
   bool template_sums = false;            // (a warm-started fit takes its first part sums against the posed initial model)
   bool regress = false;
+  bool vw_shared = false;                // vw is ONE (V) row every instance reads (smplfit_replace_hands_f32), not (B,V)
 };
 const float* rotation_targets(const Workspace& ws, bool joints) { return joints ? ws.tjc : ws.tjreg; }
 int launch_targets_in(const smplfit_handle* h, const Route& r, const TargetsIn& t, const Workspace& ws, int B, hipStream_t st) {
@@ -1363,7 +1384,7 @@ int launch_targets_in(const smplfit_handle* h, const Route& r, const TargetsIn& 
   if (t.regress && !t.tj && !h->t.has_regressor)
     return fail(SMPLFIT_ERR_BAD_ARG, "target_joints omitted but the model has no J_regressor_post_lbs over its vertices");
   if (!r.bm) {
-    launch_center_sort(d, t.tv, t.tj, t.vw, ws, B, st);
+    launch_center_sort(d, t.tv, t.tj, t.vw, ws, B, st, t.vw_shared);
     if (t.regress && !t.tj) hipLaunchKernelGGL(k_regress_joints, dim3(B), dim3(64), 0, st, d, ws.tvs, ws.tjreg);
     return 0;
   }
@@ -1373,7 +1394,7 @@ int launch_targets_in(const smplfit_handle* h, const Route& r, const TargetsIn& 
     if (int rc = launch_convert_source(*t.source, ws, B, st)) return rc;
     nslab = t.source->plan->nslab;
   } else {
-    nslab = launch_layout_bm(d, t.tv, t.vw_stream, ws, B, st);
+    nslab = launch_layout_bm(d, t.tv, t.vw_stream, ws, B, st, t.vw_shared);
   }
   hipLaunchKernelGGL(k_mean_finish, dim3(Mp / 64), dim3(64 * kMeanWaves), 0, st, d, t.tj, ws.resP, ws, B, Mp, nslab);
   if (t.template_sums) launch_template_partsum_bm(h, ws, B, st, t.vw_stream != nullptr, r.psum_combine);
@@ -1401,11 +1422,20 @@ struct LbsPass {
   const ForwardArgs* shape = nullptr;  // null: at ws.beta / ws.trans; else at the caller's betas / nb / kid / trans, which
                                        // the batch-major path copies there first (launch_posed_pass)
   float* out = nullptr;
+  // kForward to the caller, blended: out = blend_in + (mesh - blend_in) * blend_mix[v] (batch-major only; k_unlayout_vertices<true>)
+  const float* blend_in = nullptr;   // (B,V,3), may be `out`
+  const float* blend_mix = nullptr;  // (V)
 };
 LbsPass part_sums(bool joints, bool weighted, bool keep_mesh, bool mesh_all = false, bool feeds_refine = false) {
   return {Lbs::kPartSums, joints, weighted, keep_mesh, mesh_all, feeds_refine};
 }
 LbsPass mesh_alone(const ForwardArgs* shape, float* out) { return {Lbs::kForward, true, false, false, false, false, shape, out}; }
+LbsPass mesh_blended(const ForwardArgs* shape, float* out, const float* in, const float* mix) {
+  LbsPass p = mesh_alone(shape, out);
+  p.blend_in = in;
+  p.blend_mix = mix;
+  return p;
+}
 int launch_lbs_pass(const smplfit_handle* h, const Route& r, const LbsPass& p, const Workspace& ws, int B, hipStream_t st) {
   const DevModel& d = h->d;
   const int Mp = (int)align_up((size_t)B, 128);
@@ -1413,11 +1443,16 @@ int launch_lbs_pass(const smplfit_handle* h, const Route& r, const LbsPass& p, c
   if (p.form == Lbs::kForward) {
     if (r.bm) {  // forward-only pass over every slot, then the inverse of the target layout
       if (int rc = launch_lbs_fwd_bm(d, share_view(h, sf::kShareLbsAll, B), ws, B, Mp, st)) return rc;
-      if (p.out)
-        hipLaunchKernelGGL(k_unlayout_vertices, dim3((d.V + kSlabV - 1) / kSlabV, Mp / 64), dim3(256), (size_t)64 * kSlabRow * 4, st,
-                           d, ws.vpT, p.out, B);
+      const dim3 grid((d.V + kSlabV - 1) / kSlabV, Mp / 64);
+      if (p.out && p.blend_in)
+        hipLaunchKernelGGL(k_unlayout_vertices<true>, grid, dim3(256), (size_t)64 * kSlabRow * 4, st, d, ws.vpT, p.out, B, p.blend_in,
+                           p.blend_mix);
+      else if (p.out)
+        hipLaunchKernelGGL(k_unlayout_vertices<false>, grid, dim3(256), (size_t)64 * kSlabRow * 4, st, d, ws.vpT, p.out, B,
+                           (const float*)nullptr, (const float*)nullptr);
       return 0;
     }
+    if (p.blend_in) return fail(SMPLFIT_ERR_UNSUPPORTED, "forward LBS pass: the blended output is written on the batch-major path only");
     if (!p.out) return fail(SMPLFIT_ERR_UNSUPPORTED, "forward LBS pass: the mesh stays in the workspace on the batch-major path only");
     if (p.shape) return launch_lbs_any<2>(d, ws, B, false, p.shape->nb, p.shape->betas, p.shape->trans, p.out, st, p.shape->kid);
     return launch_lbs_any<2>(d, ws, B, false, d.S, ws.beta, ws.trans, p.out, st);
@@ -1622,7 +1657,7 @@ int enqueue_solve(const smplfit_handle* h, const Route& r, const Workspace& ws, 
 // of the input model on the batch-major kernels, topology transfer straight into this fit's target stream — instead
 // of being read from target_vertices).
 int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_only, const ConvertSource* source,
-            const Workspace& ws, hipStream_t st, int ph_lo = 0, int ph_hi = 1 << 30) {
+            const Workspace& ws, hipStream_t st, int ph_lo = 0, int ph_hi = 1 << 30, bool vw_shared = false) {
   // PHASES.  The launches of a fit are numbered in phases — 0: the prologue up to the first rotation pass; 1 + 2 it:
   // the vertex block of iteration `it` up to the normal equations; 2 + 2 it: solve, vertices at the solution, next
   // rotation pass; 1 + 2 num_iter: refinement and epilogue — and a call enqueues the phases [ph_lo, ph_hi) only (the
@@ -1648,7 +1683,7 @@ int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_o
                                   o.share_beta != 0, o.rotations_only != 0, warm});
   if (source && !r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "fused conversion: the batch-major path does not apply");
   if (on(0)) {
-    TargetsIn t{a.target_vertices, tj, vw, vw, source, !warm, true};
+    TargetsIn t{a.target_vertices, tj, vw, vw, source, !warm, true, vw_shared};
     if (int rc = launch_targets_in(h, r, t, ws, B, st)) return rc;
   }
   const float* tj_rot = rotation_targets(ws, joints);
@@ -1903,7 +1938,8 @@ smplfit_fit_args chunk_view(const smplfit_fit_args& a, const sf::HostTables& t, 
   return v;
 }
 
-int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const ConvertJob* job) {
+// vw_shared: args->vertex_weights is one (V) row for the whole batch (smplfit_replace_hands_f32)
+int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const ConvertJob* job, bool vw_shared = false) {
   const smplfit_fit_args& a = *args;
   const int batch = a.batch;
   int rc = check_common(h, batch, a.workspace, job ? (size_t)-1 : a.workspace_bytes);
@@ -1939,7 +1975,9 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
       src.kid = job->kid ? job->kid + b0 : nullptr;
       carve(job->plan->in->t, nb, wsbase + own, &src.wsi, true);
     }
-    return run_fit(h, chunk_view(a, h->t, b0, nb), false, job ? &src : nullptr, ws, cs, ph_lo, ph_hi);
+    smplfit_fit_args v = chunk_view(a, h->t, b0, nb);
+    if (vw_shared) v.vertex_weights = a.vertex_weights;  // (every chunk reads the one row)
+    return run_fit(h, v, false, job ? &src : nullptr, ws, cs, ph_lo, ph_hi, vw_shared);
   };
   if (nchunk <= 1) return run_chunk(0, batch, (char*)a.workspace, st, 0, 1 << 30);
   // fork: every chunk is an independent fit with its own workspace slice; chunk 0 stays on the
@@ -2078,6 +2116,24 @@ void free_slot_transfer(smplfit_convert_plan* p) {
 
 // the naively flipped pose of smplfit_flip_f32 at the front of its workspace; the fit's workspace follows
 size_t flip_pose_bytes(const smplfit_handle* h, int batch) { return align_up((size_t)batch * h->t.J * 3 * 4, 256); }
+
+// the per-instance results of the fit inside smplfit_replace_hands_f32 at the front of its workspace: relative
+// rotations (B,J,9), rotation vectors (B,3J), betas (B,S), translation (B,3); the fit's workspace follows
+struct ReplaceFront {
+  float *rel, *pose, *betas, *trans;
+  size_t bytes;
+};
+ReplaceFront replace_front(const smplfit_handle* h, int batch, char* base) {
+  const size_t B = (size_t)batch, J = h->t.J;
+  const size_t sizes[4] = {B * J * 9 * 4, B * J * 3 * 4, B * (size_t)h->t.num_betas() * 4, B * 3 * 4};
+  float* ptr[4];
+  size_t off = 0;
+  for (int k = 0; k < 4; ++k) {
+    ptr[k] = base ? (float*)(base + off) : nullptr;
+    off += align_up(sizes[k], 256);
+  }
+  return {ptr[0], ptr[1], ptr[2], ptr[3], off};
+}
 
 
 }  // namespace
@@ -3045,6 +3101,118 @@ int smplfit_flip_f32(const smplfit_flip_plan* p, const smplfit_flip_args* a) {
   ConvertJob job{&p->conv, a->pose_rotvecs, a->shape_betas, a->trans, a->shape_betas ? a->num_betas_given : 0,
                  a->kid_factor};
   return fit_impl(h, &f, &job);
+}
+
+// ---- fused hand replacement (HandReplacer.replace_hand) ----------------------------------------------
+// The weighted fit on whatever route the model and the call take (the (V) weights read through the shared-row ingest),
+// k_replace_rotations on the fit's relative rotations, the forward steps from those matrices on the batch-major
+// kernels, and the blend in the pass that writes the caller's (B, V, 3).
+int smplfit_replace_hands_plan_create(const smplfit_handle* h, const float* fit_weights, const float* mix_weights,
+                                      int32_t num_vertices, int32_t first_joint, int32_t num_joints, const float* rotvecs,
+                                      int32_t num_rotvec_values, smplfit_replace_hands_plan** plan) {
+  if (!h || !fit_weights || !mix_weights || !rotvecs || !plan)
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_replace_hands_plan_create: null argument");
+  *plan = nullptr;
+  if (num_vertices != h->t.V)
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_replace_hands_plan_create: the weight vectors must hold one value per vertex of the model");
+  if (first_joint < 0 || num_joints < 1 || first_joint > h->t.J - num_joints)
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_replace_hands_plan_create: the joint range must lie in [0, J) and hold a joint");
+  if (num_rotvec_values != 3 * num_joints)
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_replace_hands_plan_create: three rotation-vector values per joint of the range");
+  if (!h->has_device) return fail(SMPLFIT_ERR_HIP, "smplfit_replace_hands_plan_create: the handle needs a device");
+  if (h->t.n_kid || !h->t.has_regressor || !route_of(h, 1, {Entry::kForward}).bm)
+    return fail(SMPLFIT_ERR_UNSUPPORTED,
+                "smplfit_replace_hands_plan_create: the fused call needs a handle without the kid unknown, the model's joint "
+                "regressor and the batch-major kernels for the forward (<= 8 skinning weights per vertex, 10 / 16 betas, "
+                ">= 1024 vertices); use smplfit_fit_f32 + smplfit_forward_f32 and blend");
+  auto* p = new smplfit_replace_hands_plan();
+  p->h = h;
+  p->j0 = first_joint;
+  p->n = num_joints;
+  auto up = [&](const float* src, size_t count, float** dst) {
+    if (hipMalloc((void**)dst, std::max<size_t>(count * 4, 16)) != hipSuccess) return false;
+    return !src || hipMemcpy(*dst, src, count * 4, hipMemcpyHostToDevice) == hipSuccess;
+  };
+  bool ok = up(fit_weights, (size_t)num_vertices, &p->d_fitw) && up(mix_weights, (size_t)num_vertices, &p->d_mix) &&
+            up(rotvecs, (size_t)3 * num_joints, &p->d_rv) && up(nullptr, (size_t)9 * num_joints, &p->d_mats);
+  if (ok) {
+    hipLaunchKernelGGL(k_rotvecs_to_mats, dim3((num_joints + 63) / 64), dim3(64), 0, (hipStream_t) nullptr, p->d_rv, p->d_mats, num_joints);
+    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
+  }
+  if (!ok) {
+    smplfit_replace_hands_plan_destroy(p);
+    return fail(SMPLFIT_ERR_HIP, "smplfit_replace_hands_plan_create: device upload failed");
+  }
+  *plan = p;
+  return SMPLFIT_OK;
+}
+
+void smplfit_replace_hands_plan_destroy(smplfit_replace_hands_plan* p) {
+  if (!p) return;
+  for (float* q : {p->d_fitw, p->d_mix, p->d_rv, p->d_mats})
+    if (q) (void)hipFree(q);
+  delete p;
+}
+
+size_t smplfit_replace_hands_workspace_bytes(const smplfit_replace_hands_plan* p, int batch) {
+  if (!p || batch <= 0) return 0;
+  return replace_front(p->h, batch, nullptr).bytes + chunked_workspace_bytes(p->h->t, batch);
+}
+
+int smplfit_replace_hands_f32(const smplfit_replace_hands_plan* p, const smplfit_replace_hands_args* a) {
+  if (!p || !a) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_replace_hands_f32: null argument");
+  const smplfit_handle* h = p->h;
+  const DevModel& d = h->d;
+  const int B = a->batch;
+  if (!a->vertices || !a->out_vertices) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_replace_hands_f32: vertices and out_vertices are required");
+  if (B <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_replace_hands_f32: batch must be positive");
+  if (a->num_iter < 1) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_replace_hands_f32: num_iter must be >= 1");
+  if (!a->workspace || ((uintptr_t)a->workspace & 255))
+    return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
+  if (a->workspace_bytes < smplfit_replace_hands_workspace_bytes(p, B))
+    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (see smplfit_replace_hands_workspace_bytes)");
+  // the plan was made while the batch-major forward applied; a later smplfit_reload_options may have switched it off
+  const Route rf = route_of(h, B, {Entry::kForward});
+  if (!rf.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "smplfit_replace_hands_f32: the batch-major path is switched off");
+  hipStream_t st = (hipStream_t)a->hip_stream;
+  const ReplaceFront fr = replace_front(h, B, (char*)a->workspace);
+  float* pose = a->out_pose_rotvecs ? a->out_pose_rotvecs : fr.pose;
+  float* betas = a->out_shape_betas ? a->out_shape_betas : fr.betas;
+  float* trans = a->out_trans ? a->out_trans : fr.trans;
+  char* wsbase = (char*)a->workspace + fr.bytes;
+  smplfit_fit_args f{};
+  f.target_vertices = a->vertices;
+  f.vertex_weights = p->d_fitw;
+  f.batch = B;
+  f.num_iter = a->num_iter;
+  f.beta_regularizer = a->beta_regularizer;
+  f.beta_regularizer2 = a->beta_regularizer2;
+  f.final_adjust_rots = a->final_adjust_rots;
+  f.pose_rotvecs = pose;
+  f.shape_betas = betas;
+  f.trans = trans;
+  f.relative_orientations = fr.rel;
+  f.workspace = wsbase;
+  f.workspace_bytes = a->workspace_bytes - fr.bytes;
+  f.hip_stream = a->hip_stream;
+  if (int rc = fit_impl(h, &f, nullptr, true)) return rc;
+  {
+    const size_t total = (size_t)B * 9 * p->n;
+    hipLaunchKernelGGL(k_replace_rotations, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p->d_mats, p->d_rv, fr.rel,
+                       a->out_pose_rotvecs, B, d.J, p->j0, p->n);
+  }
+  // the forward at the edited relative rotations (the fit's chunks have been joined: one pass over the whole batch)
+  Workspace ws;
+  carve(h->t, B, wsbase, &ws);
+  ForwardArgs fa{};
+  fa.rel = fr.rel;
+  fa.betas = betas;
+  fa.nb = d.S - d.jt.n_kid - d.jt.n_pad;
+  fa.trans = trans;
+  fa.joints = ws.rjoints;
+  launch_forward_joint(d, fa, ws, B, st);
+  if (int rc = launch_posed_pass(h, rf, {nullptr, mesh_blended(&fa, a->out_vertices, a->vertices, p->d_mix)}, ws, B, st)) return rc;
+  return post_launch_check();
 }
 
 int smplfit_reload_options(void) {

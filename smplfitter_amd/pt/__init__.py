@@ -1,6 +1,6 @@
 """Drop-in counterpart of ``smplfitter.pt`` for the ``BodyFitter.fit`` hot path on MI355X.
 
-``BodyModel`` / ``BodyFitter`` / ``BodyFitterOpt`` / ``BodyConverter`` / ``BodyFlipper`` / ``BodyFlipperOpt`` keep the reference's names, constructor
+``BodyModel`` / ``BodyFitter`` / ``BodyFitterOpt`` / ``BodyConverter`` / ``BodyFlipper`` / ``BodyFlipperOpt`` / ``HandReplacer`` keep the reference's names, constructor
 arguments, ``forward`` / ``fit`` / ``convert`` / ``flip`` signatures and result keys (reference src/smplfitter/pt/__init__.py).  ``get_cached_fit_fn`` mirrors
 pt/__init__.py:58-132 without ``torch.jit.script`` (a ctypes-backed module is not scriptable).
 """
@@ -18,10 +18,11 @@ from .bodyfitter_opt import BodyFitterOpt
 from .bodyconverter import BodyConverter
 from .bodyflipper import BodyFlipper
 from .bodyflipper_opt import BodyFlipperOpt
+from .handreplacer import HandReplacer
 from . import ops  # noqa: F401  (registers torch.ops.smplfitter_amd.fit / .forward)
 
 __all__ = ['BodyModel', 'BodyFitter', 'BodyFitterOpt', 'BodyConverter', 'BodyFlipper', 'BodyFlipperOpt',
-           'get_cached_body_model', 'get_cached_fit_fn']
+           'HandReplacer', 'get_cached_body_model', 'get_cached_fit_fn']
 
 
 @functools.lru_cache()

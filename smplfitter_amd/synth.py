@@ -36,6 +36,9 @@ SMPLX_PARENTS = (
     + [21, 40, 41, 21, 43, 44, 21, 46, 47, 21, 49, 50, 21, 52, 53]
 )
 
+# SMPL-H: the 22 body joints and the two hands of SMPL-X (no jaw, no eyes): left fingers 22..36, right 37..51.
+SMPLH_PARENTS = SMPL_PARENTS[:22] + [p if p < 22 else p - 3 for p in SMPLX_PARENTS[25:]]
+
 # A plausible T-pose skeleton (metres, y up, +x = body's left).  Not SMPL's actual numbers.
 _BODY_JOINTS = np.array(
     [
@@ -124,8 +127,9 @@ def _dist_to_segments(pts, seg):
 
 
 def make_model_arrays(kind='smpl', seed=0, num_vertices=None, num_betas=10, shuffle=True):
-    """Build the raw arrays of a synthetic SMPL-shaped ('smpl', 24 joints) or SMPL-X-shaped
-    ('smplx', 55 joints) model.  Returns a dict with the reference's on-disk keys.
+    """Build the raw arrays of a synthetic SMPL-shaped ('smpl', 24 joints), SMPL-X-shaped
+    ('smplx', 55 joints) or SMPL-H-shaped ('smplh', 52 joints: the SMPL-X construction without jaw and eyes, on
+    6890 vertices; 'smplh_fat': fat fingers) model.  Returns a dict with the reference's on-disk keys.
 
     'smplx_fat' is the SMPL-X-shaped model with FAT fingers / face parts (3.5 cm instead of 1.2 cm): the
     bone parts' twist about the bone axis is recovered from the vertices' off-axis spread
@@ -155,6 +159,10 @@ def make_model_arrays(kind='smpl', seed=0, num_vertices=None, num_betas=10, shuf
         parents = list(SMPLX_PARENTS)
         joints = _smplx_joints()
         V = 10475 if num_vertices is None else num_vertices
+    elif kind == 'smplh':
+        parents = list(SMPLH_PARENTS)
+        joints = np.delete(_smplx_joints(), [22, 23, 24], axis=0)
+        V = 6890 if num_vertices is None else num_vertices
     else:
         raise ValueError(f'unknown synthetic model kind {kind!r}')
     J = len(parents)
@@ -251,15 +259,21 @@ def make_model_arrays(kind='smpl', seed=0, num_vertices=None, num_betas=10, shuf
     )
 
 
-def write_model_files(root, kind='smpl', seed=0, num_vertices=None):
-    """Write ``<root>/<kind>/<official file name>`` (+ ``kid_template.npy``); returns the dir.
+def write_model_files(root, kind='smpl', seed=0, num_vertices=None, dirname=None):
+    """Write ``<root>/<dirname or kind>/<official file name>`` (+ ``kid_template.npy``); returns the dir.
 
     File names follow the reference loader (src/smplfitter/common.py:266-283)."""
     arrs = make_model_arrays(kind, seed, num_vertices)
     kid = arrs.pop('kid_template')
-    d = osp.join(root, kind)  # 'smplx_fat' / 'smpl_b16' live in their own directory, same official file name
+    d = osp.join(root, dirname or kind)  # 'smplx_fat' / 'smpl_b16' live in their own directory, same official file name
     os.makedirs(d, exist_ok=True)
-    if not kind.startswith('smplx'):
+    if kind.startswith('smplh'):  # the 'smplh16' layout: <dir>/neutral/model.npz
+        os.makedirs(osp.join(d, 'neutral'), exist_ok=True)
+        path = osp.join(d, 'neutral', 'model.npz')
+        tmp = path + f'.tmp{os.getpid()}.npz'
+        np.savez(tmp, **arrs)
+        os.replace(tmp, path)
+    elif not kind.startswith('smplx'):
         path = osp.join(d, 'basicmodel_neutral_lbs_10_207_0_v1.1.0.pkl')
         tmp = path + f'.tmp{os.getpid()}'
         with open(tmp, 'wb') as f:
@@ -287,6 +301,8 @@ def ensure_model_root(root=None, kinds=('smpl',), seed=0):
         fn = (
             'SMPLX_NEUTRAL.npz' if kind.startswith('smplx') else 'basicmodel_neutral_lbs_10_207_0_v1.1.0.pkl'
         )
+        if kind.startswith('smplh'):
+            fn = osp.join('neutral', 'model.npz')
         if not (
             osp.exists(osp.join(root, kind, fn))
             and osp.exists(osp.join(root, kind, 'kid_template.npy'))
@@ -365,4 +381,45 @@ def write_transfer_files(data_root, seed=0, smplx_kind='smplx'):
     tmp = osp.join(d, 'smplx', f'flip.tmp{os.getpid()}.npz')
     np.savez(tmp, closest_faces=idx, bc=w)
     os.replace(tmp, osp.join(d, 'smplx', 'smplx_flip_correspondences.npz'))
+    return data_root
+
+
+HAND_REPLACER_SMPLH = 'smplh_b16'  # the SMPL-H-shaped kind of the HandReplacer fixtures (16 betas, as smplh16)
+
+
+def write_hand_replacer_files(data_root, seed=0, smplx_kind='smplx', smplh_kind=HAND_REPLACER_SMPLH):
+    """Synthetic stand-ins for what ``HandReplacer`` reads under ``$DATA_ROOT/body_models`` beside the files of
+    ``write_transfer_files`` (which this writes first, unchanged): ``smplh16/neutral/model.npz`` (+ kid template) — the
+    SMPL-H-shaped model — and ``smplx/MANO_SMPLX_vertex_ids.pkl`` — ``{'left_hand', 'right_hand'}``: SMPL-X vertex ids
+    (reference pt/handreplacer.py:20-26).
+
+    The real SMPL-H shares SMPL's topology, so the rows of ``smplx2smpl`` that a hand column dominates are hand vertices
+    of SMPL-H.  The synthetic SMPL and SMPL-H templates are separate point clouds in separate orders, so the id file is
+    built to keep that property: it lists the SMPL-X columns whose dominated rows (an entry > 0.5) are ALL vertices of
+    SMPL-H finger parts (dominant skinning joint >= 22), left or right by the part.  ``hand_indices_all`` then is a
+    subset of the finger vertices, and ``hand_mix_weight`` is 0 on most of the body, as for the real files.
+    Returns ``data_root``."""
+    write_transfer_files(data_root, seed, smplx_kind)
+    d = osp.join(data_root, 'body_models')
+    write_model_files(d, smplh_kind, seed, dirname='smplh16')
+    smpl = make_model_arrays('smpl', seed)['v_template'].astype(np.float64)
+    smplx = make_model_arrays(smplx_kind, seed)['v_template'].astype(np.float64)
+    part = np.argmax(make_model_arrays(smplh_kind, seed)['weights'], axis=1)
+    idx, w = _nearest3(smplx, smpl)  # the rows of smplx2smpl_deftrafo_setup.pkl
+    rows, ks = np.nonzero(w > 0.5)
+    cols = idx[rows, ks]
+    ok = np.ones(len(smplx), bool)
+    np.logical_and.at(ok, cols, part[rows] >= 22)
+    seen = np.zeros(len(smplx), bool)
+    seen[cols] = True
+    left = np.zeros(len(smplx), bool)
+    left[cols[part[rows] < 37]] = True
+    hand = ok & seen
+    ids = dict(left_hand=np.nonzero(hand & left)[0].astype(np.int64),
+               right_hand=np.nonzero(hand & ~left)[0].astype(np.int64))
+    path = osp.join(d, 'smplx', 'MANO_SMPLX_vertex_ids.pkl')
+    tmp = path + f'.tmp{os.getpid()}'
+    with open(tmp, 'wb') as f:
+        pickle.dump(ids, f, protocol=2)
+    os.replace(tmp, path)
     return data_root
