@@ -266,7 +266,13 @@ class OracleFitter:
         )
 
     # -- global rotations (pt/bodyfitter.py:1321-1416) --------------------------------------------
-    def fit_global_rotations(self, tv, tj, rv, rj, vw, jw):
+    PART_LEAF, PART_MULTI, PART_BONE = 0, 1, 2
+
+    def fit_global_rotations(self, tv, tj, rv, rj, vw, jw, return_cov=False):
+        """``return_cov``: also a dict with what each part's rotation was computed from — ``cov`` (B, J, 3, 3) the centred
+        cross-covariances, ``kind`` (J,) PART_LEAF / PART_MULTI / PART_BONE (-1: no rotation of its own, the SMPL toes)
+        and, for the bone parts, the normalised ``bone_ref`` / ``bone_tgt`` (B, J, 3) with their lengths
+        ``bone_ref_len`` / ``bone_tgt_len`` (B, J) and ``twist_sc`` (B, J, 2), the two arguments of the twist's atan2."""
         m, dt, J = self.m, self.m.dtype, self.m.J
         if tj is None or rj is None:
             tj = np.einsum('jv,bvc->bjc', m.J_regressor_post_lbs, tv)
@@ -274,6 +280,11 @@ class OracleFitter:
         B = tv.shape[0]
         raw, st, sa, sw = self.part_sums(tv, rv, vw)
         R = np.zeros((B, J, 3, 3), dt)
+        cov = np.zeros((B, J, 3, 3), dt)
+        kind = np.full(J, -1)
+        bones = {k: np.zeros((B, J, 3), dt) for k in ('bone_ref', 'bone_tgt')}
+        bones.update({k: np.zeros((B, J), dt) for k in ('bone_ref_len', 'bone_tgt_len')})
+        twist_sc = np.zeros((B, J, 2), dt)
 
         def center(x, i):  # mean of children-and-self, as (1/n)-weighted sum (:124-129)
             n = len(self.cas[i])
@@ -281,6 +292,7 @@ class OracleFitter:
 
         for i in self.leaf:
             A = self._centered(raw[:, i], st[:, i], sa[:, i], sw[:, i], center(tj, i), center(rj, i))
+            cov[:, i], kind[i] = A, self.PART_LEAF
             R[:, i] = proj_so3(np.broadcast_to(A, (B, 3, 3)).astype(dt))
         for i in self.multi:  # Kabsch on the part's joints only (:1361-1383)
             js = self.cas[i]
@@ -295,16 +307,21 @@ class OracleFitter:
                 swj = np.full((1, 1), float(len(js)), dt)
             rawj = np.einsum('bnr,bnc->brc', tjs, np.broadcast_to(rjs_w, (B,) + rjs_w.shape[1:]))
             A = self._centered(rawj, ts.sum(1), rjs_w.sum(1), swj, center(tj, i), center(rj, i))
+            cov[:, i], kind[i] = A, self.PART_MULTI
             R[:, i] = proj_so3(np.broadcast_to(A, (B, 3, 3)).astype(dt))
         for i in self.bone:  # swing from the bone, twist from the vertices (:1389-1412)
             k, c = self.cas[i]
             b_ref = rj[:, c] - rj[:, k]
             b_tgt = tj[:, c] - tj[:, k]
+            bones['bone_ref_len'][:, i] = np.linalg.norm(b_ref, axis=-1)
+            bones['bone_tgt_len'][:, i] = np.linalg.norm(b_tgt, axis=-1)
             b_ref = divide_no_nan(b_ref, np.linalg.norm(b_ref, axis=-1, keepdims=True))
             b_tgt = divide_no_nan(b_tgt, np.linalg.norm(b_tgt, axis=-1, keepdims=True))
             b_ref = np.broadcast_to(b_ref, (B, 3)).astype(dt)
             Rsw = align_unit_vectors(b_ref, b_tgt)
             A = self._centered(raw[:, i], st[:, i], sa[:, i], sw[:, i], center(tj, i), center(rj, i))
+            cov[:, i], kind[i] = A, self.PART_BONE
+            bones['bone_ref'][:, i], bones['bone_tgt'][:, i] = b_ref, b_tgt
             H = Rsw @ np.swapaxes(np.broadcast_to(A, (B, 3, 3)), -1, -2)
             trH = H[:, 0, 0] + H[:, 1, 1] + H[:, 2, 2]
             bHb = np.einsum('br,brc,bc->b', b_tgt, H, b_tgt)
@@ -312,10 +329,13 @@ class OracleFitter:
                 [H[:, 1, 2] - H[:, 2, 1], H[:, 2, 0] - H[:, 0, 2], H[:, 0, 1] - H[:, 1, 0]], -1
             )
             ang = np.arctan2((b_tgt * vee).sum(-1), trH - bHb)
+            twist_sc[:, i, 0], twist_sc[:, i, 1] = (b_tgt * vee).sum(-1), trH - bHb
             R[:, i] = rotvec2mat((b_tgt * ang[:, None]).astype(dt)) @ Rsw
         if self.smpl_family:  # toes take the feet (:147-156)
             R[:, 10] = R[:, 7]
             R[:, 11] = R[:, 8]
+        if return_cov:
+            return R, dict(cov=cov, kind=kind, twist_sc=twist_sc, **bones)
         return R
 
     # -- shape solve (pt/bodyfitter.py:840-1102) --------------------------------------------------

@@ -390,8 +390,9 @@ class BodyFitter(nn.Module):
                      joint_weights=None, beta_regularizer=1.0, beta_regularizer2=0.0,
                      kid_regularizer=None, add_mean=False, want_mesh=True, share_beta=False, scale_mode=0,
                      scale_regularizer=0.0, beta_ref=None, kid_ref=None, share_beta_group=None):
-        """One shape solve for given global rotations; targets are centred internally and, unless
-        ``add_mean``, the returned trans / vertices / joints live in the centred frame."""
+        """One shape solve for given global rotations; targets are centred internally and the returned
+        trans / vertices / joints live in the centred frame; ``add_mean`` adds the target mean back to
+        trans alone (vertices / joints stay centred)."""
         bm = self.body_model
         device = bm.v_template.device
         prep = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()  # noqa: E731

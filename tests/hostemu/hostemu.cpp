@@ -585,6 +585,8 @@ void hostemu_proj_so3(const float* A, float* R, int n) { for (int i = 0; i < n; 
 void hostemu_mat2rotvec(const float* R, float* rv, int n) { for (int i = 0; i < n; ++i) sf::mat2rotvec(R + i * 9, rv + i * 3); }
 void hostemu_rotvec2mat(const float* rv, float* R, int n) { for (int i = 0; i < n; ++i) sf::rotvec2mat(rv + i * 3, R + i * 9); }
 void hostemu_align(const float* a, const float* b, float* R, int n) { for (int i = 0; i < n; ++i) sf::align_unit_vectors(a + i * 3, b + i * 3, R + i * 9); }
+// b: 12 floats per element, the target bone and the centred cross-covariance (the layout of smplfit_primitives_f32's op 4)
+void hostemu_swing_twist(const float* bref, const float* b, float* R, int n) { for (int i = 0; i < n; ++i) sf::swing_twist(bref + i * 3, b + i * 12, b + i * 12 + 3, R + i * 9); }
 
 int hostemu_fit(const smplfit_model_desc* d, const float* tv, const float* tj, const float* vw,
                 const float* jw, int B, int num_iter, float reg, float reg2, float kid_reg,

@@ -55,12 +55,27 @@ def load():
     for fn in ('hostemu_proj_so3', 'hostemu_mat2rotvec', 'hostemu_rotvec2mat'):
         getattr(lib, fn).argtypes = [vp, vp, i32]
     lib.hostemu_align.argtypes = [vp, vp, vp, i32]
+    lib.hostemu_swing_twist.argtypes = [vp, vp, vp, i32]
     _cache = lib
     return lib
 
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def prim(op, a, b, out_shape):
+    """The rotation primitives of sf_math.h in the host build, with the operation numbers and layouts of
+    smplfit_primitives_f32 (a runner for tests/prim_util.py)."""
+    lib = load()
+    a = np.ascontiguousarray(a, np.float32)
+    b = None if b is None else np.ascontiguousarray(b, np.float32)
+    out = np.full(out_shape, np.nan, np.float32)
+    if op < 3:
+        (lib.hostemu_proj_so3, lib.hostemu_rotvec2mat, lib.hostemu_mat2rotvec)[op](_p(a), _p(out), len(a))
+    else:
+        (lib.hostemu_align, lib.hostemu_swing_twist)[op - 3](_p(a), _p(b), _p(out), len(a))
+    return out
 
 
 def desc_from_md(md, kind='smpl', enable_kid=False):

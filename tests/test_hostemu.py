@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import hostemu_util as H
+import prim_util as P
 import util
 
 
@@ -78,6 +79,68 @@ def test_proj_so3_against_fp64_svd():
         err = np.abs(R.astype(np.float64) - ref)[ok].max()
         assert err < 2e-6, (name, err)  # (3e-8 observed on every set: the rounding of the fp32 outputs)
         assert np.abs(np.linalg.det(R.astype(np.float64)) - 1).max() < 1e-5, name
+
+
+# ---- the hard-input families of tests/prim_util.py on the HOST build (libm, no FMA contraction); the device build runs
+# the same arrays under the same gates in tests/test_gpu_primitives.py -----------------------------------------------------
+def test_proj_so3_hard_families(capsys):
+    """sf::proj_so3 on the inputs test_proj_so3_against_fp64_svd discards: reflections whose two smallest singular values
+    close up (the closed form hands over to the Jacobi sweeps there), rank 1, a vanishing s3 of either sign, rotations plus
+    noise, all at three scales, and exactly degenerate matrices — every output a proper rotation, as optimal as the SVD's
+    and, scaled by the conditioning, as close to it."""
+    with capsys.disabled():
+        print()
+        P.check_proj_so3(H.prim, 'host')
+    P.check_proj_nonfinite(H.prim, 'host')
+
+
+def test_mat2rotvec_branches(capsys):
+    with capsys.disabled():
+        print()
+        P.check_mat2rotvec(H.prim, 'host')
+
+
+def test_rotvec2mat_angles(capsys):
+    with capsys.disabled():
+        print()
+        P.check_rotvec2mat(None, 'fp32 oracle', oracle_only=True)  # the bound holds for the reference arithmetic itself
+        P.check_rotvec2mat(H.prim, 'host')
+
+
+def test_align_near_parallel(capsys):
+    """Unit pairs approaching parallel and antiparallel, identical and exactly opposite ones."""
+    with capsys.disabled():
+        print()
+        P.check_align(H.prim, 'host')
+
+
+def test_swing_twist_near_parallel(capsys):
+    """Bones approaching parallel and antiparallel, zero bones, a zero covariance, twists at +-(pi - 10^-k)."""
+    with capsys.disabled():
+        print()
+        P.check_swing_twist(H.prim, 'host')
+
+
+def test_prim_util_families():
+    """The generators build what they say: the twist angles sit at +-(pi - 10^-k), the reflections are reflections with the
+    stated gap, 2 pi / 3 +- k ulp puts fp32 traces on both sides of 0, the tie axes tie."""
+    for k in range(1, 8):
+        br, bt, A = P.swing_twist_inputs()[f'twist_{k}']
+        _, ang = P.swing_twist_ref(br, bt, A, np.float64)
+        assert np.abs(np.pi - np.abs(ang) - 10.0 ** -k).max() < 5e-6  # (bones and covariance are rounded to fp32)
+        assert (ang > 0).any() and (ang < 0).any()
+    fams = P.proj_families()
+    A, dec = fams['refl_gap']
+    s = np.linalg.svd(A.astype(np.float64), compute_uv=False)
+    assert (np.linalg.det(A.astype(np.float64))[(dec < 0) & (dec > -6)] < 0).all()  # (e = 0: s3 = 0; below 1e-6: fp32 rounding)
+    for e in (0, -3, -6):
+        assert np.allclose(((s[:, 1] - s[:, 2]) / s[:, 0])[dec == e], 10.0 ** e, rtol=0.3)
+    assert np.array_equal(fams['rank1_up'][0], fams['rank1'][0] * np.float32(2.0 ** 60))
+    R = P.exp64(P.rotvec_grid()['trace0']).astype(np.float32)
+    tr = R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2]
+    assert (tr > 0).any() and (tr <= 0).any()
+    Rpi = P.exp64(P.rotvec_grid()['pi']).astype(np.float32)
+    assert ((Rpi[:, 0, 0] == Rpi[:, 1, 1]) | (Rpi[:, 1, 1] == Rpi[:, 2, 2])).sum() >= 6  # exact diagonal ties
 
 
 @pytest.mark.parametrize('name', ['smpl', 'smplx', 'smpl1024'])
@@ -249,3 +312,25 @@ def test_num_betas_padding(nb, model_root, golden):
             continue
         o = H.fit(md, 'smpl', gnb[f'nb{nb}.target_vertices'], gnb[f'nb{nb}.target_joints'], enable_kid=kid, **util.NB_CFG[cfg])
         util.check_nb(om64, gnb, nb, kid, cfg, o)
+
+
+@pytest.mark.parametrize('name', ['smpl'])
+def test_rotation_pass_hard_targets(name, model_root, golden, capsys):
+    """The first rotation pass of the host build (sf::joint_stage behind the part sums) on the hard-target families of
+    tests/stage_util.py against OracleFitter.fit_global_rotations in fp64 — the criteria tests/test_gpu_stages_hard.py
+    applies to BodyFitter._part_rotations on the device."""
+    import stage_util as S
+
+    g = golden(name)
+    kind, md = util.load_md(model_root, name, g)
+    om64, of64 = util.make_oracle(md, kind, np.float64)
+    _, of32 = util.make_oracle(md, kind, np.float32)
+    fams = S.families(om64, of64)
+    with capsys.disabled():
+        print()
+        for family in S.UNMASKED + S.MASKED:
+            fam = fams[family]
+            G = H.fit(md, kind, fam['tv'], fam['tj'], fam['vw'], fam['jw'], num_iter=1, final_adjust_rots=False)['glob_rotmats_iter0']
+            G64, info = S.oracle_rotations(of64, fam)
+            G32, _ = S.oracle_rotations(of32, fam)
+            S.check_rotations(name, family, S.rotation_figures(G, G32, G64, info, S.dist_gate(name)), 'host')
