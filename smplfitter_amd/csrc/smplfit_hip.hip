@@ -280,6 +280,20 @@ struct Workspace {
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// The bump allocator of every workspace layout: regions handed out in order from `base`, each starting on a 256-byte
+// boundary.  A null base only counts.  off: the bytes taken so far, a multiple of 256 — the size of the layout once
+// its function has run.  Nothing else aligns or advances a workspace offset.
+struct Arena {
+  char* base;
+  size_t off = 0;
+  template <class T>
+  T* take(size_t count) {
+    const size_t o = off;
+    off = align_up(off + count * sizeof(T), 256);
+    return base ? reinterpret_cast<T*>(base + o) : nullptr;
+  }
+};
+
 // Kernels that may ask for more than 64 KB of dynamic LDS: the attribute is set once per (device, kernel) — a list
 // under a mutex, so that every device id has its own entry (round 5 kept 16 flags indexed by id & 15: the ids from 16
 // up shared a flag with a lower id and never got the attribute)
@@ -322,15 +336,12 @@ constexpr int kAccExtrasHost = 16;  // (= kAccExtras of kernels_bm.inc: the extr
 // general path: instances per chunk of a share_beta solve (the workspace reserves their S^2 + S doubles)
 inline int share_chunk(int B) { return std::min((B + 63) / 64 * 64, 256); }
 
-size_t carve(const sf::HostTables& t, int B, char* base, Workspace* w, bool fwd_only = false) {
+// LAYOUT fit: the workspace of one fit / forward / shape solve of B instances (smplfit_workspace_bytes: its chunks).
+Workspace carve(const sf::HostTables& t, int B, Arena& ar, bool fwd_only = false) {
   const size_t Mp = align_up((size_t)B, 128);
   const size_t Vp = t.Vp, J = t.J, S = t.S, NE1 = t.ne() + 1;
-  size_t off = 0;
   auto take = [&](size_t bytes, bool fwd = false) {  // fwd: also part of the forward-only slice
-    if (fwd_only && !fwd) return (char*)nullptr;
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return base ? base + o : nullptr;
+    return fwd_only && !fwd ? (char*)nullptr : ar.take<char>(bytes);
   };
   Workspace ws;
   ws.tvs = (float*)take((size_t)B * 3 * Vp * 4);
@@ -403,8 +414,7 @@ size_t carve(const sf::HostTables& t, int B, char* base, Workspace* w, bool fwd_
   ws.GT = (float*)take(pro ? Mp * J * 9 * 4 : 0);
   ws.pextT = (float*)take(pro ? Mp * J * 3 * (S + 1) * 4 : 0);
   ws.gramjP = (float*)take(pro ? (size_t)prologue_splits((int)J) * NE1 * Mp * 4 : 0);
-  if (w) *w = ws;
-  return off;
+  return ws;
 }
 
 // Cache policy of the streams.  The per-iteration streams of a fit (v_posed, the targets: 0.34 GB each at B = 4096)
@@ -877,20 +887,17 @@ int launch_lbs_any(const DevModel& d, const Workspace& ws, int B, bool weighted,
   return 0;
 }
 
-size_t chunked_workspace_bytes(const sf::HostTables& t, int batch, const sf::HostTables* tin = nullptr);
-
-// Handle, batch and workspace of every entry point.  bwd: smplfit_forward_backward_f32, whose workspace has a size
-// function of its own and whose messages name it.
-int check_common(const smplfit_handle* h, int batch, void* workspace, size_t workspace_bytes, bool bwd = false) {
-  if (!h) return fail(SMPLFIT_ERR_BAD_ARG, bwd ? "smplfit_forward_backward_f32: null handle" : "null handle");
-  if (!h->has_device) return fail(SMPLFIT_ERR_HIP, "handle was created host-only (no device)");
-  if (batch <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "batch must be positive");
+// Handle, batch and workspace of every entry point `who`.  needed: what the entry's workspace query `query` answers
+// for this handle and batch (the queries answer 0 for a null handle or a batch <= 0, so they may be asked first).
+int check_call(const char* who, const smplfit_handle* h, int batch, const void* workspace, size_t given, size_t needed,
+               const char* query) {
+  const auto bad = [who](int code, const std::string& what) { return fail(code, std::string(who) + ": " + what); };
+  if (!h) return bad(SMPLFIT_ERR_BAD_ARG, "null handle");
+  if (!h->has_device) return bad(SMPLFIT_ERR_HIP, "handle was created host-only (no device)");
+  if (batch <= 0) return bad(SMPLFIT_ERR_BAD_ARG, "batch must be positive");
   if (!workspace || ((uintptr_t)workspace & 255))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
-  if (bwd && workspace_bytes < smplfit_forward_backward_workspace_bytes(h, batch))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (smplfit_forward_backward_workspace_bytes)");
-  if (!bwd && workspace_bytes < chunked_workspace_bytes(h->t, batch))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (see smplfit_workspace_bytes)");
+    return bad(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
+  if (given < needed) return bad(SMPLFIT_ERR_WORKSPACE, std::string("workspace too small (see ") + query + ")");
   return 0;
 }
 
@@ -904,15 +911,44 @@ int check_scale_share(const char* who, int scale_mode, const float* scale_corr, 
   return 0;
 }
 
-// The inputs of a forward evaluation (smplfit_forward_ex_f32, smplfit_forward_backward_f32)
-int check_forward_inputs(const char* who, const DevModel& d, const float* pose, const float* glob, const float* rel,
-                         const float* betas, int num_betas_given, const float* kid) {
-  if ((pose != nullptr) + (glob != nullptr) + (rel != nullptr) > 1)
+// The inputs of a forward evaluation as the argument structs of the forward, its backward and both objectives name
+// them: one rotation form or none, (B, given) betas, the kid factor.  Read once per call (forward_inputs), checked
+// (check_forward_inputs), and the kernels' argument structs are filled from them (forward_args here, JointBwdArgs in
+// launch_forward_backward).
+struct ForwardInputs {
+  const float *pose, *glob, *rel, *betas, *kid;
+  int given;
+};
+template <class A>
+ForwardInputs forward_inputs(const A& a) {
+  return {a.pose_rotvecs, a.glob_rotmats, a.rel_rotmats, a.shape_betas, a.kid_factor, a.num_betas_given};
+}
+int check_forward_inputs(const char* who, const DevModel& d, const ForwardInputs& in) {
+  if ((in.pose != nullptr) + (in.glob != nullptr) + (in.rel != nullptr) > 1)
     return fail(SMPLFIT_ERR_BAD_ARG, "Only one rotation input may be provided");
-  if (betas && num_betas_given > d.S - d.jt.n_kid - d.jt.n_pad)
+  if (in.betas && in.given > d.S - d.jt.n_kid - d.jt.n_pad)
     return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": more betas than the model holds; slice first");
-  if (kid && !d.jt.n_kid) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": kid_factor given to a handle without kid");
+  if (in.kid && !d.jt.n_kid) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": kid_factor given to a handle without kid");
   return 0;
+}
+// Betas per instance row.  The forward clamps to the model's; the backward family reads the rows as given
+// (check_forward_inputs has refused more than the model holds).
+int forward_nb(const DevModel& d, const ForwardInputs& in) {
+  return in.betas ? std::min(in.given, d.S - d.jt.n_kid - d.jt.n_pad) : 0;
+}
+int backward_nb(const ForwardInputs& in) { return in.betas ? std::max(0, in.given) : 0; }
+ForwardArgs forward_args(const ForwardInputs& in, int nb, const float* trans, float* joints, float* orient) {
+  ForwardArgs fa{};
+  fa.pose = in.pose;
+  fa.glob = in.glob;
+  fa.rel = in.rel;
+  fa.betas = in.betas;
+  fa.nb = nb;
+  fa.kid = in.kid;
+  fa.trans = trans;
+  fa.joints = joints;
+  fa.orient = orient;
+  return fa;
 }
 
 // Arithmetic of the posedirs contraction: "bf16x3" (default) runs it on the bf16 matrix cores with every fp32
@@ -1321,6 +1357,7 @@ int post_launch_check() {
 //   launch_lbs_pass           the LBS pass: part sums against the targets / the mesh alone (also to the caller: mesh out)
 //   launch_normal_equations   GEMM, joint-row transpose, the vertex block of one shape solve
 //   launch_alignment          scale and translation of a known-shape fit
+//   launch_forward_backward   the forward's vector-Jacobian product (below, behind the layouts it runs in)
 // and the rules that fill their arguments: solve_weights, set_joint_block, refine_args.
 // ------------------------------------------------------------------------------------------------
 
@@ -1893,17 +1930,28 @@ int chunk_plan_n(int n, int batch, int* sizes) {
 }
 int chunk_plan(const sf::HostTables& t, int batch, int* sizes) { return chunk_plan_n(chunk_count(t), batch, sizes); }
 
-// `tin`: the input model of a fused conversion — every chunk's slice is followed by that model's forward-only slice.
-// Sized for every chunk count a call may pick (the tuning options can be reloaded between the two calls).
-size_t chunked_workspace_bytes(const sf::HostTables& t, int batch, const sf::HostTables* tin) {
+// LAYOUT one chunk of a fit call: the fit's workspace, then — `tin`, the input model of a fused conversion — that
+// model's forward-only slice
+struct ChunkLayout {
+  Workspace ws, wsi;
+};
+ChunkLayout chunk_layout(const sf::HostTables& t, const sf::HostTables* tin, int nb, Arena& ar) {
+  ChunkLayout l{};
+  l.ws = carve(t, nb, ar);
+  if (tin) l.wsi = carve(*tin, nb, ar, true);
+  return l;
+}
+
+// The chunks of a call one behind the other (fit_impl).  Sized for every chunk count a call may pick (the tuning
+// options can be reloaded between the two calls).
+size_t chunked_workspace_bytes(const sf::HostTables& t, int batch, const sf::HostTables* tin = nullptr) {
   size_t need = 0;
   for (int n = 1; n <= kMaxChunks; ++n) {
     int sizes[kMaxChunks];
     const int k = chunk_plan_n(n, batch, sizes);
-    size_t total = 0;
-    for (int i = 0; i < k; ++i)
-      total += carve(t, sizes[i], nullptr, nullptr) + (tin ? carve(*tin, sizes[i], nullptr, nullptr, true) : 0);
-    need = std::max(need, total);
+    Arena ar{nullptr};
+    for (int i = 0; i < k; ++i) chunk_layout(t, tin, sizes[i], ar);
+    need = std::max(need, ar.off);
   }
   return need;
 }
@@ -1941,14 +1989,13 @@ smplfit_fit_args chunk_view(const smplfit_fit_args& a, const sf::HostTables& t, 
   return v;
 }
 
-// vw_shared: args->vertex_weights is one (V) row for the whole batch (smplfit_replace_hands_f32)
+// vw_shared: args->vertex_weights is one (V) row for the whole batch (smplfit_replace_hands_f32).  The entry has run
+// check_call against its own query, which holds chunked_workspace_bytes from a.workspace on: a.workspace_bytes is not
+// read here.
 int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const ConvertJob* job, bool vw_shared = false) {
   const smplfit_fit_args& a = *args;
   const int batch = a.batch;
-  int rc = check_common(h, batch, a.workspace, job ? (size_t)-1 : a.workspace_bytes);
-  if (rc) return rc;
-  if (job && a.workspace_bytes < chunked_workspace_bytes(h->t, batch, &job->plan->in->t))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (see smplfit_convert_workspace_bytes)");
+  int rc = 0;
   if ((!a.target_vertices && !job) || !a.pose_rotvecs || !a.shape_betas || !a.trans)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_f32: null input/output pointer");
   if (a.num_iter < 1) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_f32: num_iter must be >= 1");
@@ -1958,16 +2005,23 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_warm_f32: num_initial_betas must lie in [0, the model's betas]; slice first");
   if ((rc = check_scale_share("smplfit_fit_ex_f32", a.scale_mode, a.scale_corr, a.share_beta, a.share_allreduce))) return rc;
   hipStream_t st = (hipStream_t)a.hip_stream;
-  int sizes[kMaxChunks];
+  int sizes[kMaxChunks] = {batch};
   // share_beta couples all instances in every shape solve: one chunk
   const int nchunk = (h->have_streams && !a.share_beta) ? chunk_plan(h->t, batch, sizes) : 1;
   const int Jin = job ? job->plan->in->t.J : 0;
-  auto chunk_bytes = [&](int nb) {
-    return carve(h->t, nb, nullptr, nullptr) + (job ? carve(job->plan->in->t, nb, nullptr, nullptr, true) : 0);
-  };
-  auto run_chunk = [&](int b0, int nb, char* wsbase, hipStream_t cs, int ph_lo, int ph_hi) -> int {
-    Workspace ws;
-    const size_t own = carve(h->t, nb, wsbase, &ws);
+  int b0s[kMaxChunks];
+  ChunkLayout lay[kMaxChunks];  // every chunk's slice of the workspace, one behind the other
+  {
+    Arena ar{(char*)a.workspace};
+    int b0 = 0;
+    for (int c = 0; c < nchunk; ++c) {
+      b0s[c] = b0;
+      lay[c] = chunk_layout(h->t, job ? &job->plan->in->t : nullptr, sizes[c], ar);
+      b0 += sizes[c];
+    }
+  }
+  auto run_chunk = [&](int c, hipStream_t cs, int ph_lo, int ph_hi) -> int {
+    const int b0 = b0s[c], nb = sizes[c];
     ConvertSource src{};
     if (job) {
       src.plan = job->plan;
@@ -1976,13 +2030,13 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
       src.trans = job->trans ? job->trans + (size_t)b0 * 3 : nullptr;
       src.nb = job->nb;
       src.kid = job->kid ? job->kid + b0 : nullptr;
-      carve(job->plan->in->t, nb, wsbase + own, &src.wsi, true);
+      src.wsi = lay[c].wsi;
     }
     smplfit_fit_args v = chunk_view(a, h->t, b0, nb);
     if (vw_shared) v.vertex_weights = a.vertex_weights;  // (every chunk reads the one row)
-    return run_fit(h, v, false, job ? &src : nullptr, ws, cs, ph_lo, ph_hi, vw_shared);
+    return run_fit(h, v, false, job ? &src : nullptr, lay[c].ws, cs, ph_lo, ph_hi, vw_shared);
   };
-  if (nchunk <= 1) return run_chunk(0, batch, (char*)a.workspace, st, 0, 1 << 30);
+  if (nchunk <= 1) return run_chunk(0, st, 0, 1 << 30);
   // fork: every chunk is an independent fit with its own workspace slice; chunk 0 stays on the
   // caller's stream, the others go to the handle's side streams and are joined back by events
   // (stream-ordered with respect to the caller, hipGraph-capturable).  The handle's streams and
@@ -1999,18 +2053,7 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
   std::lock_guard<std::mutex> lock(h->mu);
   SF_HIP_TRY(hipEventRecord(h->ev_fork, st));
   const int nphase = 2 + 2 * a.num_iter;
-  int b0s[kMaxChunks], first_error = 0;
-  char* wsps[kMaxChunks];
-  {
-    char* wsp = (char*)a.workspace;
-    int b0 = 0;
-    for (int c = 0; c < nchunk; ++c) {
-      b0s[c] = b0;
-      wsps[c] = wsp;
-      wsp += chunk_bytes(sizes[c]);
-      b0 += sizes[c];
-    }
-  }
+  int first_error = 0;
   std::string first_msg;
   bool forked[kMaxChunks] = {true, false, false, false};
   auto note = [&](int rc2) {
@@ -2031,7 +2074,7 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
         }
         forked[c] = true;
       }
-      note(run_chunk(b0s[c], sizes[c], wsps[c], cs, ph, ph + 1));
+      note(run_chunk(c, cs, ph, ph + 1));
     }
   // a chunk that was forked is always joined back, also after an error: an unjoined fork would
   // invalidate a stream capture and leave work in flight that the caller's stream does not wait for
@@ -2117,27 +2160,197 @@ void free_slot_transfer(smplfit_convert_plan* p) {
     if (q) (void)hipFree(q);
 }
 
-// the naively flipped pose of smplfit_flip_f32 at the front of its workspace; the fit's workspace follows
-size_t flip_pose_bytes(const smplfit_handle* h, int batch) { return align_up((size_t)batch * h->t.J * 3 * 4, 256); }
-
-// the per-instance results of the fit inside smplfit_replace_hands_f32 at the front of its workspace: relative
-// rotations (B,J,9), rotation vectors (B,3J), betas (B,S), translation (B,3); the fit's workspace follows
-struct ReplaceFront {
-  float *rel, *pose, *betas, *trans;
-  size_t bytes;
-};
-ReplaceFront replace_front(const smplfit_handle* h, int batch, char* base) {
-  const size_t B = (size_t)batch, J = h->t.J;
-  const size_t sizes[4] = {B * J * 9 * 4, B * J * 3 * 4, B * (size_t)h->t.num_betas() * 4, B * 3 * 4};
-  float* ptr[4];
-  size_t off = 0;
-  for (int k = 0; k < 4; ++k) {
-    ptr[k] = base ? (float*)(base + off) : nullptr;
-    off += align_up(sizes[k], 256);
-  }
-  return {ptr[0], ptr[1], ptr[2], ptr[3], off};
+// ------------------------------------------------------------------------------------------------
+// LAYOUTS.  One function per entry point: it takes the entry's regions from an Arena in order and leaves the total in
+// it.  The entry's workspace query runs it on a null base, the entry itself on the caller's pointer; a layout that
+// begins with another one calls it.  (carve and chunk_layout, above, are the fit's.)
+// ------------------------------------------------------------------------------------------------
+Workspace fit_workspace(const smplfit_handle* h, int B, void* base) {
+  Arena ar{(char*)base};
+  return carve(h->t, B, ar);
 }
 
+// LAYOUT forward-backward: the fit's workspace (the backward recomputes the posed pass in it), then BwdWorkspace
+struct BackwardLayout {
+  Workspace ws;
+  BwdWorkspace bw;
+};
+BackwardLayout backward_layout(const sf::HostTables& t, int B, Arena& ar) {
+  BackwardLayout l;
+  l.ws = carve(t, B, ar);
+  const size_t NC = (size_t)t.P + t.S;
+  l.bw.dvp = ar.take<float>((size_t)B * 3 * t.Vp);
+  l.bw.dA = ar.take<float>((size_t)B * t.J * 12);
+  l.bw.dtv = ar.take<float>((size_t)B * 3);
+  l.bw.part = ar.take<float>((size_t)bwd_nsplit(t.Vp) * B * NC);
+  l.bw.dfeat = ar.take<float>((size_t)B * NC);
+  l.bw.jscr = ar.take<float>((size_t)B * sf::joint_bwd_scratch_floats(t.J));
+  return l;
+}
+
+// LAYOUT fit objective: the backward's, then the (B, J, 3) joint cotangent of k_obj_joint.  (The mesh objective takes
+// the backward's own: its loss sums live in LDS, k_obj_vertex.)
+struct ObjectiveLayout {
+  BackwardLayout fb;
+  float* gjoints;
+};
+ObjectiveLayout objective_layout(const sf::HostTables& t, int B, Arena& ar) {
+  ObjectiveLayout l;
+  l.fb = backward_layout(t, B, ar);
+  l.gjoints = ar.take<float>((size_t)B * t.J * 3);
+  return l;
+}
+
+// LAYOUT adjoint of the shape solve: the backward's (the three vector-Jacobian products run in it), then AdjWorkspace
+struct AdjointLayout {
+  BackwardLayout fb;
+  AdjWorkspace aw;
+};
+AdjointLayout adjoint_layout(const sf::HostTables& t, int B, Arena& ar) {
+  AdjointLayout l;
+  l.fb = backward_layout(t, B, ar);
+  l.aw.lam = ar.take<float>((size_t)B * (t.S + 3));
+  l.aw.lamb = ar.take<float>((size_t)B * std::max(1, t.num_betas()));
+  l.aw.lamk = ar.take<float>((size_t)B);
+  l.aw.c1 = ar.take<float>((size_t)B * t.V * 3);
+  l.aw.c2 = ar.take<float>((size_t)B * t.V * 3);
+  l.aw.c1j = ar.take<float>((size_t)B * t.J * 3);
+  l.aw.c2j = ar.take<float>((size_t)B * t.J * 3);
+  l.aw.g1 = ar.take<float>((size_t)B * t.J * 9);
+  l.aw.g2 = ar.take<float>((size_t)B * t.J * 9);
+  l.aw.g3 = ar.take<float>((size_t)B * t.J * 9);
+  return l;
+}
+
+// LAYOUT flip: the naively flipped pose (B,3J) the warm start reads, then the chunks of the fused conversion's fit
+struct FlipLayout {
+  float* init_pose;
+  char* fit;
+};
+FlipLayout flip_layout(const smplfit_convert_plan& conv, int B, Arena& ar) {
+  FlipLayout l;
+  l.init_pose = ar.take<float>((size_t)B * conv.out->t.J * 3);
+  l.fit = ar.take<char>(chunked_workspace_bytes(conv.out->t, B, &conv.in->t));
+  return l;
+}
+
+// LAYOUT hand replacement: the per-instance results of its fit — relative rotations (B,J,9), rotation vectors (B,3J),
+// betas (B,S), translation (B,3): the last three stand in for parameter outputs the caller left NULL —, then the
+// chunks of the fit (the forward behind it runs in the same bytes, as one fit workspace)
+struct ReplaceLayout {
+  float *rel, *pose, *betas, *trans;
+  char* fit;
+};
+ReplaceLayout replace_layout(const sf::HostTables& t, int B, Arena& ar) {
+  ReplaceLayout l;
+  l.rel = ar.take<float>((size_t)B * t.J * 9);
+  l.pose = ar.take<float>((size_t)B * t.J * 3);
+  l.betas = ar.take<float>((size_t)B * t.num_betas());
+  l.trans = ar.take<float>((size_t)B * 3);
+  l.fit = ar.take<char>(chunked_workspace_bytes(t, B));
+  return l;
+}
+
+// [dfeat | dshape] = dv_posed . [posedirs | shapedirs]^T: the split-K partial products, then their sum in chunk order
+void launch_bwd_reduce(const DevModel& d, const BwdWorkspace& bw, int B, hipStream_t st) {
+  const int NC = d.P + d.S, nsplit = bwd_nsplit(d.Vp);
+  hipLaunchKernelGGL(k_bwd_reduce, dim3((NC + kBwdTile - 1) / kBwdTile, (B + kBwdTile - 1) / kBwdTile, nsplit),
+                     dim3(256), 0, st, d, bw, B);
+  hipLaunchKernelGGL(k_bwd_combine, dim3((unsigned)(((size_t)B * NC + 255) / 256)), dim3(256), 0, st, bw, B, NC, nsplit);
+}
+
+// STEP forward backward.  The vector-Jacobian product of the forward at `in` (nb betas per row), in a laid-out
+// BackwardLayout.  With a vertex cotangent: the posed pass recomputed without trans (the joint block (G | t) and
+// v_posed), the vertex kernel, the pose-feature / shape reduction; then the joint backward, which writes `out`.
+// Where the cotangents come from is all that varies between the callers:
+struct Cotangents {
+  // from memory (smplfit_forward_backward_f32, the adjoint), each may be null:
+  const float *vertices = nullptr, *joints = nullptr, *orient = nullptr;
+  // or formed from the objective: the vertex's in registers by k_obj_vertex in place of k_bwd_vertex (trans added
+  // there), and — joint term — the joints' by k_obj_joint into its gjoints, loss added behind k_obj_vertex's (stream order)
+  const ObjArgs* obj = nullptr;
+  const ObjJointArgs* obj_joints = nullptr;
+};
+struct GradOutputs {
+  float *pose, *glob, *rel, *betas, *trans, *kid;  // each may be null; pose / glob / rel: that of the form given
+};
+template <class A>
+GradOutputs grad_outputs(const A& a) {
+  return {a.grad_pose_rotvecs, a.grad_glob_rotmats, a.grad_rel_rotmats, a.grad_shape_betas, a.grad_trans, a.grad_kid_factor};
+}
+int launch_forward_backward(const smplfit_handle* h, const ForwardInputs& in, int nb, const Cotangents& ct,
+                            const GradOutputs& out, const BackwardLayout& l, int B, hipStream_t st) {
+  const DevModel& d = h->d;
+  const Workspace& ws = l.ws;
+  const BwdWorkspace& bw = l.bw;
+  const bool vertex = ct.vertices || ct.obj;
+  if (vertex) {
+    // (route_of: Entry::kForwardBackward is never batch-major; these kernels serve every model)
+    const ForwardArgs fa = forward_args(in, nb, nullptr, ws.rjoints, nullptr);
+    if (int rc = launch_posed_pass(h, route_of(h, B, {Entry::kForwardBackward}), {&fa, {}}, ws, B, st)) return rc;
+    if (ct.obj)
+      hipLaunchKernelGGL(k_obj_vertex, dim3(B), dim3(256), bwd_vertex_lds_bytes(d, true), st, d, ws, bw, B, nb, in.betas,
+                         in.kid, *ct.obj);
+    else
+      hipLaunchKernelGGL(k_bwd_vertex, dim3(B), dim3(256), bwd_vertex_lds_bytes(d, false), st, d, ws, bw, B, nb, in.betas,
+                         in.kid, ct.vertices);
+    launch_bwd_reduce(d, bw, B, st);
+  }
+  if (ct.obj_joints) hipLaunchKernelGGL(k_obj_joint, dim3((B + 63) / 64), dim3(64), 0, st, *ct.obj_joints, B, d.J);
+  JointBwdArgs ja{};
+  ja.pose = in.pose;
+  ja.glob = in.glob;
+  ja.rel = in.rel;
+  ja.betas = in.betas;
+  ja.kid = in.kid;
+  ja.nb = nb;
+  ja.gjoints = ct.obj_joints ? ct.obj_joints->gjoints : ct.joints;
+  ja.gorient = ct.orient;
+  ja.vertex = vertex;
+  ja.g_pose = out.pose;
+  ja.g_glob = out.glob;
+  ja.g_rel = out.rel;
+  ja.g_betas = out.betas;
+  ja.g_trans = out.trans;
+  ja.g_kid = out.kid;
+  hipLaunchKernelGGL(k_bwd_joint, dim3((B + 63) / 64), dim3(64), 0, st, d, bw, ja, B);
+  return 0;
+}
+
+// Both objective entry points (A: either argument struct).  jt: the joint term's fields, which only
+// smplfit_fit_objective_args has — null for smplfit_mesh_objective_f32, whose workspace is the backward's; the term
+// itself runs when target_joints is given.
+struct JointTerm {
+  const float *target, *weights;
+  float scale;
+};
+template <class A>
+int objective_impl(const char* who, const smplfit_handle* h, const A& a, const JointTerm* jt, size_t needed,
+                          const char* query) {
+  const int B = a.batch;
+  if (int rc = check_call(who, h, B, a.workspace, a.workspace_bytes, needed, query)) return rc;
+  const DevModel& d = h->d;
+  const ForwardInputs in = forward_inputs(a);
+  if (int rc = check_forward_inputs(who, d, in)) return rc;
+  if (!a.target_vertices) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": target_vertices is required");
+  if (jt && jt->weights && !jt->target)
+    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": joint_weights without target_joints");
+  if (!a.loss) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": loss output is required");
+  Arena ar{(char*)a.workspace};
+  ObjectiveLayout l{};
+  if (jt) l = objective_layout(h->t, B, ar);
+  else l.fb = backward_layout(h->t, B, ar);
+  const ObjArgs oa{a.target_vertices, a.vertex_weights, a.trans, a.scale, a.loss};
+  ObjJointArgs oj{};
+  Cotangents ct;
+  ct.obj = &oa;
+  if (jt && jt->target) {
+    oj = {l.fb.ws.rjoints, a.trans, jt->target, jt->weights, jt->scale, l.gjoints, a.loss};
+    ct.obj_joints = &oj;
+  }
+  if (int rc = launch_forward_backward(h, in, backward_nb(in), ct, grad_outputs(a), l.fb, B, (hipStream_t)a.hip_stream)) return rc;
+  return post_launch_check();
+}
 
 }  // namespace
 
@@ -2537,6 +2750,9 @@ int smplfit_fit_warm_f32(const smplfit_handle* h, const float* target_vertices,
 
 int smplfit_fit_ex_f32(const smplfit_handle* h, const smplfit_fit_args* args) {
   if (!args) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_ex_f32: null arguments");
+  if (int rc = check_call("smplfit_fit_f32", h, args->batch, args->workspace, args->workspace_bytes,
+                          smplfit_workspace_bytes(h, args->batch), "smplfit_workspace_bytes"))
+    return rc;
   return fit_impl(h, args, nullptr);
 }
 
@@ -2548,7 +2764,8 @@ int smplfit_fit_known_shape_f32(const smplfit_handle* h, const float* shape_beta
                                 int final_adjust_rots, int scale_fit, float* pose_rotvecs, float* trans,
                                 float* scale_corr, float* orientations, float* relative_orientations,
                                 void* workspace, size_t workspace_bytes, void* hip_stream) {
-  int rc = check_common(h, batch, workspace, workspace_bytes);
+  int rc = check_call("smplfit_fit_known_shape_f32", h, batch, workspace, workspace_bytes, smplfit_workspace_bytes(h, batch),
+                      "smplfit_workspace_bytes");
   if (rc) return rc;
   if (!shape_betas || !target_vertices || !pose_rotvecs || !trans)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_known_shape_f32: null input/output pointer");
@@ -2562,8 +2779,7 @@ int smplfit_fit_known_shape_f32(const smplfit_handle* h, const float* shape_beta
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_known_shape_f32: more betas than the model holds; slice first");
   KnownShapeOptions o{num_iter, final_adjust_rots ? 1 : 0, scale_fit ? 1 : 0};
   hipStream_t st = (hipStream_t)hip_stream;
-  Workspace ws;
-  carve(t, batch, (char*)workspace, &ws);
+  const Workspace ws = fit_workspace(h, batch, workspace);
   return run_fit_known_shape(h, shape_betas, num_betas_given, kid_factor, initial_pose_rotvecs,
                              target_vertices, target_joints, vertex_weights, joint_weights, batch, o,
                              pose_rotvecs, trans, scale_corr, orientations, relative_orientations, ws, st);
@@ -2573,12 +2789,12 @@ int smplfit_part_rotations_f32(const smplfit_handle* h, const float* target_vert
                                const float* target_joints, const float* vertex_weights,
                                const float* joint_weights, int batch, float* glob_rotmats,
                                void* workspace, size_t workspace_bytes, void* hip_stream) {
-  int rc = check_common(h, batch, workspace, workspace_bytes);
+  int rc = check_call("smplfit_part_rotations_f32", h, batch, workspace, workspace_bytes, smplfit_workspace_bytes(h, batch),
+                      "smplfit_workspace_bytes");
   if (rc) return rc;
   if (!target_vertices || !glob_rotmats)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_part_rotations_f32: null pointer");
-  Workspace ws;
-  carve(h->t, batch, (char*)workspace, &ws);
+  const Workspace ws = fit_workspace(h, batch, workspace);
   smplfit_fit_args a{};  // one rotation pass; the rotations go to the orientations
   a.target_vertices = target_vertices; a.target_joints = target_joints;
   a.vertex_weights = vertex_weights; a.joint_weights = joint_weights;
@@ -2602,229 +2818,71 @@ int smplfit_forward_f32(const smplfit_handle* h, const float* pose_rotvecs,
 
 int smplfit_forward_ex_f32(const smplfit_handle* h, const smplfit_forward_args* args) {
   if (!args) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_ex_f32: null arguments");
-  const int batch = args->batch, num_betas_given = args->num_betas_given;
-  const float *shape_betas = args->shape_betas, *trans = args->trans, *kid_factor = args->kid_factor;
-  float *vertices = args->vertices, *joints = args->joints;
-  int rc = check_common(h, batch, args->workspace, args->workspace_bytes);
+  const int batch = args->batch;
+  int rc = check_call("smplfit_forward_f32", h, batch, args->workspace, args->workspace_bytes, smplfit_workspace_bytes(h, batch),
+                      "smplfit_workspace_bytes");
   if (rc) return rc;
   const DevModel& d = h->d;
-  if ((rc = check_forward_inputs("smplfit_forward_f32", d, args->pose_rotvecs, args->glob_rotmats, args->rel_rotmats, shape_betas,
-                                 num_betas_given, kid_factor)))
-    return rc;
-  if (!joints) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_f32: joints output is required");
+  const ForwardInputs in = forward_inputs(*args);
+  if ((rc = check_forward_inputs("smplfit_forward_f32", d, in))) return rc;
+  if (!args->joints) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_f32: joints output is required");
   hipStream_t st = (hipStream_t)args->hip_stream;
-  Workspace ws;
-  carve(h->t, batch, (char*)args->workspace, &ws);
-  ForwardArgs fa{};
-  fa.pose = args->pose_rotvecs;
-  fa.glob = args->glob_rotmats;
-  fa.rel = args->rel_rotmats;
-  fa.betas = shape_betas;
-  fa.nb = shape_betas ? std::min(num_betas_given, d.S - d.jt.n_kid - d.jt.n_pad) : 0;
-  fa.kid = kid_factor;
-  fa.trans = trans;
-  fa.joints = joints;
-  fa.orient = args->orientations;
+  const Workspace ws = fit_workspace(h, batch, args->workspace);
+  const ForwardArgs fa = forward_args(in, forward_nb(d, in), args->trans, args->joints, args->orientations);
   launch_forward_joint(d, fa, ws, batch, st);
-  if (vertices)  // the mesh at the same inputs, to the caller's (B, V, 3)
-    if ((rc = launch_posed_pass(h, route_of(h, batch, {Entry::kForward}), {nullptr, mesh_alone(&fa, vertices)}, ws, batch, st))) return rc;
+  if (args->vertices)  // the mesh at the same inputs, to the caller's (B, V, 3)
+    if ((rc = launch_posed_pass(h, route_of(h, batch, {Entry::kForward}), {nullptr, mesh_alone(&fa, args->vertices)}, ws, batch, st))) return rc;
   return post_launch_check();
-}
-
-// the forward's workspace, then BwdWorkspace
-size_t forward_backward_carve(const smplfit_handle* h, int B, char* base, Workspace* ws, BwdWorkspace* bw) {
-  const sf::HostTables& t = h->t;
-  size_t off = align_up(carve(t, B, base, ws), 256);
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return base ? (float*)(base + o) : nullptr;
-  };
-  const size_t NC = (size_t)t.P + t.S;
-  bw->dvp = take((size_t)B * 3 * t.Vp * 4);
-  bw->dA = take((size_t)B * t.J * 12 * 4);
-  bw->dtv = take((size_t)B * 3 * 4);
-  bw->part = take((size_t)bwd_nsplit(t.Vp) * B * NC * 4);
-  bw->dfeat = take((size_t)B * NC * 4);
-  bw->jscr = take((size_t)B * sf::joint_bwd_scratch_floats(t.J) * 4);
-  return off;
-}
-
-// [dfeat | dshape] = dv_posed . [posedirs | shapedirs]^T: the split-K partial products, then their sum in chunk order
-void launch_bwd_reduce(const DevModel& d, const BwdWorkspace& bw, int B, hipStream_t st) {
-  const int NC = d.P + d.S, nsplit = bwd_nsplit(d.Vp);
-  hipLaunchKernelGGL(k_bwd_reduce, dim3((NC + kBwdTile - 1) / kBwdTile, (B + kBwdTile - 1) / kBwdTile, nsplit),
-                     dim3(256), 0, st, d, bw, B);
-  hipLaunchKernelGGL(k_bwd_combine, dim3((unsigned)(((size_t)B * NC + 255) / 256)), dim3(256), 0, st, bw, B, NC, nsplit);
 }
 
 size_t smplfit_forward_backward_workspace_bytes(const smplfit_handle* h, int batch) {
   if (!h || batch <= 0) return 0;
-  Workspace ws;
-  BwdWorkspace bw;
-  return forward_backward_carve(h, batch, nullptr, &ws, &bw);
+  Arena ar{nullptr};
+  backward_layout(h->t, batch, ar);
+  return ar.off;
 }
 
 int smplfit_forward_backward_f32(const smplfit_handle* h, const smplfit_forward_backward_args* a) {
-  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_forward_backward_f32: null arguments");
+  const char* who = "smplfit_forward_backward_f32";
+  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
   const int B = a->batch;
-  if (int rc = check_common(h, B, a->workspace, a->workspace_bytes, true)) return rc;
-  const DevModel& d = h->d;
-  if (int rc = check_forward_inputs("smplfit_forward_backward_f32", d, a->pose_rotvecs, a->glob_rotmats, a->rel_rotmats,
-                                    a->shape_betas, a->num_betas_given, a->kid_factor))
+  if (int rc = check_call(who, h, B, a->workspace, a->workspace_bytes, smplfit_forward_backward_workspace_bytes(h, B),
+                          "smplfit_forward_backward_workspace_bytes"))
     return rc;
-  // (route_of: Entry::kForwardBackward is never batch-major; these kernels serve every model)
-  hipStream_t st = (hipStream_t)a->hip_stream;
-  Workspace ws;
-  BwdWorkspace bw;
-  forward_backward_carve(h, B, (char*)a->workspace, &ws, &bw);
-  const int nb = a->shape_betas ? std::max(0, a->num_betas_given) : 0;
-  const bool vertex = a->grad_vertices != nullptr;
-  if (vertex) {
-    // recompute: the joint block (G | t) and v_posed; then the vertex pass and the pose-feature / shape reduction
-    ForwardArgs fa{};
-    fa.pose = a->pose_rotvecs;
-    fa.glob = a->glob_rotmats;
-    fa.rel = a->rel_rotmats;
-    fa.betas = a->shape_betas;
-    fa.nb = nb;
-    fa.kid = a->kid_factor;
-    fa.trans = nullptr;
-    fa.joints = ws.rjoints;
-    fa.orient = nullptr;
-    if (int rc = launch_posed_pass(h, route_of(h, B, {Entry::kForwardBackward}), {&fa, {}}, ws, B, st)) return rc;
-    hipLaunchKernelGGL(k_bwd_vertex, dim3(B), dim3(256), bwd_vertex_lds_bytes(d, false), st, d, ws, bw, B, nb,
-                       a->shape_betas, a->kid_factor, a->grad_vertices);
-    launch_bwd_reduce(d, bw, B, st);
-  }
-  JointBwdArgs ja{};
-  ja.pose = a->pose_rotvecs;
-  ja.glob = a->glob_rotmats;
-  ja.rel = a->rel_rotmats;
-  ja.betas = a->shape_betas;
-  ja.kid = a->kid_factor;
-  ja.nb = nb;
-  ja.gjoints = a->grad_joints;
-  ja.gorient = a->grad_orientations;
-  ja.vertex = vertex;
-  ja.g_pose = a->grad_pose_rotvecs;
-  ja.g_glob = a->grad_glob_rotmats;
-  ja.g_rel = a->grad_rel_rotmats;
-  ja.g_betas = a->grad_shape_betas;
-  ja.g_trans = a->grad_trans;
-  ja.g_kid = a->grad_kid_factor;
-  hipLaunchKernelGGL(k_bwd_joint, dim3((B + 63) / 64), dim3(64), 0, st, d, bw, ja, B);
+  const ForwardInputs in = forward_inputs(*a);
+  if (int rc = check_forward_inputs(who, h->d, in)) return rc;
+  Arena ar{(char*)a->workspace};
+  const BackwardLayout l = backward_layout(h->t, B, ar);
+  Cotangents ct;
+  ct.vertices = a->grad_vertices;
+  ct.joints = a->grad_joints;
+  ct.orient = a->grad_orientations;
+  if (int rc = launch_forward_backward(h, in, backward_nb(in), ct, grad_outputs(*a), l, B, (hipStream_t)a->hip_stream)) return rc;
   return post_launch_check();
 }
 
-// The loss sums live in LDS (k_obj_vertex): the workspace is the backward's.
 size_t smplfit_mesh_objective_workspace_bytes(const smplfit_handle* h, int batch) {
   return smplfit_forward_backward_workspace_bytes(h, batch);
 }
 
-// the backward's workspace, then the (B, J, 3) joint cotangent of k_obj_joint
-size_t fit_objective_carve(const smplfit_handle* h, int B, char* base, Workspace* ws, BwdWorkspace* bw, float** gjoints) {
-  const size_t off = align_up(forward_backward_carve(h, B, base, ws, bw), 256);
-  *gjoints = base ? (float*)(base + off) : nullptr;
-  return align_up(off + (size_t)B * h->t.J * 3 * 4, 256);
-}
-
 size_t smplfit_fit_objective_workspace_bytes(const smplfit_handle* h, int batch) {
   if (!h || batch <= 0) return 0;
-  Workspace ws;
-  BwdWorkspace bw;
-  float* gj;
-  return fit_objective_carve(h, batch, nullptr, &ws, &bw, &gj);
-}
-
-// Both objective entry points: `a` carries the fields of either struct; `joints` = the call is
-// smplfit_fit_objective_f32 (its own workspace size; the joint term runs when target_joints is given).
-static int objective_impl(const smplfit_handle* h, const smplfit_fit_objective_args* a, bool joints) {
-  const std::string who = joints ? "smplfit_fit_objective_f32" : "smplfit_mesh_objective_f32";
-  if (!h) return fail(SMPLFIT_ERR_BAD_ARG, who + ": null handle");
-  if (!h->has_device) return fail(SMPLFIT_ERR_HIP, "handle was created host-only (no device)");
-  const int B = a->batch;
-  if (B <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "batch must be positive");
-  if (!a->workspace || ((uintptr_t)a->workspace & 255))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
-  if (joints) {
-    if (a->workspace_bytes < smplfit_fit_objective_workspace_bytes(h, B))
-      return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (smplfit_fit_objective_workspace_bytes)");
-  } else if (a->workspace_bytes < smplfit_mesh_objective_workspace_bytes(h, B)) {
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (smplfit_mesh_objective_workspace_bytes)");
-  }
-  const DevModel& d = h->d;
-  if (int rc = check_forward_inputs(who.c_str(), d, a->pose_rotvecs, a->glob_rotmats, a->rel_rotmats, a->shape_betas,
-                                    a->num_betas_given, a->kid_factor))
-    return rc;
-  if (!a->target_vertices) return fail(SMPLFIT_ERR_BAD_ARG, who + ": target_vertices is required");
-  if (a->joint_weights && !a->target_joints)
-    return fail(SMPLFIT_ERR_BAD_ARG, who + ": joint_weights without target_joints");
-  if (!a->loss) return fail(SMPLFIT_ERR_BAD_ARG, who + ": loss output is required");
-  hipStream_t st = (hipStream_t)a->hip_stream;
-  Workspace ws;
-  BwdWorkspace bw;
-  float* gjoints = nullptr;
-  if (joints) fit_objective_carve(h, B, (char*)a->workspace, &ws, &bw, &gjoints);
-  else forward_backward_carve(h, B, (char*)a->workspace, &ws, &bw);
-  const int nb = a->shape_betas ? std::max(0, a->num_betas_given) : 0;
-  // the posed pass of the backward: the joint block (G | t) without trans (k_obj_vertex adds it) and v_posed
-  ForwardArgs fa{};
-  fa.pose = a->pose_rotvecs;
-  fa.glob = a->glob_rotmats;
-  fa.rel = a->rel_rotmats;
-  fa.betas = a->shape_betas;
-  fa.nb = nb;
-  fa.kid = a->kid_factor;
-  fa.trans = nullptr;
-  fa.joints = ws.rjoints;
-  fa.orient = nullptr;
-  if (int rc = launch_posed_pass(h, route_of(h, B, {Entry::kForwardBackward}), {&fa, {}}, ws, B, st)) return rc;
-  const ObjArgs oa{a->target_vertices, a->vertex_weights, a->trans, a->scale, a->loss};
-  hipLaunchKernelGGL(k_obj_vertex, dim3(B), dim3(256), bwd_vertex_lds_bytes(d, true), st, d, ws, bw, B, nb,
-                     a->shape_betas, a->kid_factor, oa);
-  launch_bwd_reduce(d, bw, B, st);
-  JointBwdArgs ja{};
-  if (a->target_joints) {
-    // the joint term: cotangent to the workspace, loss added behind k_obj_vertex's (stream order)
-    const ObjJointArgs oj{ws.rjoints, a->trans, a->target_joints, a->joint_weights, a->joint_scale, gjoints, a->loss};
-    hipLaunchKernelGGL(k_obj_joint, dim3((B + 63) / 64), dim3(64), 0, st, oj, B, d.J);
-    ja.gjoints = gjoints;
-  }
-  ja.pose = a->pose_rotvecs;
-  ja.glob = a->glob_rotmats;
-  ja.rel = a->rel_rotmats;
-  ja.betas = a->shape_betas;
-  ja.kid = a->kid_factor;
-  ja.nb = nb;
-  ja.vertex = true;
-  ja.g_pose = a->grad_pose_rotvecs;
-  ja.g_glob = a->grad_glob_rotmats;
-  ja.g_rel = a->grad_rel_rotmats;
-  ja.g_betas = a->grad_shape_betas;
-  ja.g_trans = a->grad_trans;
-  ja.g_kid = a->grad_kid_factor;
-  hipLaunchKernelGGL(k_bwd_joint, dim3((B + 63) / 64), dim3(64), 0, st, d, bw, ja, B);
-  return post_launch_check();
+  Arena ar{nullptr};
+  objective_layout(h->t, batch, ar);
+  return ar.off;
 }
 
 int smplfit_mesh_objective_f32(const smplfit_handle* h, const smplfit_mesh_objective_args* a) {
   if (!a) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_mesh_objective_f32: null arguments");
-  smplfit_fit_objective_args f{};
-  f.pose_rotvecs = a->pose_rotvecs; f.glob_rotmats = a->glob_rotmats; f.rel_rotmats = a->rel_rotmats;
-  f.shape_betas = a->shape_betas; f.num_betas_given = a->num_betas_given; f.trans = a->trans;
-  f.kid_factor = a->kid_factor; f.batch = a->batch; f.target_vertices = a->target_vertices;
-  f.vertex_weights = a->vertex_weights; f.scale = a->scale; f.loss = a->loss;
-  f.grad_pose_rotvecs = a->grad_pose_rotvecs; f.grad_glob_rotmats = a->grad_glob_rotmats;
-  f.grad_rel_rotmats = a->grad_rel_rotmats; f.grad_shape_betas = a->grad_shape_betas; f.grad_trans = a->grad_trans;
-  f.grad_kid_factor = a->grad_kid_factor;
-  f.workspace = a->workspace; f.workspace_bytes = a->workspace_bytes; f.hip_stream = a->hip_stream;
-  return objective_impl(h, &f, false);
+  return objective_impl("smplfit_mesh_objective_f32", h, *a, nullptr, smplfit_mesh_objective_workspace_bytes(h, a->batch),
+                        "smplfit_mesh_objective_workspace_bytes");
 }
 
 int smplfit_fit_objective_f32(const smplfit_handle* h, const smplfit_fit_objective_args* a) {
   if (!a) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_objective_f32: null arguments");
-  return objective_impl(h, a, true);
+  const JointTerm jt{a->target_joints, a->joint_weights, a->joint_scale};
+  return objective_impl("smplfit_fit_objective_f32", h, *a, &jt, smplfit_fit_objective_workspace_bytes(h, a->batch),
+                        "smplfit_fit_objective_workspace_bytes");
 }
 
 int smplfit_shape_solve_f32(const smplfit_handle* h, const float* glob_rotmats,
@@ -2848,7 +2906,8 @@ int smplfit_shape_solve_f32(const smplfit_handle* h, const float* glob_rotmats,
 int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solve_args* args) {
   if (!args) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_shape_solve_ex_f32: null arguments");
   const int batch = args->batch;
-  int rc = check_common(h, batch, args->workspace, args->workspace_bytes);
+  int rc = check_call("smplfit_shape_solve_f32", h, batch, args->workspace, args->workspace_bytes, smplfit_workspace_bytes(h, batch),
+                      "smplfit_workspace_bytes");
   if (rc) return rc;
   if (!args->glob_rotmats || !args->target_vertices || !args->shape_betas || !args->trans)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_shape_solve_f32: null pointer");
@@ -2864,8 +2923,7 @@ int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solv
   const DevModel& d = h->d;
   const float *vertex_weights = args->vertex_weights, *joint_weights = args->joint_weights;
   hipStream_t st = (hipStream_t)args->hip_stream;
-  Workspace ws;
-  carve(h->t, batch, (char*)args->workspace, &ws);
+  const Workspace ws = fit_workspace(h, batch, args->workspace);
   const bool joints = args->target_joints != nullptr;
   const SolveWeights w = solve_weights(joints, vertex_weights, joint_weights);
   FitOptions o{1, args->beta_regularizer, args->beta_regularizer2, args->kid_regularizer, 0, 0};
@@ -2914,52 +2972,23 @@ int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solv
   return post_launch_check();
 }
 
-// the backward's workspace (the three vector-Jacobian products run in it), then AdjWorkspace
-size_t shape_solve_backward_carve(const smplfit_handle* h, int B, char* base, Workspace* ws, AdjWorkspace* aw, size_t* fb_bytes) {
-  const sf::HostTables& t = h->t;
-  BwdWorkspace bw;
-  size_t off = align_up(forward_backward_carve(h, B, base, ws, &bw), 256);
-  *fb_bytes = off;
-  auto take = [&](size_t floats) {
-    size_t o = off;
-    off = align_up(off + floats * 4, 256);
-    return base ? (float*)(base + o) : nullptr;
-  };
-  aw->lam = take((size_t)B * (t.S + 3));
-  aw->lamb = take((size_t)B * std::max(1, t.num_betas()));
-  aw->lamk = take((size_t)B);
-  aw->c1 = take((size_t)B * t.V * 3);
-  aw->c2 = take((size_t)B * t.V * 3);
-  aw->c1j = take((size_t)B * t.J * 3);
-  aw->c2j = take((size_t)B * t.J * 3);
-  aw->g1 = take((size_t)B * t.J * 9);
-  aw->g2 = take((size_t)B * t.J * 9);
-  aw->g3 = take((size_t)B * t.J * 9);
-  return off;
-}
-
 size_t smplfit_shape_solve_backward_workspace_bytes(const smplfit_handle* h, int batch) {
   if (!h || batch <= 0) return 0;
-  Workspace ws;
-  AdjWorkspace aw;
-  size_t fb;
-  return shape_solve_backward_carve(h, batch, nullptr, &ws, &aw, &fb);
+  Arena ar{nullptr};
+  adjoint_layout(h->t, batch, ar);
+  return ar.off;
 }
 
 int smplfit_shape_solve_backward_f32(const smplfit_handle* h, const smplfit_shape_solve_backward_args* a) {
   const char* who = "smplfit_shape_solve_backward_f32";
   if (!a) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
-  if (!h) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null handle");
-  if (!h->has_device) return fail(SMPLFIT_ERR_HIP, "handle was created host-only (no device)");
   const int B = a->batch;
-  if (B <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "batch must be positive");
+  if (int rc = check_call(who, h, B, a->workspace, a->workspace_bytes, smplfit_shape_solve_backward_workspace_bytes(h, B),
+                          "smplfit_shape_solve_backward_workspace_bytes"))
+    return rc;
   const DevModel& d = h->d;
   if (d.S > sf::kAdjMaxUnknowns)
     return fail(SMPLFIT_ERR_UNSUPPORTED, std::string(who) + ": more than 17 shape unknowns");
-  if (!a->workspace || ((uintptr_t)a->workspace & 255))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
-  if (a->workspace_bytes < smplfit_shape_solve_backward_workspace_bytes(h, B))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (smplfit_shape_solve_backward_workspace_bytes)");
   if (!a->glob_rotmats || !a->target_vertices || !a->shape_betas || !a->trans)
     return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null pointer");
   if (d.jt.n_kid && !a->kid_factor) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": a kid handle needs kid_factor");
@@ -2974,10 +3003,10 @@ int smplfit_shape_solve_backward_f32(const smplfit_handle* h, const smplfit_shap
   if (bref && (a->num_reference_betas < 0 || a->num_reference_betas > nb))
     return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": num_reference_betas must lie in [0, the model's betas]; slice first");
   hipStream_t st = (hipStream_t)a->hip_stream;
-  Workspace ws;
-  AdjWorkspace aw;
-  size_t fb_bytes;
-  shape_solve_backward_carve(h, B, (char*)a->workspace, &ws, &aw, &fb_bytes);
+  Arena ar{(char*)a->workspace};
+  const AdjointLayout l = adjoint_layout(h->t, B, ar);
+  const Workspace& ws = l.fb.ws;
+  const AdjWorkspace& aw = l.aw;
   const bool joints = a->target_joints != nullptr;
   const SolveWeights w = solve_weights(joints, a->vertex_weights, a->joint_weights);
   AdjArgs k{};
@@ -3020,31 +3049,23 @@ int smplfit_shape_solve_backward_f32(const smplfit_handle* h, const smplfit_shap
   if (vertex_pass || k.o_tj || k.o_jw)
     hipLaunchKernelGGL(k_adj_apply, dim3(B), dim3(256), adj_apply_lds_bytes(d), st, d, ws, k, aw, B, vertex_pass ? 1 : 0);
   if (k.want_glob) {
-    // three vector-Jacobian products of the forward at given rotations
-    smplfit_forward_backward_args f{};
-    f.glob_rotmats = a->glob_rotmats;
-    f.batch = B;
-    f.workspace = a->workspace;
-    f.workspace_bytes = fb_bytes;
-    f.hip_stream = a->hip_stream;
-    f.shape_betas = nb ? a->shape_betas : nullptr;
-    f.num_betas_given = nb;
-    f.kid_factor = a->kid_factor;
-    f.grad_vertices = aw.c1;
-    f.grad_joints = joints ? aw.c1j : nullptr;
-    f.grad_glob_rotmats = aw.g1;
-    if (int rc = smplfit_forward_backward_f32(h, &f)) return rc;
-    f.shape_betas = nb ? aw.lamb : nullptr;
-    f.kid_factor = d.jt.n_kid ? aw.lamk : nullptr;
-    f.grad_vertices = aw.c2;
-    f.grad_joints = joints ? aw.c2j : nullptr;
-    f.grad_glob_rotmats = aw.g2;
-    if (int rc = smplfit_forward_backward_f32(h, &f)) return rc;
-    f.shape_betas = nullptr;
-    f.num_betas_given = 0;
-    f.kid_factor = nullptr;
-    f.grad_glob_rotmats = aw.g3;
-    if (int rc = smplfit_forward_backward_f32(h, &f)) return rc;
+    // three vector-Jacobian products of the forward at given rotations: at the solution with the
+    // cotangents c1, at the multipliers with c2, and at zero shape with c2 — each recomputes its posed pass
+    ForwardInputs in{};
+    in.glob = a->glob_rotmats;
+    GradOutputs out{};
+    Cotangents ct;
+    const auto vjp = [&](const float* betas, const float* kid, const float* cv, const float* cj, float* g) {
+      in.betas = nb ? betas : nullptr;
+      in.kid = kid;
+      ct.vertices = cv;
+      ct.joints = joints ? cj : nullptr;
+      out.glob = g;
+      return launch_forward_backward(h, in, in.betas ? nb : 0, ct, out, l.fb, B, st);
+    };
+    if (int rc = vjp(a->shape_betas, a->kid_factor, aw.c1, aw.c1j, aw.g1)) return rc;
+    if (int rc = vjp(aw.lamb, d.jt.n_kid ? aw.lamk : nullptr, aw.c2, aw.c2j, aw.g2)) return rc;
+    if (int rc = vjp(nullptr, nullptr, aw.c2, aw.c2j, aw.g3)) return rc;
     const size_t n = (size_t)B * d.J * 9;
     hipLaunchKernelGGL(k_adj_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, aw.g1, aw.g2, aw.g3,
                        a->grad_glob_rotmats, n);
@@ -3157,9 +3178,11 @@ int smplfit_convert_f32(const smplfit_convert_plan* p, const smplfit_convert_arg
   const CallShape conv{Entry::kConvert, false};
   if (!route_of(p->in, 1, conv).bm || !route_of(p->out, a->batch, conv).bm)
     return fail(SMPLFIT_ERR_UNSUPPORTED, "smplfit_convert_f32: the batch-major path is switched off");
+  if (int rc = check_call("smplfit_convert_f32", p->out, a->batch, a->workspace, a->workspace_bytes,
+                          smplfit_convert_workspace_bytes(p, a->batch), "smplfit_convert_workspace_bytes"))
+    return rc;
   smplfit_fit_args f = fused_fit_args(*a);
   f.workspace = a->workspace;
-  f.workspace_bytes = a->workspace_bytes;
   ConvertJob job{p, a->pose_rotvecs, a->shape_betas, a->trans, a->shape_betas ? a->num_betas_given : 0, nullptr};
   return fit_impl(p->out, &f, &job);
 }
@@ -3208,37 +3231,36 @@ void smplfit_flip_plan_destroy(smplfit_flip_plan* p) {
 
 size_t smplfit_flip_workspace_bytes(const smplfit_flip_plan* p, int batch) {
   if (!p || batch <= 0) return 0;
-  return flip_pose_bytes(p->conv.out, batch) + chunked_workspace_bytes(p->conv.out->t, batch, &p->conv.in->t);
+  Arena ar{nullptr};
+  flip_layout(p->conv, batch, ar);
+  return ar.off;
 }
 
 int smplfit_flip_f32(const smplfit_flip_plan* p, const smplfit_flip_args* a) {
   if (!p || !a) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: null argument");
   const smplfit_handle* h = p->conv.out;
   const int B = a->batch;
+  if (int rc = check_call("smplfit_flip_f32", h, B, a->workspace, a->workspace_bytes, smplfit_flip_workspace_bytes(p, B),
+                          "smplfit_flip_workspace_bytes"))
+    return rc;
   if (!a->pose_rotvecs) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: pose_rotvecs is required");
-  if (B <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: batch must be positive");
   if (a->shape_betas && (a->num_betas_given < 0 || a->num_betas_given > h->t.num_betas()))
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: more betas than the model holds; slice first");
   if (!a->out_pose_rotvecs || !a->out_shape_betas || !a->out_trans)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: null output pointer");
   if (a->num_iter < 1) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_flip_f32: num_iter must be >= 1");
-  if (!a->workspace || ((uintptr_t)a->workspace & 255))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
-  if (a->workspace_bytes < smplfit_flip_workspace_bytes(p, B))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (see smplfit_flip_workspace_bytes)");
   // the plan was made while the batch-major path applied; a later smplfit_reload_options may have switched it off
   const CallShape conv{Entry::kConvert, false};
   if (!route_of(h, B, conv).bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "smplfit_flip_f32: the batch-major path is switched off");
   hipStream_t st = (hipStream_t)a->hip_stream;
-  const size_t pose_bytes = flip_pose_bytes(h, B);
-  float* init_pose = (float*)a->workspace;
-  hipLaunchKernelGGL(k_naive_flip, dim3((B + 255) / 256), dim3(256), 0, st, a->pose_rotvecs, p->d_perm, init_pose, B, h->t.J);
+  Arena ar{(char*)a->workspace};
+  const FlipLayout l = flip_layout(p->conv, B, ar);
+  hipLaunchKernelGGL(k_naive_flip, dim3((B + 255) / 256), dim3(256), 0, st, a->pose_rotvecs, p->d_perm, l.init_pose, B, h->t.J);
   smplfit_fit_args f = fused_fit_args(*a);
-  f.initial_pose_rotvecs = init_pose;
+  f.initial_pose_rotvecs = l.init_pose;
   f.initial_shape_betas = a->shape_betas;
   f.num_initial_betas = a->shape_betas ? a->num_betas_given : 0;
-  f.workspace = (char*)a->workspace + pose_bytes;
-  f.workspace_bytes = a->workspace_bytes - pose_bytes;
+  f.workspace = l.fit;
   ConvertJob job{&p->conv, a->pose_rotvecs, a->shape_betas, a->trans, a->shape_betas ? a->num_betas_given : 0,
                  a->kid_factor};
   return fit_impl(h, &f, &job);
@@ -3297,7 +3319,9 @@ void smplfit_replace_hands_plan_destroy(smplfit_replace_hands_plan* p) {
 
 size_t smplfit_replace_hands_workspace_bytes(const smplfit_replace_hands_plan* p, int batch) {
   if (!p || batch <= 0) return 0;
-  return replace_front(p->h, batch, nullptr).bytes + chunked_workspace_bytes(p->h->t, batch);
+  Arena ar{nullptr};
+  replace_layout(p->h->t, batch, ar);
+  return ar.off;
 }
 
 int smplfit_replace_hands_f32(const smplfit_replace_hands_plan* p, const smplfit_replace_hands_args* a) {
@@ -3305,22 +3329,20 @@ int smplfit_replace_hands_f32(const smplfit_replace_hands_plan* p, const smplfit
   const smplfit_handle* h = p->h;
   const DevModel& d = h->d;
   const int B = a->batch;
+  if (int rc = check_call("smplfit_replace_hands_f32", h, B, a->workspace, a->workspace_bytes,
+                          smplfit_replace_hands_workspace_bytes(p, B), "smplfit_replace_hands_workspace_bytes"))
+    return rc;
   if (!a->vertices || !a->out_vertices) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_replace_hands_f32: vertices and out_vertices are required");
-  if (B <= 0) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_replace_hands_f32: batch must be positive");
   if (a->num_iter < 1) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_replace_hands_f32: num_iter must be >= 1");
-  if (!a->workspace || ((uintptr_t)a->workspace & 255))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
-  if (a->workspace_bytes < smplfit_replace_hands_workspace_bytes(p, B))
-    return fail(SMPLFIT_ERR_WORKSPACE, "workspace too small (see smplfit_replace_hands_workspace_bytes)");
   // the plan was made while the batch-major forward applied; a later smplfit_reload_options may have switched it off
   const Route rf = route_of(h, B, {Entry::kForward});
   if (!rf.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "smplfit_replace_hands_f32: the batch-major path is switched off");
   hipStream_t st = (hipStream_t)a->hip_stream;
-  const ReplaceFront fr = replace_front(h, B, (char*)a->workspace);
+  Arena ar{(char*)a->workspace};
+  const ReplaceLayout fr = replace_layout(h->t, B, ar);
   float* pose = a->out_pose_rotvecs ? a->out_pose_rotvecs : fr.pose;
   float* betas = a->out_shape_betas ? a->out_shape_betas : fr.betas;
   float* trans = a->out_trans ? a->out_trans : fr.trans;
-  char* wsbase = (char*)a->workspace + fr.bytes;
   smplfit_fit_args f{};
   f.target_vertices = a->vertices;
   f.vertex_weights = p->d_fitw;
@@ -3333,8 +3355,7 @@ int smplfit_replace_hands_f32(const smplfit_replace_hands_plan* p, const smplfit
   f.shape_betas = betas;
   f.trans = trans;
   f.relative_orientations = fr.rel;
-  f.workspace = wsbase;
-  f.workspace_bytes = a->workspace_bytes - fr.bytes;
+  f.workspace = fr.fit;
   f.hip_stream = a->hip_stream;
   if (int rc = fit_impl(h, &f, nullptr, true)) return rc;
   {
@@ -3343,14 +3364,11 @@ int smplfit_replace_hands_f32(const smplfit_replace_hands_plan* p, const smplfit
                        a->out_pose_rotvecs, B, d.J, p->j0, p->n);
   }
   // the forward at the edited relative rotations (the fit's chunks have been joined: one pass over the whole batch)
-  Workspace ws;
-  carve(h->t, B, wsbase, &ws);
-  ForwardArgs fa{};
-  fa.rel = fr.rel;
-  fa.betas = betas;
-  fa.nb = d.S - d.jt.n_kid - d.jt.n_pad;
-  fa.trans = trans;
-  fa.joints = ws.rjoints;
+  const Workspace ws = fit_workspace(h, B, fr.fit);
+  ForwardInputs in{};
+  in.rel = fr.rel;
+  in.betas = betas;
+  const ForwardArgs fa = forward_args(in, d.S - d.jt.n_kid - d.jt.n_pad, trans, ws.rjoints, nullptr);
   launch_forward_joint(d, fa, ws, B, st);
   if (int rc = launch_posed_pass(h, rf, {nullptr, mesh_blended(&fa, a->out_vertices, a->vertices, p->d_mix)}, ws, B, st)) return rc;
   return post_launch_check();
@@ -3365,13 +3383,13 @@ int smplfit_reload_options(void) {
 int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, int reps,
                             void* workspace, size_t workspace_bytes, void* hip_stream,
                             float* avg_ms) {
-  int rc = check_common(h, batch, workspace, workspace_bytes);
+  int rc = check_call("smplfit_time_kernel_f32", h, batch, workspace, workspace_bytes, smplfit_workspace_bytes(h, batch),
+                      "smplfit_workspace_bytes");
   if (rc) return rc;
   if (!avg_ms || reps < 1) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_time_kernel_f32: bad argument");
   const DevModel& d = h->d;
   hipStream_t st = (hipStream_t)hip_stream;
-  Workspace ws;
-  carve(h->t, batch, (char*)workspace, &ws);
+  const Workspace ws = fit_workspace(h, batch, workspace);
   hipEvent_t e0, e1;
   SF_HIP_TRY(hipEventCreate(&e0));
   SF_HIP_TRY(hipEventCreate(&e1));

@@ -317,3 +317,39 @@ def test_reload_options(lib, monkeypatch, model_root, golden):
     _lib.reload_options()
     assert lib.smplfit_pick_share_mult(h.ptr, 0, 4096) == 1
     h.close()
+
+
+# (model, kid, B) -> smplfit_workspace_bytes, smplfit_forward_backward_workspace_bytes, adjoint - forward_backward.
+# Recorded from the build in front of the commit that states every layout once on one arena; a change that alters a
+# layout on purpose updates them.
+WORKSPACE_PINS = {
+    ('smpl', False, 1): (85467904, 85576448, 170240),
+    ('smpl', False, 65): (98816000, 105824512, 10962176),
+    ('smpl', False, 129): (197417984, 211326464, 21754112),
+    ('smpl', True, 65): (102907648, 109921792, 10962432),
+    ('smplx', False, 65): (127319808, 140493056, 16820736),
+    ('smplx', False, 129): (254309632, 280452608, 33381120),
+}
+
+
+@pytest.mark.parametrize('name,kid', [('smpl', False), ('smpl', True), ('smplx', False)])
+def test_workspace_layout_queries(lib, name, kid, model_root, golden):
+    """The five handle-level workspace queries of a host-only handle at B = 1, 64, 65, 129: the mesh objective takes the
+    backward's workspace, the fit objective adds one 256-byte aligned (B, J, 3) cotangent, the adjoint adds its own
+    regions behind the backward's, and the sizes are the recorded ones."""
+    import hostemu_util as H
+
+    kind, md = util.load_md(model_root, name, golden(name))
+    desc, keep = H.desc_from_md(md, kind, enable_kid=kid)
+    h = _lib.Handle(desc, host_only=True)
+    J = h.info.num_joints
+    for B in (1, 64, 65, 129):
+        fit, fb = h.workspace_bytes(B), h.forward_backward_workspace_bytes(B)
+        adj = h.shape_solve_backward_workspace_bytes(B)
+        assert fit > 0 and fb > fit
+        assert h.mesh_objective_workspace_bytes(B) == fb
+        assert h.fit_objective_workspace_bytes(B) - fb == (12 * B * J + 255) // 256 * 256
+        assert adj > fb
+        if (name, kid, B) in WORKSPACE_PINS:
+            assert (fit, fb, adj - fb) == WORKSPACE_PINS[name, kid, B], (name, kid, B)
+    h.close()

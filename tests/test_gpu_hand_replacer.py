@@ -238,3 +238,47 @@ def test_errors(gh, dev, smplfit_env):
     _lib.check(lib.smplfit_replace_hands_f32(plan.ptr, C.byref(args)))
     torch.cuda.synchronize()
     assert torch.equal(out, hr.replace_hand(verts))
+
+
+def test_replace_hands_guards(gh, dev, smplfit_env):
+    """smplfit_replace_hands_f32 at B = 65 with the parameter outputs NULL (the regions at the front of the workspace
+    take the fit's results), out_vertices and a workspace of exactly the queried size each between two 1 MB guard
+    regions, the output pre-filled with NaN, the workspace once zeroed and once filled with a NaN pattern: every guard
+    byte survives, every output element is written and finite, the two fills give the same bits.  A workspace one byte
+    short is refused before anything is enqueued."""
+    from smplfitter_amd import _lib
+    from test_gpu_flipper import _guarded, _intact
+
+    hr = fused(get_replacer(gh, dev), dev, smplfit_env)
+    B = 65
+    verts = meshes(hr, B, 41, dev)
+    plan, lib = hr._plan(dev), _lib.load()
+    nws = plan.workspace_bytes(B)
+    mk = lambda out, ws, n: _lib.ReplaceHandsArgs(  # noqa: E731
+        vertices=verts.data_ptr(), batch=B, num_iter=3, beta_regularizer=1.0, final_adjust_rots=1,
+        out_vertices=out.data_ptr(), workspace=ws.data_ptr(), workspace_bytes=n,
+        hip_stream=torch.cuda.current_stream(dev).cuda_stream)
+    res = {}
+    for fill in ('zero', 'nan'):
+        obuf, out = _guarded(4 * verts.numel(), dev)
+        out.view(torch.float32).fill_(float('nan'))
+        wbuf, ws = _guarded(nws, dev)
+        assert ws.data_ptr() % 256 == 0
+        if fill == 'zero':
+            ws.zero_()
+        else:
+            ws.view(torch.int32)[: nws // 4].fill_(0x7FC00000 | 0x1234)
+        _lib.check(lib.smplfit_replace_hands_f32(plan.ptr, C.byref(mk(out, ws, nws))))
+        torch.cuda.synchronize()
+        assert _intact(wbuf, nws), 'workspace guard written'
+        assert _intact(obuf, out.numel()), 'guard region of out_vertices written'
+        assert bool(torch.isfinite(out.view(torch.float32)).all()), 'out_vertices: an element was not written'
+        res[fill] = out.clone()
+        del obuf, out, wbuf, ws
+    assert torch.equal(res['zero'], res['nan'])
+    assert not torch.equal(res['zero'].view(torch.float32).view_as(verts), verts)  # (the hands were replaced)
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    out = torch.full_like(verts, float('nan'))
+    assert lib.smplfit_replace_hands_f32(plan.ptr, C.byref(mk(out, ws, nws - 1))) == _lib.SMPLFIT_ERR_WORKSPACE
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out).all())  # nothing was enqueued

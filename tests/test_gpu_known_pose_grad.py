@@ -254,3 +254,73 @@ def test_refusals_and_poisoned_row(model_root, golden, dev):
     for k in clean:
         assert np.array_equal(clean[k][[0, 2]], bad[k][[0, 2]]), k
     assert np.isnan(bad['vertex_weights'][1]).any()  # (delta . res: the residual of the poisoned row)
+
+
+@pytest.mark.parametrize('name,B', [('smpl', 65), ('smplxfat', 5)])
+def test_shape_solve_backward_guards(name, B, model_root, golden, dev):
+    """smplfit_shape_solve_backward_f32 called directly on case e (target joints, both weight kinds, a kid handle, both
+    ridge references) with every gradient output requested, so that every region of its workspace is used and the three
+    backward passes run; B = 65: a second, partial block of k_bwd_joint; smplxfat: more than 32 joints.  Every output
+    and a workspace of exactly the queried size lie between two 1 MB guard regions, the outputs pre-filled with NaN, the
+    workspace once zeroed and once filled with a NaN pattern: every guard byte survives, every output element is
+    written and finite, the two fills give the same bits.  A workspace one byte short is refused before anything is
+    enqueued."""
+    import ctypes as C
+
+    from smplfitter_amd import _lib
+    from test_gpu_flipper import _guarded, _intact
+
+    m, md, m64, g = _model(name, model_root, golden, dev)
+    x, kw, kid = ku.case_inputs(g, 'e', B, seed=B)
+    assert kid
+    f = _fitter(name, kid, model_root, golden, dev)
+    ts = {k: _t(v, dev) for k, v in x.items()}
+    with torch.no_grad():
+        r = f.fit_with_known_pose(**ts, **kw)
+    cot = {k: _t(v, dev) for k, v in ku.cotangents(B, B, 10, kid).items()}
+    J, V, nref = m.num_joints, m.num_vertices, x['beta_regularizer_reference'].shape[1]
+    G = r['orientations'].contiguous()
+    h = m._native(dev, kid=True)
+    nws = h.shape_solve_backward_workspace_bytes(B)
+    assert nws > h.forward_backward_workspace_bytes(B)
+    sizes = dict(glob_rotmats=B * J * 9, target_vertices=B * V * 3, target_joints=B * J * 3, vertex_weights=B * V,
+                 joint_weights=B * J, beta_regularizer_reference=B * nref, kid_regularizer_reference=B)
+    lib = _lib.load()
+    mk = lambda outs, ws, n: _lib.ShapeSolveBackwardArgs(  # noqa: E731
+        glob_rotmats=G.data_ptr(), target_vertices=ts['target_vertices'].data_ptr(),
+        target_joints=ts['target_joints'].data_ptr(), vertex_weights=ts['vertex_weights'].data_ptr(),
+        joint_weights=ts['joint_weights'].data_ptr(), beta_regularizer=kw['beta_regularizer'],
+        beta_regularizer2=kw['beta_regularizer2'], kid_regularizer=kw['kid_regularizer'],
+        beta_regularizer_reference=ts['beta_regularizer_reference'].data_ptr(), num_reference_betas=nref,
+        kid_regularizer_reference=ts['kid_regularizer_reference'].data_ptr(), batch=B,
+        shape_betas=r['shape_betas'].data_ptr(), trans=r['trans'].data_ptr(), kid_factor=r['kid_factor'].data_ptr(),
+        grad_shape_betas=cot['shape_betas'].data_ptr(), grad_trans=cot['trans'].data_ptr(),
+        grad_kid_factor=cot['kid_factor'].data_ptr(), workspace=ws.data_ptr(), workspace_bytes=n,
+        hip_stream=torch.cuda.current_stream(dev).cuda_stream,
+        **{f'grad_{k}': o.data_ptr() for k, o in outs.items()})
+    out = {}
+    for fill in ('zero', 'nan'):
+        bufs = {k: _guarded(4 * n, dev) for k, n in sizes.items()}
+        for _, o in bufs.values():
+            o.view(torch.float32).fill_(float('nan'))
+        wbuf, ws = _guarded(nws, dev)
+        assert ws.data_ptr() % 256 == 0
+        if fill == 'zero':
+            ws.zero_()
+        else:
+            ws.view(torch.int32)[: nws // 4].fill_(0x7FC00000 | 0x1234)
+        _lib.check(lib.smplfit_shape_solve_backward_f32(h.ptr, C.byref(mk({k: o for k, (_, o) in bufs.items()}, ws, nws))))
+        torch.cuda.synchronize()
+        assert _intact(wbuf, nws), 'workspace guard written'
+        for k, (buf, o) in bufs.items():
+            assert _intact(buf, o.numel()), f'guard region of output {k} written'
+            assert bool(torch.isfinite(o.view(torch.float32)).all()), f'output {k}: an element was not written'
+        out[fill] = {k: o.clone() for k, (_, o) in bufs.items()}
+        del bufs, wbuf, ws
+    for k in out['zero']:
+        assert torch.equal(out['zero'][k], out['nan'][k]), k
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    outs = {k: torch.full((n,), float('nan'), device=dev) for k, n in sizes.items()}
+    assert lib.smplfit_shape_solve_backward_f32(h.ptr, C.byref(mk(outs, ws, nws - 1))) == _lib.SMPLFIT_ERR_WORKSPACE
+    torch.cuda.synchronize()
+    assert all(bool(torch.isnan(o).all()) for o in outs.values())  # nothing was enqueued
