@@ -120,6 +120,15 @@ enum smplfit_table_id {
   SMPLFIT_TAB_CELL_COUNTS = 9,     /* (8) cells per instance block of the cell tables below: the four kinds'
                                       coarse tables, then their fine ones (empty: the model has no
                                       batch-major tables)                                          */
+  /* tables derived for single kernels (any model unless noted) */
+  SMPLFIT_TAB_INV_SLOT = 11,       /* (V)  sorted slot of every original vertex                 */
+  SMPLFIT_TAB_PART_SEG_START = 12, /* (J+1) first segment of each part, empty range: unused part */
+  SMPLFIT_TAB_ANC_START = 13,      /* (J+1) CSR offsets into the next table                     */
+  SMPLFIT_TAB_ANC = 14,            /* ancestors of every joint, root first, the joint excluded  */
+  SMPLFIT_TAB_ROT_SLOTS = 15,      /* (J)  the joint's slot among the joints a toe copies its rotation
+                                      from, numbered by ascending toe; -1 = none                */
+  SMPLFIT_TAB_REFINE_WAVES = 16,   /* one value per adjustable part, in level order: the wave (0-7) of the
+                                      batch-major refinement kernel that owns it                */
 };
 int smplfit_get_table(const smplfit_handle* h, int table_id, int32_t* dst, size_t cap, size_t* n);
 
@@ -130,7 +139,11 @@ int smplfit_get_table(const smplfit_handle* h, int table_id, int32_t* dst, size_
  * `what` 0 piece_start (ncells + 1), 1 piece records
  * (npieces + 1, 12): count, joints[4], local slots[4], first slot, row closed behind the piece (-1 none), kind 0:
  * joints of that row | (cell + 1) << 8 behind the last piece of a cell; 2 the rows: part per row (kinds 1-3) or
- * (nrows, 12) joint of every local slot, -1 unused (kind 0). */
+ * (nrows, 12) joint of every local slot, -1 unused (kind 0); 3 aux_start (J + 1) and 4 aux_rows: per joint, CSR, where
+ * the combine kernels find its partial sums — the rows of its part, ascending (kinds 1-3), or the offsets of its
+ * moments in the residual pass's output, ncells * (S + 6) / 4 * 4 + row * 36 + 3 * local slot in (row, slot) order
+ * (kind 0); 5 aux_pad: kind 0 the same as (J, pitch) rows, pitch = the longest run rounded up to 16, -1 behind a
+ * joint's last entry; size 0 for kinds 1-3. */
 int smplfit_get_share_table(const smplfit_handle* h, int kind, int what, int32_t* dst, size_t cap, size_t* n);
 /* Cells per wave a launch over `batch` instances picks for `kind` 0-3 — of the fine table when the batch takes it
  * (with the current tuning options). */

@@ -703,9 +703,7 @@ __global__ __launch_bounds__(64) void k_regress_joints_bm(DevModel m, const floa
 // segment's rows to ws.resP.  The waves never meet: no barrier.
 // Output: ws.resP = [cell][16][Mp] ([r1 : S][Sb : 3]) followed by [segment row][kGQ x 3][Mp] (moments).
 constexpr size_t kResidualLds = (size_t)kBW * kGQ * 3 * 64 * 4;
-// floats of a cell record r1 (S) | Sb (3), padded to a multiple of four: 16 for 10 / 11 unknowns, 20 for 16 / 17
-__host__ __device__ constexpr int res_share_rec(int S) { return (S + 3 + 3) / 4 * 4; }
-constexpr int kResRowRec = 3 * kGQ;
+// (res_share_rec(S), the floats of a cell record, and kResRowRec = 3 kGQ, those of a segment row: sf_tables.h)
 
 #ifndef SMPLFIT_RES_WAVES
 #define SMPLFIT_RES_WAVES 4
@@ -1619,7 +1617,6 @@ __global__ __launch_bounds__(64 * kRefWaves) void k_refine_bm(DevModel m, Refine
 // ------------------------------------------------------------------------------------------------
 constexpr int kRotJoints = 4;   // joints a wave fits per round (their part sums and previous rotations in registers)
 constexpr int kRotMaxJ = 64;    // (three 64-lane requests cover a row of 3 J joint coordinates)
-constexpr int kRotSlots = 8;    // joints whose rotation another joint takes (the feet of the toes) at most
 struct RotArgs {
   const float* tj;    // (B, J, 3) centred target joints (given or regressed)
   const float* rj;    // (B, J, 3) reference joints, or (J, 3) when rj_shared

@@ -63,6 +63,41 @@ struct JointTabs {
   const float *pair_c1, *pair_c2, *pair_c3, *diag_g0, *diag_c2, *diag_c3;
 };
 
+// The JointTabs of a model's tables `t` (sf::HostTables): the scalars, and every array through `ptr` — the library passes "upload the vector, return
+// the device pointer", the host emulation "return vec.data()".
+template <class Tables, class F>
+JointTabs bind_joint_tabs(const Tables& t, F&& ptr) {
+  JointTabs jt{};
+  jt.J = t.J; jt.S = t.S; jt.num_levels = t.num_levels(); jt.adj_last_level = t.adj_last_level;
+  jt.P = t.P; jt.Kp = t.Kp;
+  jt.n_kid = t.n_kid;
+  jt.n_pad = t.n_pad;
+  jt.parents = ptr(t.parents);
+  jt.fk_js = ptr(t.fk_js);
+  jt.fk_level_start = ptr(t.fk_level_start);
+  jt.cas_start = ptr(t.cas_start);
+  jt.cas_flat = ptr(t.cas_flat);
+  jt.part_type = ptr(t.part_type);
+  jt.toe_src = ptr(t.toe_src);
+  jt.adj_level_start = ptr(t.adj_level_start);
+  jt.adj_parts = ptr(t.adj_parts);
+  jt.j_ext = ptr(t.j_ext);
+  jt.bone_ext = ptr(t.bone_ext);
+  jt.fk_jp = ptr(t.fk_jp);
+  jt.bone_lv = ptr(t.bone_lv);
+  jt.cs_joint = ptr(t.cs_joint);
+  jt.cw_joint = ptr(t.cw_joint);
+  jt.np = (int)t.pair_c3.size();
+  jt.pair_j = ptr(t.pair_j);
+  jt.pair_c1 = ptr(t.pair_c1);
+  jt.pair_c2 = ptr(t.pair_c2);
+  jt.pair_c3 = ptr(t.pair_c3);
+  jt.diag_g0 = ptr(t.diag_g0);
+  jt.diag_c2 = ptr(t.diag_c2);
+  jt.diag_c3 = ptr(t.diag_c3);
+  return jt;
+}
+
 // ---------------------------------------------------------------------------------------------
 // LDS carve for the joint-level stages (floats).
 // ---------------------------------------------------------------------------------------------

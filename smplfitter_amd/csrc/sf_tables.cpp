@@ -159,6 +159,75 @@ void build_share_table(const HostTables& t, int kind, ShareTable& out, int cell_
       out.ncells = 0;
     }
 }
+
+// aux_start / aux_rows / aux_pad of one table (see ShareTable)
+void build_share_aux(const HostTables& t, bool residual, ShareTable& st) {
+  st.aux_start.assign(t.J + 1, 0);
+  st.aux_rows.clear();
+  st.aux_pad.clear();
+  for (int j = 0; j < t.J; ++j) {
+    for (int r = 0; r < st.nrows; ++r)
+      if (!residual) {
+        if (st.row_part[r] == j) st.aux_rows.push_back(r);
+      } else {
+        for (int q = 0; q < kGroupJoints; ++q)
+          if (st.row_joints[(size_t)r * kGroupJoints + q] == j)
+            st.aux_rows.push_back((int32_t)(st.ncells * res_share_rec(t.S) + r * kResRowRec + 3 * q));
+      }
+    st.aux_start[j + 1] = (int32_t)st.aux_rows.size();
+  }
+  st.max_aux = 0;
+  for (int j = 0; j < t.J; ++j) st.max_aux = std::max(st.max_aux, st.aux_start[j + 1] - st.aux_start[j]);
+  st.aux_pitch = std::max(16, round_up(st.max_aux, 16));
+  if (residual) {
+    st.aux_pad.assign((size_t)t.J * st.aux_pitch, -1);
+    for (int j = 0; j < t.J; ++j)
+      std::copy(st.aux_rows.begin() + st.aux_start[j], st.aux_rows.begin() + st.aux_start[j + 1],
+                st.aux_pad.begin() + (size_t)j * st.aux_pitch);
+  }
+}
+
+// The tables of the batch-major stage kernels that follow from the tree alone: the ancestor chains of k_prologue_bm,
+// the toe slots of k_rotations_bm, the wave groups of k_refine_bm (see HostTables).
+void build_stage_tables(HostTables& t) {
+  t.anc_start.assign(t.J + 1, 0);
+  t.anc.clear();
+  for (int j = 0; j < t.J; ++j) {
+    std::vector<int32_t> chain;
+    for (int a = j; a > 0;) chain.push_back(a = t.parents[a]);
+    t.anc.insert(t.anc.end(), chain.rbegin(), chain.rend());
+    t.anc_start[j + 1] = (int32_t)t.anc.size();
+  }
+  if (t.anc.empty()) t.anc.push_back(0);
+
+  std::fill(t.rot_slots, t.rot_slots + kMaxJoints, (int8_t)-1);
+  t.rot_nslots = t.rot_toes_per_wave = 0;
+  int toes[kRefWaves] = {};  // toes of one wave of k_rotations_bm (joint j belongs to wave j % kRefWaves)
+  for (int j = 0; j < t.J; ++j) {
+    const int src = t.toe_src[j];
+    if (src < 0) continue;
+    if (t.rot_slots[src] < 0) t.rot_slots[src] = (int8_t)t.rot_nslots++;
+    t.rot_toes_per_wave = std::max(t.rot_toes_per_wave, ++toes[j % kRefWaves]);
+  }
+
+  std::fill(t.refine_waves, t.refine_waves + kRefMaxAdj, (int8_t)0);
+  t.refine_group_max = 1 << 20;
+  const int nadj = t.adj_level_start[t.adj_last_level + 1];
+  if (nadj > kRefMaxAdj) return;
+  std::vector<int> top(nadj), per_wave(kRefWaves, 0);
+  int ntop = 0;
+  t.refine_group_max = 0;
+  for (int ai = 0; ai < nadj; ++ai) {
+    top[ai] = ai;
+    for (int p = t.adj_parts[ai]; p > 0;) {  // up to the root: the group of the nearest adjustable ancestor is the group of the top-most one
+      p = t.parents[p];
+      for (int a2 = 0; a2 < ai; ++a2)
+        if (t.adj_parts[a2] == p && top[ai] == ai) top[ai] = top[a2];
+    }
+    t.refine_waves[ai] = (int8_t)(top[ai] == ai ? (ntop++) % kRefWaves : t.refine_waves[top[ai]]);
+    t.refine_group_max = std::max(t.refine_group_max, ++per_wave[t.refine_waves[ai]]);
+  }
+}
 }  // namespace
 
 void build_share_tables(HostTables& t) {
@@ -193,6 +262,8 @@ void build_share_tables(HostTables& t) {
       t.shares.clear();
       return;
     }
+  // (behind the fallbacks: a table that is a copy of another one gets that one's rows)
+  for (int k = 0; k < 2 * kShareKinds; ++k) build_share_aux(t, k % kShareKinds == kShareResidual, t.shares[k]);
 }
 
 int pick_share_mult(const HostTables& t, int kind, int nblocks, int slots, int wg_waves) {
@@ -355,6 +426,7 @@ std::string build_tables(const smplfit_model_desc& d, HostTables& t, bool* unsup
   for (int i = 0; i < J; ++i)
     if (t.part_type[i] == kPartBone || t.part_type[i] == kPartLeaf || t.adj_flag[i])
       t.used_part[i] = 1;
+  build_stage_tables(t);
 
   // ---- part assignment = argmax skinning weight, toes -> feet (:36-44) ----
   t.part_assignment.assign(V, 0);
@@ -402,9 +474,11 @@ std::string build_tables(const smplfit_model_desc& d, HostTables& t, bool* unsup
   const int Vp = t.Vp;
   t.perm.assign(Vp, -1);
   t.slot_part.assign(Vp, -1);
+  t.inv_slot.assign(V, 0);
   t.n_used = 0;
   for (int i = 0; i < V; ++i) {
     t.perm[i] = order[i];
+    t.inv_slot[order[i]] = i;
     t.slot_part[i] = t.part_assignment[order[i]];
     if (t.used_part[t.slot_part[i]]) t.n_used = i + 1;
   }
@@ -415,6 +489,9 @@ std::string build_tables(const smplfit_model_desc& d, HostTables& t, bool* unsup
     for (int s = i; s < e; s += kTile) t.segments.push_back({s, std::min(kTile, e - s), p});
     i = e;
   }
+  t.part_seg_start.assign(J + 1, 0);  // (the segments are ordered by part id: a part's run starts behind the lower parts')
+  for (const Segment& sg : t.segments) ++t.part_seg_start[sg.part + 1];
+  for (int p = 0; p < J; ++p) t.part_seg_start[p + 1] += t.part_seg_start[p];
 
   // ---- per-slot constants ----
   const int P = t.P;
@@ -590,6 +667,7 @@ std::string build_tables(const smplfit_model_desc& d, HostTables& t, bool* unsup
       for (int s = 0; s < S; ++s)
         t.j_ext[((size_t)j * 3 + c) * S1 + 1 + s] = J_shapedirs[((size_t)j * 3 + c) * S + s];
     }
+  t.j_template.assign(d.J_template, d.J_template + (size_t)J * 3);
   for (int j = 0; j < J; ++j)
     for (int k = 0; k < 3 * S1; ++k)
       t.bone_ext[(size_t)j * 3 * S1 + k] =
@@ -806,13 +884,11 @@ std::string build_tables(const smplfit_model_desc& d, HostTables& t, bool* unsup
   t.reg_rowsum.assign(J, 0.f);
   if (d.J_regressor_post_lbs && d.regressor_num_vertices == V) {
     t.reg_start.assign(1, 0);
-    std::vector<int> slot_of(V);
-    for (int i = 0; i < V; ++i) slot_of[order[i]] = i;
     for (int j = 0; j < J; ++j) {
       std::vector<std::pair<int, float>> row;
       for (int v = 0; v < V; ++v) {
         float r = d.J_regressor_post_lbs[(size_t)j * V + v];
-        if (r != 0.f) row.push_back({slot_of[v], r});
+        if (r != 0.f) row.push_back({t.inv_slot[v], r});
       }
       std::sort(row.begin(), row.end());
       for (auto& e : row) {

@@ -96,6 +96,13 @@ constexpr int kPieceCost = SMPLFIT_PIECE_COST;
 // record is a PAIR of such records — the second one carries joints 4..7 in [1..4] and their local slots in [5..8] (its
 // other fields repeat the first one's): piece_rec() = 24.
 constexpr int kPieceRec = 12;
+// ws.resP, the output of the residual pass (k_residual_bm): per cell a record r1 (S) | Sb (3), padded to a multiple of
+// four floats (16 for 10 / 11 unknowns, 20 for 16 / 17), then per segment row the moments of its local joint slots
+constexpr int res_share_rec(int S) { return (S + 3 + 3) / 4 * 4; }
+constexpr int kResRowRec = 3 * kGroupJoints;
+constexpr int kRefWaves = 8;    // waves per workgroup of k_refine_bm / k_rotations_bm (64 instances; the waves take joints)
+constexpr int kRefMaxAdj = 16;  // adjustable parts k_refine_bm is told the wave of (HostTables::refine_waves)
+constexpr int kRotSlots = 8;    // joints whose rotation another joint takes (the feet of the toes) at most, k_rotations_bm
 enum ShareKind : int {
   kShareResidual = 0,  // all slots; a row = a SEGMENT (run of pieces of one cell whose joints number <= kGroupJoints): moments
   kShareLbsAll = 1,    // all slots; a row = the part sums of a run of one part inside a cell (joints-omitted fits, forward)
@@ -112,6 +119,13 @@ struct ShareTable {
   std::vector<int32_t> pieces;       // (npieces + 1, kPieceRec)
   std::vector<int32_t> row_part;     // (nrows) LBS tables: the part of a row
   std::vector<int32_t> row_joints;   // (nrows, kGroupJoints) residual tables: joint of every local slot, -1 = unused
+  // Where the combine kernels find the partial sums of a joint, CSR over the joints (aux_start (J + 1), aux_rows).  LBS
+  // tables: the rows of ws.psumP of the part, ascending.  Residual tables: the offsets in ws.resP (in rows of Mp
+  // floats) of the joint's moments, ncells * res_share_rec(S) + row * kResRowRec + 3 * local slot, in (row, slot)
+  // order — and the same as (J, aux_pitch) rows, -1 behind a joint's last entry (aux_pad, k_solve_bm).
+  std::vector<int32_t> aux_start, aux_rows, aux_pad;
+  int max_aux = 0;     // longest run of aux_rows
+  int aux_pitch = 16;  // max_aux rounded up to 16, at least 16
 };
 
 struct HostTables {
@@ -143,13 +157,26 @@ struct HostTables {
   std::vector<int32_t> adj_level_start, adj_parts;  // adjustable parts per level (levels as fk)
   int adj_last_level = -1;
   std::vector<int32_t> used_part;       // (J)
+  std::vector<int32_t> anc_start, anc;  // ancestors of every joint from the root down, the joint itself excluded: CSR
+                                        // (J + 1) / one 0 when no joint has one (k_prologue_bm: the FK as a sum along the chain)
+  // k_rotations_bm: a joint's slot among the joints a toe copies (numbered by ascending toe), or -1; their number; the
+  // most toes among the joints j = w (mod kRefWaves) of one wave
+  int8_t rot_slots[kMaxJoints];
+  int rot_nslots = 0, rot_toes_per_wave = 0;
+  // k_refine_bm: the wave of every adjustable part, in adj_parts order.  Parts under one top-most adjustable ancestor
+  // form a group and share a wave (which keeps their part sums in registers); the groups are dealt to the waves in
+  // turn.  refine_group_max: the most parts one wave gets (1 << 20 with more than kRefMaxAdj adjustable parts).
+  int8_t refine_waves[kRefMaxAdj] = {};
+  int refine_group_max = 0;
 
   // vertex ordering
   std::vector<int32_t> part_assignment;  // (V) original order
   std::vector<int32_t> perm;             // (Vp) original index of sorted slot, -1 padding
+  std::vector<int32_t> inv_slot;         // (V) sorted slot of every original vertex
   std::vector<int32_t> slot_part;        // (Vp) part of sorted slot, -1 padding
   int n_used = 0;                        // slots [0, n_used) belong to used parts
   std::vector<Segment> segments;         // part-aligned tiles over [0, n_used)
+  std::vector<int32_t> part_seg_start;   // (J + 1) first segment of each part (empty range: unused part)
 
   // per-slot constants (SoA over Vp)
   std::vector<float> vt;        // (3,Vp)  v_template
@@ -179,6 +206,7 @@ struct HostTables {
 
   // per-joint constants
   std::vector<float> j_ext;     // (J,3,S+1)  [J_template | J_shapedirs]
+  std::vector<float> j_template;  // (J,3)  column 0 of j_ext
   std::vector<float> bone_ext;  // (J,3,S+1)  j_ext - j_ext[parent] (root: j_ext - j_ext[0] = 0)
   // the level FK of the joint stage without dependent table reads: per position of fk_js the packed (joint | parent << 16)
   // and a copy of the joint's bone_ext rows in that order
@@ -245,5 +273,12 @@ std::string build_tables(const smplfit_model_desc& d, HostTables& t, bool* unsup
 // resident waves: the multiplier with the smallest rounds x (share length + prologue) estimate.
 int pick_share_mult(const HostTables& t, int kind, int nblocks, int slots, int wg_waves = kBmWaves);
 void build_share_tables(HostTables& t);
+
+// (n, 3) start, count, part
+inline std::vector<int32_t> flatten(const std::vector<Segment>& segs) {
+  std::vector<int32_t> out;
+  for (const Segment& s : segs) out.insert(out.end(), {s.start, s.count, s.part});
+  return out;
+}
 
 }  // namespace sf

@@ -108,25 +108,47 @@ struct ShareView {
   int aux_pitch;
 };
 
+// The device arrays of one object (a handle, a transfer matrix, a plan): every one is allocated through it — 16 bytes
+// at least — and they are freed together.  A failed call leaves the HIP call and its error in smplfit_last_error().
+struct DeviceArrays {
+  std::vector<void*> ptrs;
+  template <class P>
+  int alloc(size_t bytes, P* dst) {  // uninitialised
+    void* p = nullptr;
+    bytes = std::max<size_t>(bytes, 16);
+    SF_HIP_TRY(hipMalloc(&p, bytes));
+    ptrs.push_back(p);
+    *dst = (P)p;
+    return 0;
+  }
+  template <class T, class P>
+  int upload(const T* src, size_t count, P* dst) {
+    if (int rc = alloc(count * sizeof(T), dst)) return rc;
+    if (count) SF_HIP_TRY(hipMemcpy((void*)*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+  }
+  template <class T, class P>
+  int upload(const std::vector<T>& src, P* dst) { return upload(src.data(), src.size(), dst); }
+  void free_all() {
+    for (void* p : ptrs) (void)hipFree(p);
+    ptrs.clear();
+  }
+};
+
 }  // namespace
 
 constexpr int kMaxChunks = 4;  // batch chunks of one fit call run on the caller's stream + 3 side streams
 
-// k_refine_bm: the wave that owns an adjustable part (parts are grouped by their top-most adjustable ancestor, refine_bm_groups)
-constexpr int kRefMaxAdj = 16;
-struct RefGroups { int8_t wave[kRefMaxAdj]; };
+// k_refine_bm: the wave that owns an adjustable part (sf::HostTables::refine_waves)
+struct RefGroups { int8_t wave[sf::kRefMaxAdj]; };
 
 struct smplfit_handle {
   sf::HostTables t;
   DevModel d{};
   // the cell tables of the batch-major vertex kernels on the device: views[kind]
   std::vector<ShareView> views;
-  std::vector<void*> allocs;
+  DeviceArrays dev;
   bool has_device = false;
-  int refine_group_max = 0;  // most adjustable parts one wave of k_refine_bm gets (groups under one top-most adjustable ancestor)
-  RefGroups refine_groups{};
-  int8_t rot_slots[64];      // k_rotations_bm: a joint's slot among the joints a toe copies, or -1
-  int rot_nslots = 0, rot_toes_per_wave = 0;
   // registers per lane the split-bf16 GEMM kernels were built with (hipFuncGetAttributes at create).  They must own
   // the whole register file of a CU (256 x 8 waves, see k_posedirs_gemm_bf16x3 "exclusive CU"); if a toolchain ever
   // allocates fewer, the fp32-MFMA GEMM is used instead
@@ -145,6 +167,7 @@ struct smplfit_transfer {
   std::vector<float> values;
   int32_t *d_indptr = nullptr, *d_indices = nullptr;
   float* d_values = nullptr;
+  DeviceArrays dev;
   bool negate_x = false;  // SMPLFIT_TRANSFER_NEGATE_X: x -> -x after the product (the mirror of BodyFlipper)
 };
 
@@ -154,6 +177,7 @@ struct smplfit_convert_plan {
   int nslab = 0;
   int32_t *d_oslot = nullptr, *d_start = nullptr, *d_islot = nullptr;
   float* d_w = nullptr;
+  DeviceArrays dev;  // (of a plan of its own; the arrays of a flip plan's `conv` are the flip plan's)
   bool negate_x = false;  // the matrix was made with SMPLFIT_TRANSFER_NEGATE_X
 };
 
@@ -162,6 +186,7 @@ struct smplfit_convert_plan {
 struct smplfit_flip_plan {
   smplfit_convert_plan conv;
   int32_t* d_perm = nullptr;  // (J)
+  DeviceArrays dev;
 };
 
 // Fused hand replacement plan (smplfit_replace_hands_f32): the constants of HandReplacer on the device.
@@ -172,6 +197,7 @@ struct smplfit_replace_hands_plan {
   float* d_mix = nullptr;     // (V) blend weight of the new mesh
   float* d_rv = nullptr;      // (3 n) replacement rotation vectors
   float* d_mats = nullptr;    // (n, 9) the same as rotation matrices (k_rotvecs_to_mats)
+  DeviceArrays dev;
 };
 
 namespace {
@@ -323,7 +349,7 @@ constexpr int kPgWaves = 8, kPgPairs = SMPLFIT_PG_PAIRS;
 constexpr int pair_gram_units(int J, int npairs) { return 2 * J + (npairs + kPgPairs - 1) / kPgPairs; }
 constexpr int pair_gram_workgroups(int J, int npairs) { return (pair_gram_units(J, npairs) + kPgWaves - 1) / kPgWaves; }
 constexpr int kProWaves = 8;  // joints (= waves) per workgroup of k_prologue_bm
-constexpr int kRefWaves = 8;  // waves per workgroup of k_refine_bm (64 instances; the waves take joints)
+using sf::kRefWaves, sf::kRotSlots, sf::res_share_rec, sf::kResRowRec;  // (sf_tables.h: the table builder uses them too)
 constexpr int prologue_splits(int J) { return (J + kProWaves - 1) / kProWaves; }
 constexpr int kAccExtrasHost = 16;  // (= kAccExtras of kernels_bm.inc: the extras of the scaled solve behind a cell record)
 
@@ -1183,7 +1209,8 @@ void launch_rotations_bm(const smplfit_handle* h, const JointStageArgs& ja, int 
   const DevModel& d = h->d;
   const int Mp = (int)align_up((size_t)B, 128);
   RotArgs ra{ja.tj, ja.rj, ja.jw, ja.Gprev, ja.rj_shared, gprev_mode, B, {}};
-  std::memcpy(ra.slot, h->rot_slots, sizeof(ra.slot));
+  static_assert(sizeof(ra.slot) == sizeof(h->t.rot_slots), "RotArgs::slot holds HostTables::rot_slots");
+  std::memcpy(ra.slot, h->t.rot_slots, sizeof(ra.slot));
   const size_t lds = (size_t)rot_bm_lds_floats(d.J) * 4;
   if (d.J <= kRotJoints * kRefWaves) {
     if (lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(&k_rotations_bm));
@@ -1213,38 +1240,21 @@ void launch_joint_stage_fit(const smplfit_handle* h, JointStageArgs ja, const Wo
 // K6' (k_refine_bm): the refinement + epilogue with lane = instance, reading the part-sum rows of the last LBS pass
 // itself.  Applies where k_prologue_bm ran (pro: ws.GT holds the rotations of the last joint stage, coarse cell tables)
 // on models whose joint arrays of 64 instances fit the LDS (at most 32 joints).
-// (groups of adjustable parts by their top-most adjustable ancestor: a wave of k_refine_bm takes a group — the groups are
-// dealt to the waves in turn — and keeps the part sums of its at most kRefParts parts in registers)
-int refine_bm_groups(const sf::HostTables& t, RefGroups* rg) {  // -> the most parts a wave gets
-  const int nadj = t.adj_level_start[t.adj_last_level + 1];
-  if (nadj > kRefMaxAdj) return 1 << 20;
-  std::vector<int> top(nadj), per_wave(kRefWaves, 0);
-  int ntop = 0, mx = 0;
-  for (int ai = 0; ai < nadj; ++ai) {
-    top[ai] = ai;
-    for (int p = t.adj_parts[ai]; p > 0;) {  // up to the root: the group of the nearest adjustable ancestor is the group of the top-most one
-      p = t.parents[p];
-      for (int a2 = 0; a2 < ai; ++a2)
-        if (t.adj_parts[a2] == p && top[ai] == ai) top[ai] = top[a2];
-    }
-    rg->wave[ai] = (int8_t)(top[ai] == ai ? (ntop++) % kRefWaves : rg->wave[top[ai]]);
-    mx = std::max(mx, ++per_wave[rg->wave[ai]]);
-  }
-  return mx;
-}
 // sv: the table of the LBS pass whose rows hold the part sums (unused without final_adjust)
 void launch_refine_bm(const smplfit_handle* h, RefineArgs ra, const ShareView& sv, const Workspace& ws, int B, hipStream_t st) {
   const DevModel& d = h->d;
   const int Mp = (int)align_up((size_t)B, 128);
   ra.B = B;
   ra.b0 = 0;
+  RefGroups rg;
+  std::memcpy(rg.wave, h->t.refine_waves, sizeof(rg.wave));
   const size_t lds = (size_t)refine_bm_lds_floats(d.J) * 4;
   if (d.S == 11) {
     if (lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(&k_refine_bm<11>));
-    hipLaunchKernelGGL(k_refine_bm<11>, dim3((B + 63) / 64), dim3(64 * kRefWaves), lds, st, d, ra, sv, ws, ws.rjoints, Mp, h->refine_groups);
+    hipLaunchKernelGGL(k_refine_bm<11>, dim3((B + 63) / 64), dim3(64 * kRefWaves), lds, st, d, ra, sv, ws, ws.rjoints, Mp, rg);
   } else {
     if (lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(&k_refine_bm<10>));
-    hipLaunchKernelGGL(k_refine_bm<10>, dim3((B + 63) / 64), dim3(64 * kRefWaves), lds, st, d, ra, sv, ws, ws.rjoints, Mp, h->refine_groups);
+    hipLaunchKernelGGL(k_refine_bm<10>, dim3((B + 63) / 64), dim3(64 * kRefWaves), lds, st, d, ra, sv, ws, ws.rjoints, Mp, rg);
   }
 }
 
@@ -1325,9 +1335,9 @@ Route route_of(const smplfit_handle* h, int B, const CallShape& c) {
   r.jd_transpose = r.bm && !r.prologue_bm;
   // (once k_rotations_bm runs nothing writes the instance-major ws.G any more: a model whose refinement stays on
   // k_refine_epilogue — more than 32 joints — gets it from k_gt_to_g in front of that kernel)
-  r.rot_bm = r.prologue_bm && tn.rot_bm && d.J <= kRotMaxJ && h->rot_nslots <= kRotSlots && h->rot_toes_per_wave <= 2 &&
+  r.rot_bm = r.prologue_bm && tn.rot_bm && d.J <= kRotMaxJ && h->t.rot_nslots <= kRotSlots && h->t.rot_toes_per_wave <= 2 &&
              (size_t)rot_bm_lds_floats(d.J) * 4 <= 160 * 1024;
-  r.refine_bm = r.prologue_bm && tn.refine_bm && d.J <= 32 && h->refine_group_max <= kRefParts &&
+  r.refine_bm = r.prologue_bm && tn.refine_bm && d.J <= 32 && h->t.refine_group_max <= kRefParts &&
                 (size_t)refine_bm_lds_floats(d.J) * 4 <= 160 * 1024;
   r.gt_to_g = r.rot_bm && !r.refine_bm;
   r.psum_combine = !r.rot_bm;
@@ -1894,17 +1904,6 @@ int launch_convert_source(const ConvertSource& src, const Workspace& ws, int B, 
   return 0;
 }
 
-template <typename T>
-int upload(smplfit_handle* h, const std::vector<T>& src, const T** dst) {
-  void* p = nullptr;
-  const size_t bytes = std::max<size_t>(src.size() * sizeof(T), 16);
-  SF_HIP_TRY(hipMalloc(&p, bytes));
-  h->allocs.push_back(p);
-  if (!src.empty()) SF_HIP_TRY(hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  *dst = (const T*)p;
-  return 0;
-}
-
 // Chunk plan of one fit call: a large batch may be split into chunks (SMPLFIT_CHUNKS=1..4) that run concurrently on
 // the caller's stream and the handle's side streams, so that the small latency-bound kernels of one chunk run beside
 // the heavy kernels of the other (the GEMM itself never shares a CU).  Default, measured at B = 4096 in round 4 (the
@@ -2121,16 +2120,12 @@ void launch_transfer_rows(const smplfit_transfer* t, const float* in, int batch,
 }
 
 // The tables of k_transfer_bm in `p` (models p->in / p->out set): the matrix (NULL = identity) re-indexed to the sorted
-// slots of the two models, uploaded to the current device.  Shared by the conversion and the flip plans.
-int upload_slot_transfer(smplfit_convert_plan* p, const smplfit_transfer* transfer, const char* who) {
-  const smplfit_handle *in = p->in, *out = p->out;
-  const int Vo = out->t.V;
-  std::vector<int32_t> inv_in(in->t.V, 0), oslot(Vo, 0), start(Vo + 1, 0), islot;
+// slots of the two models, uploaded to the current device as arrays of `dev`.  Shared by the conversion and the flip plans.
+int upload_slot_transfer(smplfit_convert_plan* p, DeviceArrays& dev, const smplfit_transfer* transfer, const char* who) {
+  const std::vector<int32_t>& inv_in = p->in->t.inv_slot;
+  const int Vo = p->out->t.V;
+  std::vector<int32_t> start(Vo + 1, 0), islot;
   std::vector<float> w;
-  for (int i = 0; i < in->t.Vp; ++i)
-    if (in->t.perm[i] >= 0) inv_in[in->t.perm[i]] = i;
-  for (int i = 0; i < out->t.Vp; ++i)
-    if (out->t.perm[i] >= 0) oslot[out->t.perm[i]] = i;
   for (int r = 0; r < Vo; ++r) {
     if (transfer) {
       for (int e = transfer->indptr[r]; e < transfer->indptr[r + 1]; ++e) {
@@ -2145,19 +2140,10 @@ int upload_slot_transfer(smplfit_convert_plan* p, const smplfit_transfer* transf
   }
   p->nslab = (Vo + kSlabV - 1) / kSlabV;
   p->negate_x = transfer && transfer->negate_x;
-  auto up = [&](const void* src, size_t bytes, void** dst) {
-    if (hipMalloc(dst, std::max<size_t>(bytes, 16)) != hipSuccess) return false;
-    return bytes == 0 || hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
-  if (!up(oslot.data(), oslot.size() * 4, (void**)&p->d_oslot) || !up(start.data(), start.size() * 4, (void**)&p->d_start) ||
-      !up(islot.data(), islot.size() * 4, (void**)&p->d_islot) || !up(w.data(), w.size() * 4, (void**)&p->d_w))
+  if (dev.upload(p->out->t.inv_slot, &p->d_oslot) || dev.upload(start, &p->d_start) || dev.upload(islot, &p->d_islot) ||
+      dev.upload(w, &p->d_w))
     return fail(SMPLFIT_ERR_HIP, std::string(who) + ": device upload failed");
   return 0;
-}
-
-void free_slot_transfer(smplfit_convert_plan* p) {
-  for (void* q : {(void*)p->d_oslot, (void*)p->d_start, (void*)p->d_islot, (void*)p->d_w})
-    if (q) (void)hipFree(q);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2393,44 +2379,21 @@ int smplfit_create(const smplfit_model_desc* desc, int flags, smplfit_handle** o
   d.V = t.V; d.J = t.J; d.S = t.S; d.P = t.P; d.Vp = t.Vp; d.Kp = t.Kp; d.KW = t.KW;
   d.n_used = t.n_used;
   d.nseg = (int)t.segments.size();
-  std::vector<int32_t> seg;
-  for (auto& s : t.segments) {
-    seg.push_back(s.start);
-    seg.push_back(s.count);
-    seg.push_back(s.part);
-  }
-  std::vector<float> jtemplate((size_t)t.J * 3);
-  for (int k = 0; k < t.J * 3; ++k) jtemplate[k] = t.j_ext[(size_t)k * (t.S + 1)];
-  int rc = 0;
-  auto up = [&](auto& vec, auto** dst) {
-    if (rc == 0) rc = upload(h, vec, dst);
-  };
+  d.nsegall = (int)t.segments_all.size();
+  d.ngt = (int)t.gtiles.size();
+  d.kc32 = t.kc32;
   d.general = t.general ? 1 : 0;
-  {
-    std::vector<int32_t> sa;
-    for (auto& sg : t.segments_all) {
-      sa.push_back(sg.start);
-      sa.push_back(sg.count);
-      sa.push_back(sg.part);
-    }
-    d.nsegall = (int)t.segments_all.size();
-    up(sa, &d.segall);
-  }
+  d.bm_tables = t.shares.empty() ? 0 : 1;
+  // every table the kernels read, as sf_tables.cpp made it: the first failed upload is the call's error
+  int rc = 0;
+  auto up = [&](const auto& vec, auto* dst) {
+    if (rc == 0) rc = h->dev.upload(vec, dst);
+  };
+  up(sf::flatten(t.segments_all), &d.segall);
   up(t.sdg, &d.sdg);
   up(t.perm, &d.perm);
-  up(seg, &d.segments);
-  std::vector<int32_t> pss(t.J + 1, 0);
-  {
-    size_t k = 0;
-    for (int p = 0; p < t.J; ++p) {
-      // segments are ordered by part id over the used parts
-      while (k < t.segments.size() && t.segments[k].part < p) ++k;
-      pss[p] = (int32_t)k;
-      while (k < t.segments.size() && t.segments[k].part == p) ++k;
-      pss[p + 1] = (int32_t)k;
-    }
-  }
-  up(pss, &d.part_seg_start);
+  up(sf::flatten(t.segments), &d.segments);
+  up(t.part_seg_start, &d.part_seg_start);
   up(t.vt, &d.vt);
   up(t.dm, &d.dm);
   up(t.sd, &d.sd);
@@ -2439,7 +2402,50 @@ int smplfit_create(const smplfit_model_desc* desc, int flags, smplfit_handle** o
   up(t.pdSw, &d.pdSw);
   up(t.pdB, &d.pdB);
   up(t.pdB2, &d.pdB2);
-  d.kc32 = t.kc32;
+  std::vector<uint16_t>().swap(h->t.pdB2);  // the host copy of the stage images is not needed any more
+  up(t.cpackA, &d.cpackA);
+  up(t.cpackB, &d.cpackB);
+  up(t.gblob, &d.gblob);
+  up(sf::flatten(t.gtiles), &d.gtiles);
+  up(t.j_template, &d.j_template);
+  up(t.reg_start, &d.reg_start);
+  up(t.reg_slot, &d.reg_slot);
+  up(t.reg_val, &d.reg_val);
+  up(t.reg_rowsum, &d.reg_rowsum);
+  up(t.inv_slot, &d.inv_slot);
+  h->views.assign(t.shares.size(), ShareView{});  // the share tables of the batch-major vertex kernels: (coarse, fine) x kinds
+  for (size_t i = 0; i < t.shares.size(); ++i) {
+    const sf::ShareTable& stb = t.shares[i];
+    ShareView& sv = h->views[i];
+    sv.ncells = stb.ncells;
+    sv.nrows = stb.nrows;
+    sv.rec = stb.rec;
+    sv.mult = 1;
+    sv.max_aux = stb.max_aux;
+    sv.aux_pitch = stb.aux_pitch;
+    up(stb.piece_start, &sv.piece_start);
+    up(stb.pieces, &sv.pieces);
+    up(stb.aux_start, &sv.aux_start);
+    up(stb.aux_rows, &sv.aux_rows);
+    if (!stb.aux_pad.empty()) up(stb.aux_pad, &sv.aux_pad);  // (residual tables only)
+  }
+  up(t.brec, &d.brec);
+  up(t.pair_E, &d.pair_E);
+  up(t.jn_start, &d.jn_start);
+  up(t.jn, &d.jn);
+  up(t.anc_start, &d.anc_start);
+  up(t.anc, &d.anc);
+  up(t.pair_c2e, &d.pair_c2e);
+  up(t.diag_c2e, &d.diag_c2e);
+  d.jt = sf::bind_joint_tabs(t, [&](const auto& vec) {
+    decltype(vec.data()) p = nullptr;
+    up(vec, &p);
+    return p;
+  });
+  if (rc != 0) {
+    smplfit_destroy(h);
+    return rc;
+  }
   {
     int regs = 1 << 20;
     for (const void* fn : {reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<true>),
@@ -2462,125 +2468,6 @@ int smplfit_create(const smplfit_model_desc* desc, int flags, smplfit_handle** o
       });
     }
   }
-  std::vector<uint16_t>().swap(h->t.pdB2);  // the host copy of the stage images is not needed any more
-  up(t.cpackA, &d.cpackA);
-  up(t.cpackB, &d.cpackB);
-  up(t.gblob, &d.gblob);
-  std::vector<int32_t> gt;
-  for (auto& g : t.gtiles) {
-    gt.push_back(g.start);
-    gt.push_back(g.count);
-    gt.push_back(g.part);
-  }
-  up(gt, &d.gtiles);
-  d.ngt = (int)t.gtiles.size();
-  up(jtemplate, &d.j_template);
-  up(t.reg_start, &d.reg_start);
-  up(t.reg_slot, &d.reg_slot);
-  up(t.reg_val, &d.reg_val);
-  up(t.reg_rowsum, &d.reg_rowsum);
-  {
-    {
-      std::vector<int32_t> inv(t.V, 0);
-      for (int i = 0; i < t.Vp; ++i)
-        if (t.perm[i] >= 0) inv[t.perm[i]] = i;
-      up(inv, &d.inv_slot);
-    }
-    // the share tables of the batch-major vertex kernels
-    d.bm_tables = t.shares.empty() ? 0 : 1;
-    h->views.assign(t.shares.size(), ShareView{});  // (coarse, fine) x kinds
-    for (size_t i = 0; i < t.shares.size(); ++i) {
-      const sf::ShareTable& stb = t.shares[i];
-      ShareView& sv = h->views[i];
-      sv.ncells = stb.ncells;
-      sv.nrows = stb.nrows;
-      sv.rec = stb.rec;
-      sv.mult = 1;
-      up(stb.piece_start, &sv.piece_start);
-      up(stb.pieces, &sv.pieces);
-      std::vector<int32_t> astart(t.J + 1, 0), arows;
-      if ((int)(i % sf::kShareKinds) == sf::kShareResidual) {  // per joint: the resP rows holding its moments
-        for (int j = 0; j < t.J; ++j) {
-          for (int r = 0; r < stb.nrows; ++r)
-            for (int q = 0; q < sf::kGroupJoints; ++q)
-              if (stb.row_joints[(size_t)r * sf::kGroupJoints + q] == j)
-                arows.push_back((int32_t)(stb.ncells * res_share_rec(t.S) + r * kResRowRec + 3 * q));
-          astart[j + 1] = (int32_t)arows.size();
-        }
-      } else {  // per part: its rows of ws.psumP
-        for (int j = 0; j < t.J; ++j) {
-          for (int r = 0; r < stb.nrows; ++r)
-            if (stb.row_part[r] == j) arows.push_back(r);
-          astart[j + 1] = (int32_t)arows.size();
-        }
-      }
-      sv.max_aux = 0;
-      for (int j = 0; j < t.J; ++j) sv.max_aux = std::max(sv.max_aux, astart[j + 1] - astart[j]);
-      up(astart, &sv.aux_start);
-      up(arows, &sv.aux_rows);
-      sv.aux_pitch = std::max(16, (sv.max_aux + 15) / 16 * 16);
-      sv.aux_pad = nullptr;
-      if ((int)(i % sf::kShareKinds) == sf::kShareResidual) {
-        std::vector<int32_t> pad((size_t)t.J * sv.aux_pitch, -1);
-        for (int j = 0; j < t.J; ++j)
-          for (int k = astart[j]; k < astart[j + 1]; ++k) pad[(size_t)j * sv.aux_pitch + (k - astart[j])] = arows[k];
-        up(pad, &sv.aux_pad);
-      }
-    }
-    up(t.brec, &d.brec);
-    up(t.pair_E, &d.pair_E);
-    up(t.jn_start, &d.jn_start);
-    up(t.jn, &d.jn);
-    {  // ancestors of every joint, root first (k_prologue_bm walks them: the level-by-level FK as a sum along the chain)
-      std::vector<int32_t> as(t.J + 1, 0), an;
-      for (int j = 0; j < t.J; ++j) {
-        std::vector<int32_t> ch;
-        for (int a2 = j; a2 > 0;) {
-          a2 = t.parents[a2];
-          ch.push_back(a2);
-        }
-        an.insert(an.end(), ch.rbegin(), ch.rend());
-        as[j + 1] = (int32_t)an.size();
-      }
-      if (an.empty()) an.push_back(0);
-      up(as, &d.anc_start);
-      up(an, &d.anc);
-    }
-    up(t.pair_c2e, &d.pair_c2e);
-    up(t.diag_c2e, &d.diag_c2e);
-  }
-  sf::JointTabs& jt = d.jt;
-  jt.J = t.J; jt.S = t.S; jt.num_levels = t.num_levels(); jt.adj_last_level = t.adj_last_level;
-  jt.P = t.P; jt.Kp = t.Kp;
-  jt.n_kid = t.n_kid;
-  jt.n_pad = t.n_pad;
-  up(t.parents, &jt.parents);
-  up(t.fk_js, &jt.fk_js);
-  up(t.fk_level_start, &jt.fk_level_start);
-  up(t.cas_start, &jt.cas_start);
-  up(t.cas_flat, &jt.cas_flat);
-  up(t.part_type, &jt.part_type);
-  up(t.toe_src, &jt.toe_src);
-  up(t.adj_level_start, &jt.adj_level_start);
-  up(t.adj_parts, &jt.adj_parts);
-  up(t.j_ext, &jt.j_ext);
-  up(t.bone_ext, &jt.bone_ext);
-  up(t.fk_jp, &jt.fk_jp);
-  up(t.bone_lv, &jt.bone_lv);
-  up(t.cs_joint, &jt.cs_joint);
-  up(t.cw_joint, &jt.cw_joint);
-  jt.np = (int)t.pair_c3.size();
-  up(t.pair_j, &jt.pair_j);
-  up(t.pair_c1, &jt.pair_c1);
-  up(t.pair_c2, &jt.pair_c2);
-  up(t.pair_c3, &jt.pair_c3);
-  up(t.diag_g0, &jt.diag_g0);
-  up(t.diag_c2, &jt.diag_c2);
-  up(t.diag_c3, &jt.diag_c3);
-  if (rc != 0) {
-    smplfit_destroy(h);
-    return rc;
-  }
   // side streams + events of the chunked fit
   for (int i = 0; i < kMaxChunks - 1; ++i) {
     if (hipStreamCreateWithFlags(&h->side[i], hipStreamNonBlocking) != hipSuccess ||
@@ -2595,17 +2482,6 @@ int smplfit_create(const smplfit_model_desc* desc, int flags, smplfit_handle** o
   }
   h->have_streams = true;
   h->has_device = true;
-  h->refine_group_max = refine_bm_groups(h->t, &h->refine_groups);
-  {
-    std::fill(h->rot_slots, h->rot_slots + 64, (int8_t)-1);
-    for (int j = 0; j < (int)h->t.toe_src.size() && j < 64; ++j) {
-      const int src = h->t.toe_src[j];
-      if (src >= 0 && src < 64 && h->rot_slots[src] < 0) h->rot_slots[src] = (int8_t)h->rot_nslots++;
-    }
-    int per_wave[kRefWaves] = {};  // toes of one wave of k_rotations_bm (joint j belongs to wave j % kRefWaves)
-    for (int j = 0; j < (int)h->t.toe_src.size(); ++j)
-      if (h->t.toe_src[j] >= 0) h->rot_toes_per_wave = std::max(h->rot_toes_per_wave, ++per_wave[j % kRefWaves]);
-  }
   *out = h;
   return SMPLFIT_OK;
 }
@@ -2620,7 +2496,7 @@ void smplfit_destroy(smplfit_handle* h) {
     if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]);
   }
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  for (void* p : h->allocs) (void)hipFree(p);
+  h->dev.free_all();
   delete h;
 }
 
@@ -2659,11 +2535,7 @@ int smplfit_get_table(const smplfit_handle* h, int table_id, int32_t* dst, size_
     case SMPLFIT_TAB_ADJ_FLAG: src = &t.adj_flag; break;
     case SMPLFIT_TAB_USED_PART: src = &t.used_part; break;
     case SMPLFIT_TAB_SEGMENTS:
-      for (auto& s : t.segments) {
-        tmp.push_back(s.start);
-        tmp.push_back(s.count);
-        tmp.push_back(s.part);
-      }
+      tmp = sf::flatten(t.segments);
       src = &tmp;
       break;
     case SMPLFIT_TAB_VERTEX_PIECES:
@@ -2681,23 +2553,37 @@ int smplfit_get_table(const smplfit_handle* h, int table_id, int32_t* dst, size_
       for (auto& st : t.shares) tmp.push_back(st.ncells);
       src = &tmp;
       break;
+    case SMPLFIT_TAB_INV_SLOT: src = &t.inv_slot; break;
+    case SMPLFIT_TAB_PART_SEG_START: src = &t.part_seg_start; break;
+    case SMPLFIT_TAB_ANC_START: src = &t.anc_start; break;
+    case SMPLFIT_TAB_ANC: src = &t.anc; break;
+    case SMPLFIT_TAB_ROT_SLOTS:
+      tmp.assign(t.rot_slots, t.rot_slots + t.J);
+      src = &tmp;
+      break;
+    case SMPLFIT_TAB_REFINE_WAVES:
+      if (t.adj_parts.size() <= (size_t)sf::kRefMaxAdj) tmp.assign(t.refine_waves, t.refine_waves + t.adj_parts.size());
+      src = &tmp;
+      break;
     default: return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_get_table: unknown table id");
   }
   *n = src->size();
-  if (dst) std::memcpy(dst, src->data(), std::min(cap, src->size()) * sizeof(int32_t));
+  if (dst && !src->empty()) std::memcpy(dst, src->data(), std::min(cap, src->size()) * sizeof(int32_t));
   return SMPLFIT_OK;
 }
 
 int smplfit_get_share_table(const smplfit_handle* h, int kind, int what, int32_t* dst, size_t cap, size_t* n) {
   if (!h || !n) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_get_share_table: null argument");
   const sf::HostTables& t = h->t;
-  if (kind < 0 || kind >= (int)t.shares.size() || what < 0 || what > 2)
+  if (kind < 0 || kind >= (int)t.shares.size() || what < 0 || what > 5)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_get_share_table: unknown kind / table (or a model without batch-major tables)");
   const sf::ShareTable& st = t.shares[kind];
-  const std::vector<int32_t>* src =
-      what == 0 ? &st.piece_start : what == 1 ? &st.pieces : (kind % sf::kShareKinds == sf::kShareResidual ? &st.row_joints : &st.row_part);
+  const std::vector<int32_t>* const tabs[] = {&st.piece_start, &st.pieces,
+                                              kind % sf::kShareKinds == sf::kShareResidual ? &st.row_joints : &st.row_part,
+                                              &st.aux_start, &st.aux_rows, &st.aux_pad};
+  const std::vector<int32_t>* src = tabs[what];
   *n = src->size();
-  if (dst) std::memcpy(dst, src->data(), std::min(cap, src->size()) * sizeof(int32_t));
+  if (dst && !src->empty()) std::memcpy(dst, src->data(), std::min(cap, src->size()) * sizeof(int32_t));
   return SMPLFIT_OK;
 }
 
@@ -3096,17 +2982,10 @@ int smplfit_transfer_create(int32_t num_vertices_in, int32_t num_vertices_out, c
   t->indices.assign(indices, indices + nnz);
   t->values.assign(values, values + nnz);
   t->negate_x = (flags & SMPLFIT_TRANSFER_NEGATE_X) != 0;
-  if (!(flags & SMPLFIT_CREATE_HOST_ONLY)) {
-    auto up = [&](const void* src, size_t bytes, void** dst) {
-      if (hipMalloc(dst, std::max<size_t>(bytes, 16)) != hipSuccess) return false;
-      return bytes == 0 || hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-    };
-    if (!up(t->indptr.data(), t->indptr.size() * 4, (void**)&t->d_indptr) ||
-        !up(t->indices.data(), t->indices.size() * 4, (void**)&t->d_indices) ||
-        !up(t->values.data(), t->values.size() * 4, (void**)&t->d_values)) {
-      smplfit_transfer_destroy(t);
-      return fail(SMPLFIT_ERR_HIP, "smplfit_transfer_create: device upload failed");
-    }
+  if (!(flags & SMPLFIT_CREATE_HOST_ONLY) &&
+      (t->dev.upload(t->indptr, &t->d_indptr) || t->dev.upload(t->indices, &t->d_indices) || t->dev.upload(t->values, &t->d_values))) {
+    smplfit_transfer_destroy(t);
+    return fail(SMPLFIT_ERR_HIP, "smplfit_transfer_create: device upload failed");
   }
   *out = t;
   return SMPLFIT_OK;
@@ -3114,9 +2993,7 @@ int smplfit_transfer_create(int32_t num_vertices_in, int32_t num_vertices_out, c
 
 void smplfit_transfer_destroy(smplfit_transfer* t) {
   if (!t) return;
-  if (t->d_indptr) (void)hipFree(t->d_indptr);
-  if (t->d_indices) (void)hipFree(t->d_indices);
-  if (t->d_values) (void)hipFree(t->d_values);
+  t->dev.free_all();
   delete t;
 }
 
@@ -3150,7 +3027,7 @@ int smplfit_convert_plan_create(const smplfit_handle* in, const smplfit_handle* 
   auto* p = new smplfit_convert_plan();
   p->in = in;
   p->out = out;
-  if (int rc = upload_slot_transfer(p, transfer, "smplfit_convert_plan_create")) {
+  if (int rc = upload_slot_transfer(p, p->dev, transfer, "smplfit_convert_plan_create")) {
     smplfit_convert_plan_destroy(p);
     return rc;
   }
@@ -3160,7 +3037,7 @@ int smplfit_convert_plan_create(const smplfit_handle* in, const smplfit_handle* 
 
 void smplfit_convert_plan_destroy(smplfit_convert_plan* p) {
   if (!p) return;
-  free_slot_transfer(p);
+  p->dev.free_all();
   delete p;
 }
 
@@ -3210,10 +3087,8 @@ int smplfit_flip_plan_create(const smplfit_handle* h, const smplfit_transfer* mi
   auto* p = new smplfit_flip_plan();
   p->conv.in = h;
   p->conv.out = h;
-  int rc = upload_slot_transfer(&p->conv, mirror, "smplfit_flip_plan_create");
-  if (!rc && (hipMalloc((void**)&p->d_perm, (size_t)J * 4) != hipSuccess ||
-              hipMemcpy(p->d_perm, joint_perm, (size_t)J * 4, hipMemcpyHostToDevice) != hipSuccess))
-    rc = fail(SMPLFIT_ERR_HIP, "smplfit_flip_plan_create: device upload failed");
+  int rc = upload_slot_transfer(&p->conv, p->dev, mirror, "smplfit_flip_plan_create");
+  if (!rc && p->dev.upload(joint_perm, (size_t)J, &p->d_perm)) rc = fail(SMPLFIT_ERR_HIP, "smplfit_flip_plan_create: device upload failed");
   if (rc) {
     smplfit_flip_plan_destroy(p);
     return rc;
@@ -3224,8 +3099,7 @@ int smplfit_flip_plan_create(const smplfit_handle* h, const smplfit_transfer* mi
 
 void smplfit_flip_plan_destroy(smplfit_flip_plan* p) {
   if (!p) return;
-  free_slot_transfer(&p->conv);
-  if (p->d_perm) (void)hipFree(p->d_perm);
+  p->dev.free_all();
   delete p;
 }
 
@@ -3292,12 +3166,9 @@ int smplfit_replace_hands_plan_create(const smplfit_handle* h, const float* fit_
   p->h = h;
   p->j0 = first_joint;
   p->n = num_joints;
-  auto up = [&](const float* src, size_t count, float** dst) {
-    if (hipMalloc((void**)dst, std::max<size_t>(count * 4, 16)) != hipSuccess) return false;
-    return !src || hipMemcpy(*dst, src, count * 4, hipMemcpyHostToDevice) == hipSuccess;
-  };
-  bool ok = up(fit_weights, (size_t)num_vertices, &p->d_fitw) && up(mix_weights, (size_t)num_vertices, &p->d_mix) &&
-            up(rotvecs, (size_t)3 * num_joints, &p->d_rv) && up(nullptr, (size_t)9 * num_joints, &p->d_mats);
+  DeviceArrays& dev = p->dev;
+  bool ok = !dev.upload(fit_weights, (size_t)num_vertices, &p->d_fitw) && !dev.upload(mix_weights, (size_t)num_vertices, &p->d_mix) &&
+            !dev.upload(rotvecs, (size_t)3 * num_joints, &p->d_rv) && !dev.alloc((size_t)9 * num_joints * sizeof(float), &p->d_mats);
   if (ok) {
     hipLaunchKernelGGL(k_rotvecs_to_mats, dim3((num_joints + 63) / 64), dim3(64), 0, (hipStream_t) nullptr, p->d_rv, p->d_mats, num_joints);
     ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess;
@@ -3312,8 +3183,7 @@ int smplfit_replace_hands_plan_create(const smplfit_handle* h, const float* fit_
 
 void smplfit_replace_hands_plan_destroy(smplfit_replace_hands_plan* p) {
   if (!p) return;
-  for (float* q : {p->d_fitw, p->d_mix, p->d_rv, p->d_mats})
-    if (q) (void)hipFree(q);
+  p->dev.free_all();
   delete p;
 }
 

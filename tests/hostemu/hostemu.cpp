@@ -24,25 +24,6 @@ struct HostCtx {
   float sum_to_last(float v) const { return v; }  // (one lane: the partial sum is the sum)
 };
 
-sf::JointTabs make_tabs(const sf::HostTables& t) {
-  sf::JointTabs jt;
-  jt.J = t.J; jt.S = t.S; jt.num_levels = t.num_levels(); jt.adj_last_level = t.adj_last_level;
-  jt.P = t.P; jt.Kp = t.Kp;
-  jt.n_kid = t.n_kid;
-  jt.n_pad = t.n_pad;
-  jt.parents = t.parents.data(); jt.fk_js = t.fk_js.data();
-  jt.fk_level_start = t.fk_level_start.data(); jt.cas_start = t.cas_start.data();
-  jt.cas_flat = t.cas_flat.data(); jt.part_type = t.part_type.data(); jt.toe_src = t.toe_src.data();
-  jt.adj_level_start = t.adj_level_start.data(); jt.adj_parts = t.adj_parts.data();
-  jt.j_ext = t.j_ext.data(); jt.bone_ext = t.bone_ext.data();
-  jt.fk_jp = t.fk_jp.data(); jt.bone_lv = t.bone_lv.data();
-  jt.cs_joint = t.cs_joint.data(); jt.cw_joint = t.cw_joint.data();
-  jt.np = (int)t.pair_c3.size(); jt.pair_j = t.pair_j.data(); jt.pair_c1 = t.pair_c1.data();
-  jt.pair_c2 = t.pair_c2.data(); jt.pair_c3 = t.pair_c3.data(); jt.diag_g0 = t.diag_g0.data();
-  jt.diag_c2 = t.diag_c2.data(); jt.diag_c3 = t.diag_c3.data();
-  return jt;
-}
-
 template <int S, int KW>
 struct Emu {
   const sf::HostTables& t;
@@ -54,7 +35,7 @@ struct Emu {
   sf::JointScratch sh;
   std::vector<float> solve_scratch;
 
-  Emu(const sf::HostTables& tt, int b) : t(tt), jt(make_tabs(tt)), B(b) {
+  Emu(const sf::HostTables& tt, int b) : t(tt), jt(sf::bind_joint_tabs(tt, [](const auto& v) { return v.data(); })), B(b) {
     const int J = t.J, Vp = t.Vp, NE1 = sf::ne_size(S) + 1;
     tvs.assign((size_t)B * 3 * Vp, 0.f); vws.assign((size_t)B * Vp, 0.f);
     vposed.assign((size_t)B * 3 * Vp, 0.f); rp.assign((size_t)B * t.Kp, 0.f);

@@ -57,6 +57,9 @@ def test_no_device_fails_loudly(lib, model_root):
     desc, keep = H.desc_from_md(md, kind)
     with pytest.raises(_lib.SmplfitError):
         _lib.Handle(desc)  # uploading without a device must raise, never fall back
+    with pytest.raises(_lib.SmplfitError):  # and so must a transfer matrix
+        _lib.Transfer(5, 3, np.array([0, 2, 2, 3], np.int32), np.array([0, 4, 1], np.int32),
+                      np.array([0.5, 0.5, 1.0], np.float32))
     from smplfitter_amd.pt import BodyModel
 
     m = BodyModel('smpl', 'neutral', model_root=f'{model_root}/smpl', num_betas=10)
@@ -113,6 +116,7 @@ def test_host_tables_match_reference_structure(lib, name, model_root, golden):
         assert len(joints) == nq
     assert (np.diff(pcs[:, 3]) <= 0).all()  # used pieces first
     check_share_tables(h, of, md, perm, V, plain=name != 'smpl_rnd', nj=nj)
+    check_derived_tables(h, md, perm, name)
     if V >= 1024:
         assert h.info.padded_vertices > V
     assert h.workspace_bytes(64) > 0
@@ -136,6 +140,7 @@ def test_general_models_create(lib, kind, model_root):
     assert len(h.table('vertex_pieces')) == 0 and len(h.table('cell_counts')) == 0 and len(h.table('joint_pairs')) == 0
     perm = h.table('sort_perm')
     assert sorted(perm[perm >= 0].tolist()) == list(range(md.num_vertices))
+    check_derived_tables(h, md, perm, kind)  # (no cell tables: the per-table part checks nothing here)
     assert h.workspace_bytes(8) > 0
     h.close()
     desc, keep = H.desc_from_md(md, 'smpl', enable_kid=True)
@@ -206,6 +211,82 @@ def check_share_tables(h, of, md, perm, V, plain=True, nj=4):
     if V > 6000 and plain:  # (the random-joint variant has a piece per vertex: 256 cells)
         m4k, m32k = lib.smplfit_pick_share_mult(h.ptr, 0, 4096), lib.smplfit_pick_share_mult(h.ptr, 0, 32768)
         assert (4096 // 64) * ncells[0] // m4k == 4096 and (32768 // 64) * ncells[0] // m32k == 4096
+
+
+def check_derived_tables(h, md, perm, name):
+    """The tables the table builder derives for single kernels (on a host-only handle: nothing is uploaded), each
+    against a definition of its own in numpy."""
+    V, J = md.num_vertices, md.num_joints
+    parents = [int(p) for p in md.kintree_parents]
+    # sorted slot of every original vertex
+    inv = h.table('inv_slot')
+    live = np.nonzero(perm >= 0)[0]
+    assert len(inv) == V and (inv[perm[live]] == live).all()
+    # first segment of every part
+    seg = h.table('segments').reshape(-1, 3)
+    pss = h.table('part_seg_start')
+    assert len(pss) == J + 1 and (np.diff(pss) >= 0).all()
+    used = h.table('used_part')
+    for p in range(J):
+        assert list(range(pss[p], pss[p + 1])) == np.nonzero(seg[:, 2] == p)[0].tolist()
+        assert used[p] or pss[p] == pss[p + 1]
+    # ancestors, root first (k_prologue_bm)
+    ast, anc = h.table('anc_start'), h.table('anc')
+    assert len(ast) == J + 1 and ast[0] == 0 and ast[-1] == len(anc)
+    for j in range(J):
+        chain, a = [], j
+        while a > 0:
+            a = parents[a]
+            chain.append(a)
+        assert anc[ast[j]:ast[j + 1]].tolist() == chain[::-1]
+    assert ast[1] == 0  # the root has none
+    # where the combine kernels find a joint's partial sums
+    ncells = h.table('cell_counts')
+    S = (10 if h.info.num_betas <= 10 else 16) + h.info.has_kid  # the unknowns the kernels are built for
+    for table in range(len(ncells)):
+        rows = h.share_table(table, 2)
+        ast, arows, apad = (h.share_table(table, what) for what in (3, 4, 5))
+        assert len(ast) == J + 1 and ast[0] == 0 and ast[-1] == len(arows)
+        runs = [arows[ast[j]:ast[j + 1]].tolist() for j in range(J)]
+        if table % 4 == 0:  # residual kind: the moments of (row r, local slot q) in ws.resP, as k_residual_bm writes them
+            rj = rows.reshape(-1, 12)
+            base = int(ncells[table]) * ((S + 6) // 4 * 4)
+            for j in range(J):
+                assert runs[j] == [base + r * 36 + 3 * q for r, q in zip(*np.nonzero(rj == j))]  # (row-major order)
+            pitch = max(16, -(-max(len(r) for r in runs) // 16) * 16)
+            assert len(apad) == J * pitch
+            for j in range(J):
+                assert apad.reshape(J, pitch)[j].tolist() == runs[j] + [-1] * (pitch - len(runs[j]))
+        else:  # LBS kinds: the rows of the part, ascending
+            for j in range(J):
+                assert runs[j] == np.nonzero(rows == j)[0].tolist()
+            assert len(apad) == 0
+    # k_rotations_bm: the toes (no rotation of their own; SMPL family: 10 <- 7, 11 <- 8) and the slots of their sources
+    toe_src = {10: 7, 11: 8}
+    assert np.nonzero(h.table('part_type') == 0)[0].tolist() == sorted(toe_src)
+    want = np.full(J, -1)
+    for toe in sorted(toe_src):
+        if want[toe_src[toe]] < 0:
+            want[toe_src[toe]] = want.max() + 1
+    assert (h.table('rot_slots') == want).all()
+    if name in ('smpl', 'smplx'):  # conditions of k_rotations_bm's route (route_of): the sources fit its LDS slots, and a
+        assert want.max() + 1 <= 8  # wave (joints j % 8) composes at most two toes
+        assert max(np.bincount([toe % 8 for toe in toe_src])) <= 2
+    # k_refine_bm: parts under one top-most adjustable ancestor share a wave, the groups take the waves in turn
+    adj_flag = h.table('adj_flag')
+    adj_parts = [int(j) for j in h.table('fk_order') if adj_flag[j]]
+    waves = h.table('refine_waves')
+    assert len(waves) == len(adj_parts)
+    group_wave = {}
+    for j, w in zip(adj_parts, waves):
+        top, a = j, j
+        while a > 0:
+            a = parents[a]
+            if adj_flag[a]:
+                top = a
+        assert w == group_wave.setdefault(top, len(group_wave) % 8)
+    if name == 'smpl':  # condition of k_refine_bm's route: a wave keeps the part sums of at most four parts
+        assert max(np.bincount(waves)) <= 4
 
 
 def test_create_rejects_bad_models(lib, model_root):
