@@ -359,6 +359,44 @@ typedef struct smplfit_shape_solve_backward_args {
 } smplfit_shape_solve_backward_args;
 int smplfit_shape_solve_backward_f32(const smplfit_handle* h, const smplfit_shape_solve_backward_args* args);
 
+/* Adjoint of smplfit_fit_ex_f32 (the backward of BodyFitter.fit under autograd): the gradients of
+ * the targets and weights of a fit from the cotangents of its results.  Inputs as smplfit_fit_args passes them (no warm
+ * start, no share_beta, no scale unknown).  Cotangents, each may be NULL (= zero): grad_pose_rotvecs (B,3J),
+ * grad_shape_betas (B, the model's betas), grad_trans (B,3), grad_kid_factor (B, kid handles), grad_orientations,
+ * grad_relative_orientations (B,J,3,3).  Outputs, each may be NULL (= not wanted, no output): the gradients of
+ * target_vertices (B,V,3), target_joints (B,J,3), vertex_weights (B,V), joint_weights (B,J).  Nothing is kept from the
+ * forward call: a forward sweep recomputes the rotations and the solution of every iteration, a reverse sweep
+ * alternates the adjoints of the rotation pass and of the refinement with smplfit_forward_backward_f32 and
+ * smplfit_shape_solve_backward_f32.  Any number of skinning weights and joints, up to 17 shape unknowns (more:
+ * SMPLFIT_ERR_UNSUPPORTED).  An instance whose projection or solve is singular gets non-finite gradients, the others
+ * are not touched.  Stream-ordered, no allocation, no synchronisation; deterministic: no float atomics.
+ * Workspace: smplfit_fit_backward_workspace_bytes(h, batch, num_iter). */
+size_t smplfit_fit_backward_workspace_bytes(const smplfit_handle* h, int batch, int num_iter);
+typedef struct smplfit_fit_backward_args {
+  const float* target_vertices;             /* (B,V,3) */
+  const float* target_joints;               /* (B,J,3) or NULL */
+  const float* vertex_weights;              /* (B,V) or NULL */
+  const float* joint_weights;               /* (B,J) or NULL */
+  int32_t batch;
+  int32_t num_iter;
+  float beta_regularizer, beta_regularizer2, kid_regularizer;
+  int32_t final_adjust_rots;
+  const float* grad_pose_rotvecs;           /* (B,3J) or NULL */
+  const float* grad_shape_betas;            /* (B, the model's betas) or NULL */
+  const float* grad_trans;                  /* (B,3) or NULL */
+  const float* grad_kid_factor;             /* (B) or NULL */
+  const float* grad_orientations;           /* (B,J,3,3) or NULL */
+  const float* grad_relative_orientations;  /* (B,J,3,3) or NULL */
+  float* grad_target_vertices;              /* out (B,V,3) or NULL */
+  float* grad_target_joints;                /* out (B,J,3) or NULL */
+  float* grad_vertex_weights;               /* out (B,V) or NULL */
+  float* grad_joint_weights;                /* out (B,J) or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  void* hip_stream;
+} smplfit_fit_backward_args;
+int smplfit_fit_backward_f32(const smplfit_handle* h, const smplfit_fit_backward_args* args);
+
 /* BodyFitter.fit with a warm start (pt/bodyfitter.py:363-382): smplfit_fit_f32 plus
  *   initial_pose_rotvecs (B,3J) or NULL, initial_shape_betas (B,num_initial_betas) or NULL,
  *   initial_kid_factor (B) or NULL (enable_kid handles only).

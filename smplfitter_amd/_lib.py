@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = [
     'smplfit_replace_hands_plan_create', 'smplfit_replace_hands_plan_destroy',
     'smplfit_replace_hands_workspace_bytes', 'smplfit_replace_hands_f32',
     'smplfit_shape_solve_backward_workspace_bytes', 'smplfit_shape_solve_backward_f32',
+    'smplfit_fit_backward_workspace_bytes', 'smplfit_fit_backward_f32',
 ]  # fmt: skip
 
 _fp = C.POINTER(C.c_float)
@@ -130,6 +131,20 @@ class ShapeSolveBackwardArgs(C.Structure):
         ('grad_target_vertices', C.c_void_p), ('grad_target_joints', C.c_void_p), ('grad_vertex_weights', C.c_void_p),
         ('grad_joint_weights', C.c_void_p), ('grad_beta_regularizer_reference', C.c_void_p),
         ('grad_kid_regularizer_reference', C.c_void_p), ('grad_glob_rotmats', C.c_void_p),
+        ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('hip_stream', C.c_void_p),
+    ]
+
+
+class FitBackwardArgs(C.Structure):
+    """smplfit_fit_backward_args (include/smplfit.h)."""
+    _fields_ = [
+        ('target_vertices', C.c_void_p), ('target_joints', C.c_void_p), ('vertex_weights', C.c_void_p),
+        ('joint_weights', C.c_void_p), ('batch', C.c_int32), ('num_iter', C.c_int32),
+        ('beta_regularizer', C.c_float), ('beta_regularizer2', C.c_float), ('kid_regularizer', C.c_float),
+        ('final_adjust_rots', C.c_int32), ('grad_pose_rotvecs', C.c_void_p), ('grad_shape_betas', C.c_void_p),
+        ('grad_trans', C.c_void_p), ('grad_kid_factor', C.c_void_p), ('grad_orientations', C.c_void_p),
+        ('grad_relative_orientations', C.c_void_p), ('grad_target_vertices', C.c_void_p),
+        ('grad_target_joints', C.c_void_p), ('grad_vertex_weights', C.c_void_p), ('grad_joint_weights', C.c_void_p),
         ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('hip_stream', C.c_void_p),
     ]
 
@@ -334,6 +349,10 @@ def load():
     lib.smplfit_shape_solve_backward_workspace_bytes.restype = sz
     lib.smplfit_shape_solve_backward_f32.argtypes = [vp, C.POINTER(ShapeSolveBackwardArgs)]
     lib.smplfit_shape_solve_backward_f32.restype = i32
+    lib.smplfit_fit_backward_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.smplfit_fit_backward_workspace_bytes.restype = sz
+    lib.smplfit_fit_backward_f32.argtypes = [vp, C.POINTER(FitBackwardArgs)]
+    lib.smplfit_fit_backward_f32.restype = i32
     lib.smplfit_reload_options.argtypes = []
     lib.smplfit_reload_options.restype = i32
     if os.environ.get('SMPLFIT_LIB') and not hasattr(lib, 'smplfit_abi_version'):
@@ -453,6 +472,9 @@ class Handle:
 
     def shape_solve_backward_workspace_bytes(self, batch: int) -> int:
         return int(load().smplfit_shape_solve_backward_workspace_bytes(self._h, int(batch)))
+
+    def fit_backward_workspace_bytes(self, batch: int, num_iter: int) -> int:
+        return int(load().smplfit_fit_backward_workspace_bytes(self._h, int(batch), int(num_iter)))
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h.value:

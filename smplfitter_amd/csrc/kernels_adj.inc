@@ -243,3 +243,255 @@ __global__ __launch_bounds__(256) void k_adj_combine(const float* __restrict__ g
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (e < n) out[e] = g1[e] + (g2[e] - g3[e]);
 }
+
+// ================================================================================================
+// Adjoint of the whole fit (smplfit_fit_backward_f32, DESIGN.md §17).  The per-instance arithmetic is sf::fit_rot_* /
+// sf::fit_tail_adjoint (sf_stages.h), ONE lane per instance like k_bwd_joint; the vertex passes are one workgroup per
+// instance, one wave per part, every vertex with a single writer.  Vertex arrays here are (B, V, 3) in the caller's
+// vertex order; the part of a vertex comes from the part-aligned segments of the sorted slots.
+//   k_fa_center      centred copies of the targets (the mean over V (+ J) points, fp64 sums in a fixed order)
+//   k_fa_regress     joints regressed from a mesh (the centred targets, a fitted mesh, or the default mesh)
+//   k_fa_partsums    fp64 part sums of (targets, reference mesh): the backward's own, see sf::fit_part_cov
+//   k_fa_rot_fwd     one rotation pass                         k_fa_rot_adj   its adjoint
+//   k_fa_tail        output stage + refinement, forward and adjoint
+//   k_fa_vertex      the part-sum adjoint (a gather) and the regressor's transpose
+//   k_fa_uncenter    the centring step, into the caller's outputs
+//   k_fa_add         dst += src
+// ================================================================================================
+__device__ __forceinline__ double fa_wave_sum(double v) {  // fixed tree: the total in every lane's view of lane 0
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// grid B, block 256
+__global__ __launch_bounds__(256) void k_fa_center(DevModel m, const float* __restrict__ tv, const float* __restrict__ tj,
+                                                   float* __restrict__ ctv, float* __restrict__ ctj) {
+  __shared__ double red[256 * 3];
+  __shared__ double mean[3];
+  const int b = blockIdx.x, tid = threadIdx.x, V = m.V, J = m.J;
+  const float* t = tv + (size_t)b * V * 3;
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int i = tid; i < V; i += 256)
+    for (int c = 0; c < 3; ++c) s[c] += (double)t[(size_t)i * 3 + c];
+  if (tj)
+    for (int j = tid; j < J; j += 256)
+      for (int c = 0; c < 3; ++c) s[c] += (double)tj[((size_t)b * J + j) * 3 + c];
+  for (int c = 0; c < 3; ++c) red[tid * 3 + c] = s[c];
+  __syncthreads();
+  if (tid < 3) {
+    double a = 0.0;
+    for (int k = 0; k < 256; ++k) a += red[k * 3 + tid];
+    mean[tid] = a / (double)(V + (tj ? J : 0));
+  }
+  __syncthreads();
+  for (int k = tid; k < V * 3; k += 256) ctv[(size_t)b * V * 3 + k] = (float)((double)t[k] - mean[k % 3]);
+  if (tj)
+    for (int k = tid; k < J * 3; k += 256)
+      ctj[(size_t)b * J * 3 + k] = (float)((double)tj[(size_t)b * J * 3 + k] - mean[k % 3]);
+}
+
+// grid B (1 for a shared mesh), block 64.  src (B, V, 3), or null: the default mesh.
+__global__ __launch_bounds__(64) void k_fa_regress(DevModel m, const float* __restrict__ src, float* __restrict__ out) {
+  const int b = blockIdx.x, V = m.V;
+  for (int j = threadIdx.x; j < m.J; j += 64) {
+    float a[3] = {0.f, 0.f, 0.f};
+    for (int k = m.reg_start[j]; k < m.reg_start[j + 1]; ++k) {
+      const int i = m.reg_slot[k];
+      const float r = m.reg_val[k];
+      for (int c = 0; c < 3; ++c) a[c] += r * (src ? src[((size_t)b * V + m.perm[i]) * 3 + c] : m.dm[(size_t)c * m.Vp + i]);
+    }
+    for (int c = 0; c < 3; ++c) out[((size_t)b * m.J + j) * 3 + c] = a[c];
+  }
+}
+
+// grid B, block 256.  ref (B, V, 3), or null: the default mesh.  psum (B, J, kPsum) doubles.
+__global__ __launch_bounds__(256) void k_fa_partsums(DevModel m, const float* __restrict__ ctv, const float* __restrict__ ref,
+                                                     const float* __restrict__ vw, double* __restrict__ psum) {
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, V = m.V;
+  for (int p = wave; p < m.J; p += 4) {
+    double acc[sf::kPsum];
+    for (int k = 0; k < sf::kPsum; ++k) acc[k] = 0.0;
+    for (int s = m.part_seg_start[p]; s < m.part_seg_start[p + 1]; ++s) {
+      const int start = m.segments[s * 3], count = m.segments[s * 3 + 1];
+      if (lane >= count) continue;
+      const int i = start + lane, o = m.perm[i];
+      const size_t e = (size_t)b * V + o;
+      const float t[3] = {ctv[e * 3], ctv[e * 3 + 1], ctv[e * 3 + 2]};
+      float a[3];
+      for (int c = 0; c < 3; ++c) a[c] = ref ? ref[e * 3 + c] : m.dm[(size_t)c * m.Vp + i];
+      sf::partsum_vertex_d(t, a, vw ? vw[e] : 1.f, acc);
+    }
+    for (int k = 0; k < sf::kPsum; ++k) {
+      const double r = fa_wave_sum(acc[k]);
+      if (lane == 0) psum[((size_t)b * m.J + p) * sf::kPsum + k] = r;
+    }
+  }
+}
+
+// the joints an instance's rotation stage reads: (B, J, 3), or one (J, 3) row for every instance
+struct FaJoints {
+  const float *tj, *rj;
+  int rj_shared;
+  const float* jw;  // (B, J) or null
+};
+
+// grid ceil(B / 64), block 64
+__global__ __launch_bounds__(64) void k_fa_rot_fwd(DevModel m, const double* __restrict__ psum, FaJoints jn,
+                                                   const float* __restrict__ Gprev, float* __restrict__ Gout, int B) {
+  const int b = blockIdx.x * 64 + threadIdx.x, J = m.J;
+  if (b >= B) return;
+  sf::fit_rot_forward(m.jt, psum + (size_t)b * J * sf::kPsum, jn.tj + (size_t)b * J * 3,
+                      jn.rj + (jn.rj_shared ? 0 : (size_t)b * J * 3), jn.jw ? jn.jw + (size_t)b * J : nullptr,
+                      Gprev ? Gprev + (size_t)b * J * 9 : nullptr, Gout + (size_t)b * J * 9);
+}
+
+// the cotangents a joint-level adjoint leaves for k_fa_vertex: the part records and the joints' / joint weights'
+struct FaJointCot {
+  float* pbar;   // (B, J, kPsum) records [Abar | ct | ca]
+  float* tjbar;  // (B, J, 3) target joints
+  float* rjtbar; // (B, J, 3) reference joints of the joint term (regressed without target joints)
+  float* rjbar;  // (B, J, 3) joints of the solve
+  float* jwbar;  // (B, J)
+};
+
+// grid ceil(B / 64), block 64.  Gbar: the cotangent of the pass's output; Gprev_bar: written when Gprev is given.
+__global__ __launch_bounds__(64) void k_fa_rot_adj(DevModel m, const double* __restrict__ psum, FaJoints jn,
+                                                   const float* __restrict__ Gprev, const float* __restrict__ Gbar,
+                                                   float* __restrict__ Gprev_bar, double* __restrict__ scr, FaJointCot o, int B) {
+  const int b = blockIdx.x * 64 + threadIdx.x, J = m.J;
+  if (b >= B) return;
+  double* sc = scr + (size_t)b * sf::fit_tail_adjoint_scratch(J);
+  sf::fit_rot_adjoint(m.jt, psum + (size_t)b * J * sf::kPsum, jn.tj + (size_t)b * J * 3,
+                      jn.rj + (jn.rj_shared ? 0 : (size_t)b * J * 3), jn.jw ? jn.jw + (size_t)b * J : nullptr,
+                      Gprev ? Gprev + (size_t)b * J * 9 : nullptr, Gbar + (size_t)b * J * 9, o.pbar + (size_t)b * J * sf::kPsum,
+                      Gprev ? Gprev_bar + (size_t)b * J * 9 : nullptr, sc);
+  for (int k = 0; k < J * 3; ++k) {
+    o.tjbar[(size_t)b * J * 3 + k] = (float)sc[k];
+    o.rjtbar[(size_t)b * J * 3 + k] = (float)sc[J * 3 + k];
+    o.rjbar[(size_t)b * J * 3 + k] = 0.f;
+  }
+  for (int k = 0; k < J; ++k) o.jwbar[(size_t)b * J + k] = (float)sc[J * 6 + k];
+}
+
+struct FaTailArgs {
+  const float *G, *betas, *kid, *trans;  // the last iteration's rotations and solution (centred frame)
+  const float* rj_true;                  // (B, J, 3) joints of that solve (refinement only)
+  int final_adjust, nb;
+  const float *g_pose, *g_orient, *g_rel, *g_betas, *g_kid, *g_trans;  // the caller's cotangents or null
+  float *Gbar, *xb, *kb, *tb;  // out: the cotangents of the rotations (B,J,9), betas (B,nb), kid (B), trans (B,3)
+};
+
+// grid ceil(B / 64), block 64
+__global__ __launch_bounds__(64) void k_fa_tail(DevModel m, const double* __restrict__ psum, FaJoints jn, FaTailArgs a,
+                                                double* __restrict__ scr, FaJointCot o, int B) {
+  const int b = blockIdx.x * 64 + threadIdx.x, J = m.J, S = m.S;
+  if (b >= B) return;
+  float x[sf::kAdjMaxUnknowns], xbar[sf::kAdjMaxUnknowns], tbar[3];
+  for (int s = 0; s < S; ++s) x[s] = s < a.nb ? a.betas[(size_t)b * a.nb + s] : 0.f;
+  if (m.jt.n_kid) x[S - 1] = a.kid[b];
+  double* sc = scr + (size_t)b * sf::fit_tail_adjoint_scratch(J);
+  const bool fa = a.final_adjust != 0;
+  sf::fit_tail_adjoint(m.jt, a.G + (size_t)b * J * 9, x, a.trans + (size_t)b * 3, psum + (size_t)b * J * sf::kPsum,
+                       fa ? jn.tj + (size_t)b * J * 3 : nullptr, fa ? jn.rj + (size_t)b * J * 3 : nullptr,
+                       fa ? a.rj_true + (size_t)b * J * 3 : nullptr, jn.jw ? jn.jw + (size_t)b * J : nullptr, fa,
+                       a.g_pose ? a.g_pose + (size_t)b * J * 3 : nullptr, a.g_orient ? a.g_orient + (size_t)b * J * 9 : nullptr,
+                       a.g_rel ? a.g_rel + (size_t)b * J * 9 : nullptr, sc, a.Gbar + (size_t)b * J * 9, xbar, tbar,
+                       o.pbar + (size_t)b * J * sf::kPsum);
+  for (int s = 0; s < a.nb; ++s) a.xb[(size_t)b * a.nb + s] = xbar[s] + (a.g_betas ? a.g_betas[(size_t)b * a.nb + s] : 0.f);
+  a.kb[b] = m.jt.n_kid ? xbar[S - 1] + (a.g_kid ? a.g_kid[b] : 0.f) : 0.f;
+  for (int c = 0; c < 3; ++c) a.tb[(size_t)b * 3 + c] = tbar[c] + (a.g_trans ? a.g_trans[(size_t)b * 3 + c] : 0.f);
+  for (int k = 0; k < J * 3; ++k) {
+    o.tjbar[(size_t)b * J * 3 + k] = (float)sc[sf::fit_tail_tjbar(J) + k];
+    o.rjtbar[(size_t)b * J * 3 + k] = (float)sc[sf::fit_tail_rjtbar(J) + k];
+    o.rjbar[(size_t)b * J * 3 + k] = (float)sc[sf::fit_tail_rjbar(J) + k];
+  }
+  for (int k = 0; k < J; ++k) o.jwbar[(size_t)b * J + k] = (float)sc[sf::fit_tail_jwbar(J) + k];
+}
+
+struct FaVertexArgs {
+  const float *ctv, *ref, *vw;  // ref null: the default mesh (no cotangent)
+  int regressed;                // the joints of the stage were regressed from the vertices
+  float *acc_tv, *acc_tj, *acc_vw, *acc_jw;  // += ; acc_tj with target joints; acc_vw / acc_jw may be null
+  float *meshbar, *jointsbar;   // = ; null with the default mesh
+};
+
+// grid B, block 256
+__global__ __launch_bounds__(256) void k_fa_vertex(DevModel m, FaVertexArgs a, FaJointCot jc) {
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = m.V, J = m.J;
+  if (a.meshbar) {  // (the vertices of the parts that take no sums keep a zero cotangent)
+    for (int k = tid; k < V * 3; k += 256) a.meshbar[(size_t)b * V * 3 + k] = 0.f;
+    __syncthreads();
+  }
+  for (int p = wave; p < J; p += 4) {
+    const float* rec = jc.pbar + ((size_t)b * J + p) * sf::kPsum;
+    for (int s = m.part_seg_start[p]; s < m.part_seg_start[p + 1]; ++s) {
+      const int start = m.segments[s * 3], count = m.segments[s * 3 + 1];
+      if (lane >= count) continue;
+      const int i = start + lane, o = m.perm[i];
+      const size_t e = (size_t)b * V + o;
+      const float t[3] = {a.ctv[e * 3], a.ctv[e * 3 + 1], a.ctv[e * 3 + 2]};
+      float r[3], tb[3], ab[3];
+      for (int c = 0; c < 3; ++c) r[c] = a.ref ? a.ref[e * 3 + c] : m.dm[(size_t)c * m.Vp + i];
+      const float wb = sf::partsum_vertex_adjoint(t, r, a.vw ? a.vw[e] : 1.f, a.vw != nullptr, rec, tb, ab);
+      for (int c = 0; c < 3; ++c) {
+        a.acc_tv[e * 3 + c] += tb[c];
+        if (a.meshbar) a.meshbar[e * 3 + c] = ab[c];
+      }
+      if (a.vw && a.acc_vw) a.acc_vw[e] += wb;
+    }
+  }
+  for (int k = tid; k < J; k += 256)
+    if (a.acc_jw) a.acc_jw[(size_t)b * J + k] += jc.jwbar[(size_t)b * J + k];
+  for (int k = tid; k < J * 3; k += 256) {
+    const size_t e = (size_t)b * J * 3 + k;
+    if (!a.regressed) a.acc_tj[e] += jc.tjbar[e];
+    if (a.jointsbar) a.jointsbar[e] = jc.rjbar[e] + (a.regressed ? 0.f : jc.rjtbar[e]);
+  }
+  if (!a.regressed) return;
+  // the regressor's transpose: joint after joint (the slots of one row are distinct: one writer per vertex and step)
+  for (int j = 0; j < J; ++j) {
+    __syncthreads();
+    const float* gt = jc.tjbar + ((size_t)b * J + j) * 3;
+    const float* gr = jc.rjtbar + ((size_t)b * J + j) * 3;
+    for (int k = m.reg_start[j] + tid; k < m.reg_start[j + 1]; k += 256) {
+      const size_t e = (size_t)b * V + m.perm[m.reg_slot[k]];
+      const float r = m.reg_val[k];
+      for (int c = 0; c < 3; ++c) {
+        a.acc_tv[e * 3 + c] += r * gt[c];
+        if (a.meshbar) a.meshbar[e * 3 + c] += r * gr[c];
+      }
+    }
+  }
+}
+
+// grid B, block 256.  acc_tj null without target joints; the outputs may be null.
+__global__ __launch_bounds__(256) void k_fa_uncenter(DevModel m, const float* __restrict__ acc_tv, const float* __restrict__ acc_tj,
+                                                     const float* __restrict__ g_trans, float* __restrict__ out_tv,
+                                                     float* __restrict__ out_tj) {
+  __shared__ double red[256 * 3];
+  __shared__ float corr[3];
+  const int b = blockIdx.x, tid = threadIdx.x, V = m.V, J = m.J;
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int i = tid; i < V; i += 256)
+    for (int c = 0; c < 3; ++c) s[c] += (double)acc_tv[((size_t)b * V + i) * 3 + c];
+  if (acc_tj)
+    for (int j = tid; j < J; j += 256)
+      for (int c = 0; c < 3; ++c) s[c] += (double)acc_tj[((size_t)b * J + j) * 3 + c];
+  for (int c = 0; c < 3; ++c) red[tid * 3 + c] = s[c];
+  __syncthreads();
+  if (tid < 3) {
+    double t = 0.0;
+    for (int k = 0; k < 256; ++k) t += red[k * 3 + tid];
+    corr[tid] = sf::centring_correction(t, g_trans ? g_trans[(size_t)b * 3 + tid] : 0.f, V + (acc_tj ? J : 0));
+  }
+  __syncthreads();
+  if (out_tv)
+    for (int k = tid; k < V * 3; k += 256) out_tv[(size_t)b * V * 3 + k] = acc_tv[(size_t)b * V * 3 + k] + corr[k % 3];
+  if (out_tj && acc_tj)
+    for (int k = tid; k < J * 3; k += 256) out_tj[(size_t)b * J * 3 + k] = acc_tj[(size_t)b * J * 3 + k] + corr[k % 3];
+}
+
+__global__ __launch_bounds__(256) void k_fa_add(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < n) dst[e] += src[e];
+}

@@ -350,4 +350,242 @@ SF_HD void swing_twist(const float* b_ref, const float* b_tgt, const float* A, f
   m3_mul(Rtw, Rsw, R);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Adjoints of the rotation primitives above (smplfit_fit_backward_f32).  All 3x3 algebra in fp64, on
+// the fp32 values the forward read; cotangents are row-major like their matrices.
+// ---------------------------------------------------------------------------------------------
+SF_HD void d3_mul(const double* a, const double* b, double* o) {  // o = a b
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) o[r * 3 + c] = a[r * 3] * b[c] + a[r * 3 + 1] * b[3 + c] + a[r * 3 + 2] * b[6 + c];
+}
+SF_HD void d3_tmul(const double* a, const double* b, double* o) {  // o = a^T b
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) o[r * 3 + c] = a[r] * b[c] + a[3 + r] * b[3 + c] + a[6 + r] * b[6 + c];
+}
+SF_HD void d3_mult(const double* a, const double* b, double* o) {  // o = a b^T
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) o[r * 3 + c] = a[r * 3] * b[c * 3] + a[r * 3 + 1] * b[c * 3 + 1] + a[r * 3 + 2] * b[c * 3 + 2];
+}
+
+// Adjoint of R = proj_so3(A): with S = R^T A (symmetric; indefinite in the reflection case) solve
+// (tr(S) I - S) w = vee(R^T Rbar - Rbar^T R), vee(K) = (K21, K02, K10); Abar = R hat(w).  No SVD; singular exactly
+// where the projection is (sigma2 + d sigma3 = 0): the division then gives inf / NaN for that matrix only.
+SF_HD void proj_so3_adjoint(const double* A, const double* R, const double* Rbar, double* Abar) {
+  double S[9], K[9];
+  d3_tmul(R, A, S);
+  d3_tmul(R, Rbar, K);
+  const double v[3] = {K[7] - K[5], K[2] - K[6], K[3] - K[1]};
+  // symmetrised: R is the fp32 rounding of the projection
+  const double s01 = 0.5 * (S[1] + S[3]), s02 = 0.5 * (S[2] + S[6]), s12 = 0.5 * (S[5] + S[7]);
+  const double tr = S[0] + S[4] + S[8];
+  const double m00 = tr - S[0], m11 = tr - S[4], m22 = tr - S[8], m01 = -s01, m02 = -s02, m12 = -s12;
+  // symmetric 3x3 solve by the adjugate
+  const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+  const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+  const double det = m00 * c00 + m01 * c01 + m02 * c02;
+  const double id = 1.0 / det;
+  const double w0 = (c00 * v[0] + c01 * v[1] + c02 * v[2]) * id;
+  const double w1 = (c01 * v[0] + c11 * v[1] + c12 * v[2]) * id;
+  const double w2 = (c02 * v[0] + c12 * v[1] + c22 * v[2]) * id;
+  const double H[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
+  d3_mul(R, H, Abar);
+}
+
+// Adjoint of centered_cov.  The covariance is A = sum_i w_i (t_i - ct)(a_i - ca)^T, so with the cotangent Abar the
+// cotangents of the part sums are Rawbar = Abar, stbar = -Abar ca, sabar = -Abar^T ct, swbar = ct^T Abar ca.  The vertex
+// pass applies them in the factored form (partsum_vertex_adjoint), which does not cancel: the record it reads is
+// [Abar 9 | ct 3 | ca 3 | 0] (part_cotangent).  The cotangents of the centres: -Abar (sa - sw ca), -Abar^T (st - sw ct).
+SF_HD void part_cotangent(const double* Abar, const double* ct, const double* ca, float* rec) {
+  for (int k = 0; k < 9; ++k) rec[k] = (float)Abar[k];
+  for (int c = 0; c < 3; ++c) {
+    rec[9 + c] = (float)ct[c];
+    rec[12 + c] = (float)ca[c];
+  }
+  rec[15] = 0.f;
+}
+SF_HD void centered_cov_centres_adjoint(const double* Abar, const double* ps, const double* ct, const double* ca,
+                                        double* ctbar, double* cabar) {
+  const double sw = ps[15];
+  for (int r = 0; r < 3; ++r) {
+    ctbar[r] = cabar[r] = 0.0;
+    for (int c = 0; c < 3; ++c) {
+      ctbar[r] -= Abar[r * 3 + c] * (ps[12 + c] - sw * ca[c]);
+      cabar[r] -= Abar[c * 3 + r] * (ps[9 + c] - sw * ct[c]);
+    }
+  }
+}
+
+// Rodrigues R = cos I + sin hat(a) + (1 - cos) a a^T of r = theta a, in fp64, and its vector-Jacobian product with the
+// reference's convention at r = 0 (axis = 0 there: the gradient is 0, pt/_autograd.py _div0).
+SF_HD void rodrigues_d(const double* r, double* R) {
+  const double th = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  const double a[3] = {th == 0.0 ? 0.0 : r[0] / th, th == 0.0 ? 0.0 : r[1] / th, th == 0.0 ? 0.0 : r[2] / th};
+  const double sn = sin(th), cs = cos(th), c1 = 1.0 - cs;
+  R[0] = c1 * a[0] * a[0] + cs; R[1] = c1 * a[0] * a[1] - sn * a[2]; R[2] = c1 * a[0] * a[2] + sn * a[1];
+  R[3] = c1 * a[0] * a[1] + sn * a[2]; R[4] = c1 * a[1] * a[1] + cs; R[5] = c1 * a[1] * a[2] - sn * a[0];
+  R[6] = c1 * a[0] * a[2] - sn * a[1]; R[7] = c1 * a[1] * a[2] + sn * a[0]; R[8] = c1 * a[2] * a[2] + cs;
+}
+SF_HD void rodrigues_vjp_d(const double* r, const double* Rb, double* rbar) {
+  const double th = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+  if (th == 0.0) {
+    rbar[0] = rbar[1] = rbar[2] = 0.0;
+    return;
+  }
+  const double a[3] = {r[0] / th, r[1] / th, r[2] / th};
+  const double sn = sin(th), cs = cos(th);
+  const double vv[3] = {Rb[7] - Rb[5], Rb[2] - Rb[6], Rb[3] - Rb[1]};
+  double Ra[3], Rta[3];
+  for (int i = 0; i < 3; ++i) {
+    Ra[i] = Rb[i * 3] * a[0] + Rb[i * 3 + 1] * a[1] + Rb[i * 3 + 2] * a[2];
+    Rta[i] = Rb[i] * a[0] + Rb[3 + i] * a[1] + Rb[6 + i] * a[2];
+  }
+  const double aRa = a[0] * Ra[0] + a[1] * Ra[1] + a[2] * Ra[2], tr = Rb[0] + Rb[4] + Rb[8];
+  const double avv = a[0] * vv[0] + a[1] * vv[1] + a[2] * vv[2];
+  const double thbar = -sn * tr + cs * avv + sn * aRa;
+  double abar[3], ad = 0.0;
+  for (int i = 0; i < 3; ++i) {
+    abar[i] = sn * vv[i] + (1.0 - cs) * (Ra[i] + Rta[i]);
+    ad += a[i] * abar[i];
+  }
+  for (int i = 0; i < 3; ++i) rbar[i] = thbar * a[i] + (abar[i] - a[i] * ad) / th;
+}
+
+// Adjoint of the normalisation b = v / |v| (0 where |v| == 0, with a zero gradient there): vbar += ...
+SF_HD void normalize_adjoint_add(const double* v, const double* bbar, double* vbar) {
+  const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  if (n == 0.0) return;
+  const double b[3] = {v[0] / n, v[1] / n, v[2] / n};
+  const double d = b[0] * bbar[0] + b[1] * bbar[1] + b[2] * bbar[2];
+  for (int c = 0; c < 3; ++c) vbar[c] += (bbar[c] - b[c] * d) / n;
+}
+
+// Adjoint of swing_twist: from the cotangent Rbar of the part rotation those of the centred covariance A and of the two
+// (unnormalised) bones.  The forward is re-evaluated in fp64.
+SF_HD void swing_twist_adjoint(const double* b_ref, const double* b_tgt, const double* A, const double* Rbar, double* Abar,
+                               double* brefbar, double* btgtbar) {
+  const double nr = sqrt(b_ref[0] * b_ref[0] + b_ref[1] * b_ref[1] + b_ref[2] * b_ref[2]);
+  const double nt = sqrt(b_tgt[0] * b_tgt[0] + b_tgt[1] * b_tgt[1] + b_tgt[2] * b_tgt[2]);
+  double br[3], bt[3];
+  for (int c = 0; c < 3; ++c) {
+    br[c] = nr == 0.0 ? 0.0 : b_ref[c] / nr;
+    bt[c] = nt == 0.0 ? 0.0 : b_tgt[c] / nt;
+  }
+  // swing
+  const double cr[3] = {br[1] * bt[2] - br[2] * bt[1], br[2] * bt[0] - br[0] * bt[2], br[0] * bt[1] - br[1] * bt[0]};
+  const double dot = br[0] * bt[0] + br[1] * bt[1] + br[2] * bt[2];
+  const double sn = sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]);
+  const double ang = atan2(sn, dot);
+  const double f = sn == 0.0 ? 0.0 : ang / sn;
+  const double rv[3] = {cr[0] * f, cr[1] * f, cr[2] * f};
+  double Rsw[9], H[9];
+  rodrigues_d(rv, Rsw);
+  d3_mult(Rsw, A, H);  // H = R_swing A^T
+  const double trH = H[0] + H[4] + H[8];
+  double Hb[3], Htb[3];
+  for (int i = 0; i < 3; ++i) {
+    Hb[i] = H[i * 3] * bt[0] + H[i * 3 + 1] * bt[1] + H[i * 3 + 2] * bt[2];
+    Htb[i] = H[i] * bt[0] + H[3 + i] * bt[1] + H[6 + i] * bt[2];
+  }
+  const double bHb = bt[0] * Hb[0] + bt[1] * Hb[1] + bt[2] * Hb[2];
+  const double vee[3] = {H[5] - H[7], H[6] - H[2], H[1] - H[3]};
+  const double y = bt[0] * vee[0] + bt[1] * vee[1] + bt[2] * vee[2], x = trH - bHb;
+  const double ang2 = atan2(y, x);
+  const double rv2[3] = {bt[0] * ang2, bt[1] * ang2, bt[2] * ang2};
+  double Rtw[9];
+  rodrigues_d(rv2, Rtw);
+  // reverse: R = Rtw Rsw
+  double Rtwbar[9], Rswbar[9], rv2bar[3];
+  d3_mult(Rbar, Rsw, Rtwbar);
+  d3_tmul(Rtw, Rbar, Rswbar);
+  rodrigues_vjp_d(rv2, Rtwbar, rv2bar);
+  double btbar[3], brbar[3] = {0.0, 0.0, 0.0};
+  double ang2bar = 0.0;
+  for (int c = 0; c < 3; ++c) {
+    btbar[c] = rv2bar[c] * ang2;
+    ang2bar += rv2bar[c] * bt[c];
+  }
+  const double q = x * x + y * y;
+  const double ybar = q == 0.0 ? 0.0 : ang2bar * x / q, xbar = q == 0.0 ? 0.0 : -ang2bar * y / q;
+  double Hbar[9];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) Hbar[r * 3 + c] = (r == c ? xbar : 0.0) - xbar * bt[r] * bt[c];
+  Hbar[5] += ybar * bt[0]; Hbar[7] -= ybar * bt[0];
+  Hbar[6] += ybar * bt[1]; Hbar[2] -= ybar * bt[1];
+  Hbar[1] += ybar * bt[2]; Hbar[3] -= ybar * bt[2];
+  for (int c = 0; c < 3; ++c) btbar[c] += ybar * vee[c] - xbar * (Hb[c] + Htb[c]);
+  // H = Rsw A^T
+  double HA[9];
+  d3_mul(Hbar, A, HA);
+  for (int k = 0; k < 9; ++k) Rswbar[k] += HA[k];
+  d3_tmul(Hbar, Rsw, Abar);  // Abar = Hbar^T Rsw
+  // swing: Rsw = rodrigues(cr * ang / sn)
+  if (sn != 0.0) {
+    double rvbar[3], crbar[3];
+    rodrigues_vjp_d(rv, Rswbar, rvbar);
+    double fbar = 0.0;
+    for (int c = 0; c < 3; ++c) {
+      crbar[c] = rvbar[c] * f;
+      fbar += rvbar[c] * cr[c];
+    }
+    const double angbar = fbar / sn;
+    double snbar = -fbar * ang / (sn * sn);
+    const double q2 = sn * sn + dot * dot;
+    snbar += angbar * dot / q2;
+    const double dotbar = -angbar * sn / q2;
+    for (int c = 0; c < 3; ++c) crbar[c] += snbar * cr[c] / sn;
+    // cr = br x bt
+    brbar[0] += bt[1] * crbar[2] - bt[2] * crbar[1];
+    brbar[1] += bt[2] * crbar[0] - bt[0] * crbar[2];
+    brbar[2] += bt[0] * crbar[1] - bt[1] * crbar[0];
+    btbar[0] += crbar[1] * br[2] - crbar[2] * br[1];
+    btbar[1] += crbar[2] * br[0] - crbar[0] * br[2];
+    btbar[2] += crbar[0] * br[1] - crbar[1] * br[0];
+    for (int c = 0; c < 3; ++c) {
+      brbar[c] += dotbar * bt[c];
+      btbar[c] += dotbar * br[c];
+    }
+  }
+  for (int c = 0; c < 3; ++c) brefbar[c] = btgtbar[c] = 0.0;
+  normalize_adjoint_add(b_ref, brbar, brefbar);
+  normalize_adjoint_add(b_tgt, btbar, btgtbar);
+}
+
+// Adjoint of mat2rotvec as evaluated above (the four-way quaternion branch, 2 atan2(|xyz|, w) / |xyz| xyz; gradient 0
+// where |xyz| == 0, the _div0 convention): relbar += J^T rvbar.
+SF_HD void mat2rotvec_adjoint_add(const float* r, const double* rvbar, double* relbar) {
+  const double r00 = r[0], r01 = r[1], r02 = r[2], r10 = r[3], r11 = r[4], r12 = r[5], r20 = r[6], r21 = r[7], r22 = r[8];
+  const float trace = r[0] + r[4] + r[8];
+  double x, y, z, w;
+  int br;
+  if (trace > 0.f) {
+    br = 0; x = r21 - r12; y = r02 - r20; z = r10 - r01; w = 1.0 + ((r00 + r11) + r22);
+  } else if (r[0] > r[4] && r[0] > r[8]) {
+    br = 1; x = (1.0 - r22) + (r00 - r11); y = r10 + r01; z = r02 + r20; w = r21 - r12;
+  } else if (r[4] > r[8]) {
+    br = 2; x = r10 + r01; y = (1.0 - r22) - (r00 - r11); z = r21 + r12; w = r02 - r20;
+  } else {
+    br = 3; x = r02 + r20; y = r21 + r12; z = (1.0 + r22) - (r00 + r11); w = r10 - r01;
+  }
+  const double n2 = x * x + y * y + z * z, n = sqrt(n2);
+  if (n == 0.0) return;
+  const double at = atan2(n, w), f = 2.0 * at / n, q = n2 + w * w;
+  const double fbar = rvbar[0] * x + rvbar[1] * y + rvbar[2] * z;
+  const double nbar = fbar * (2.0 * (w / q) / n - 2.0 * at / n2);
+  const double wb = fbar * (-2.0 / q);
+  const double xb = f * rvbar[0] + nbar * x / n, yb = f * rvbar[1] + nbar * y / n, zb = f * rvbar[2] + nbar * z / n;
+  if (br == 0) {
+    relbar[7] += xb; relbar[5] -= xb; relbar[2] += yb; relbar[6] -= yb; relbar[3] += zb; relbar[1] -= zb;
+    relbar[0] += wb; relbar[4] += wb; relbar[8] += wb;
+  } else if (br == 1) {
+    relbar[8] -= xb; relbar[0] += xb; relbar[4] -= xb; relbar[3] += yb; relbar[1] += yb; relbar[2] += zb; relbar[6] += zb;
+    relbar[7] += wb; relbar[5] -= wb;
+  } else if (br == 2) {
+    relbar[3] += xb; relbar[1] += xb; relbar[8] -= yb; relbar[0] -= yb; relbar[4] += yb; relbar[7] += zb; relbar[5] += zb;
+    relbar[2] += wb; relbar[6] -= wb;
+  } else {
+    relbar[2] += xb; relbar[6] += xb; relbar[7] += yb; relbar[5] += yb; relbar[8] += zb; relbar[0] -= zb; relbar[4] -= zb;
+    relbar[3] += wb; relbar[1] -= wb;
+  }
+}
+
 }  // namespace sf

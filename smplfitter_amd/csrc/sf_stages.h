@@ -1880,6 +1880,404 @@ SF_HD float shape_adjoint_point(const float* pos, const float* al, const float* 
   return dot;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Adjoints of the two rotation stages of a fit (smplfit_fit_backward_f32): the rotation pass
+// (_fit_global_rotations, bodyfitter.py:1321-1416) and the dependent refinement with the output stage behind it
+// (:1418-1544, :513-539).  ONE lane per instance, like forward_joint_backward; the 3x3 algebra in fp64.  Shared by
+// kernels_adj.inc and the host build of tests/hostemu/hostemu_fit_adjoint.cpp.
+// ---------------------------------------------------------------------------------------------
+
+// partsum_vertex in fp64 (the backward's own part sums): acc is a kPsum record of doubles, w = 1 without weights.
+SF_HD void partsum_vertex_d(const float* t, const float* a_in, float w, double* acc) {
+  const double wd = (double)w;
+  for (int r = 0; r < 3; ++r) {
+    const double tr = (double)t[r];
+    for (int c = 0; c < 3; ++c) acc[r * 3 + c] += tr * ((double)a_in[c] * wd);
+    acc[9 + r] += tr * wd;
+    acc[12 + r] += (double)a_in[r] * wd;
+  }
+  acc[15] += wd;
+}
+
+// The centres and the centred covariance of part j (joint_stage's, in fp64 on the backward's own fp64 part sums: the
+// fp32 form cancels to ~1e-4 of A, which the gradients would inherit), and the part's rotation from its fp32 rounding.
+SF_HD void fit_part_cov(const JointTabs& tb, int j, const double* psum, const float* tj, const float* rj, const float* jw,
+                        double* ct, double* ca, double* A) {
+  const int c0 = tb.cas_start[j], n = tb.cas_start[j + 1] - c0;
+  const double inv = 1.0 / (double)n;
+  double sums[kPsum];
+  for (int c = 0; c < 3; ++c) ct[c] = ca[c] = 0.0;
+  for (int q = 0; q < n; ++q) {
+    const int m = tb.cas_flat[c0 + q];
+    for (int c = 0; c < 3; ++c) {
+      ct[c] += inv * (double)tj[m * 3 + c];
+      ca[c] += inv * (double)rj[m * 3 + c];
+    }
+  }
+  if (tb.part_type[j] == 1) {
+    for (int k = 0; k < kPsum; ++k) sums[k] = 0.0;
+    for (int q = 0; q < n; ++q) {
+      const int m = tb.cas_flat[c0 + q];
+      const double w = jw ? (double)jw[m] : 1.0;
+      for (int r = 0; r < 3; ++r) {
+        const double t = (double)tj[m * 3 + r];
+        for (int c = 0; c < 3; ++c) sums[r * 3 + c] += t * ((double)rj[m * 3 + c] * w);
+        sums[9 + r] += t * w;
+        sums[12 + r] += (double)rj[m * 3 + r] * w;
+      }
+      sums[15] += w;
+    }
+  } else {
+    for (int k = 0; k < kPsum; ++k) sums[k] = psum[j * kPsum + k];
+  }
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c)
+      A[r * 3 + c] = sums[r * 3 + c] - sums[9 + r] * ca[c] - ct[r] * sums[12 + c] + sums[15] * (ct[r] * ca[c]);
+}
+SF_HD void fit_part_rotation(const JointTabs& tb, int j, const double* psum, const float* tj, const float* rj,
+                             const float* jw, float* R) {
+  const int type = tb.part_type[j];
+  m3_identity(R);
+  if (type == 0) return;
+  double ct[3], ca[3], A[9];
+  float Af[9];
+  fit_part_cov(tb, j, psum, tj, rj, jw, ct, ca, A);
+  for (int k = 0; k < 9; ++k) Af[k] = (float)A[k];
+  if (type == 2) {
+    const int c0 = tb.cas_start[j], k0 = tb.cas_flat[c0], k1 = tb.cas_flat[c0 + 1];
+    float br[3], bt[3];
+    for (int c = 0; c < 3; ++c) {
+      br[c] = rj[k1 * 3 + c] - rj[k0 * 3 + c];
+      bt[c] = tj[k1 * 3 + c] - tj[k0 * 3 + c];
+    }
+    swing_twist(br, bt, Af, R);
+  } else {
+    proj_so3(Af, R);
+  }
+}
+
+// One rotation pass of an instance: Gout_j = R_src(j) Gprev_j (Gprev null: identity), the toes taking the feet.
+SF_HD void fit_rot_forward(const JointTabs& tb, const double* psum, const float* tj, const float* rj, const float* jw,
+                           const float* Gprev, float* Gout) {
+  for (int j = 0; j < tb.J; ++j) {
+    const int src = tb.toe_src[j] >= 0 ? tb.toe_src[j] : j;
+    float R[9];
+    fit_part_rotation(tb, src, psum, tj, rj, jw, R);
+    if (Gprev) {
+      m3_mul(R, Gprev + j * 9, Gout + j * 9);
+    } else {
+      for (int k = 0; k < 9; ++k) Gout[j * 9 + k] = R[k];
+    }
+  }
+}
+
+SF_HD int fit_rot_adjoint_scratch(int J) { return J * 7; }  // doubles: tjbar (J,3), rjbar (J,3), jwbar (J)
+
+// Adjoint of fit_rot_forward.  Gbar (J,9): the cotangent of Gout.  Outputs: pbar (J,kPsum) the cotangents of the part
+// sums as records [Abar | ct | ca] (part_cotangent; 0 for the parts that read none), Gprev_bar (J,9; null without Gprev), and in `scr` (fit_rot_adjoint_scratch
+// doubles) the cotangents of the target joints, the reference joints and the joint weights.
+SF_HD void fit_rot_adjoint(const JointTabs& tb, const double* psum, const float* tj, const float* rj, const float* jw,
+                           const float* Gprev, const float* Gbar, float* pbar, float* Gprev_bar, double* scr) {
+  const int J = tb.J;
+  double *tjb = scr, *rjb = scr + J * 3, *jwb = scr + J * 6;
+  for (int k = 0; k < J * 7; ++k) scr[k] = 0.0;
+  for (int k = 0; k < J * kPsum; ++k) pbar[k] = 0.f;
+  for (int j = 0; j < J; ++j) {
+    if (tb.toe_src[j] >= 0) continue;
+    const int type = tb.part_type[j];
+    float Rf[9];
+    fit_part_rotation(tb, j, psum, tj, rj, jw, Rf);
+    double R[9], Rbar[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < 9; ++k) R[k] = (double)Rf[k];
+    for (int t = 0; t < J; ++t) {  // the part itself and the toes that copy it
+      if (t != j && tb.toe_src[t] != j) continue;
+      double gb[9], tmp[9];
+      for (int k = 0; k < 9; ++k) gb[k] = (double)Gbar[t * 9 + k];
+      if (Gprev) {
+        double gp[9];
+        for (int k = 0; k < 9; ++k) gp[k] = (double)Gprev[t * 9 + k];
+        d3_mult(gb, gp, tmp);
+        for (int k = 0; k < 9; ++k) Rbar[k] += tmp[k];
+        d3_tmul(R, gb, tmp);
+        for (int k = 0; k < 9; ++k) Gprev_bar[t * 9 + k] = (float)tmp[k];
+      } else {
+        for (int k = 0; k < 9; ++k) Rbar[k] += gb[k];
+      }
+    }
+    if (type == 0) continue;
+    double A[9], ct[3], ca[3], Abar[9];
+    fit_part_cov(tb, j, psum, tj, rj, jw, ct, ca, A);
+    const int c0 = tb.cas_start[j], n = tb.cas_start[j + 1] - c0;
+    if (type == 2) {
+      const int k0 = tb.cas_flat[c0], k1 = tb.cas_flat[c0 + 1];
+      double br[3], bt[3], brb[3], btb[3];
+      for (int c = 0; c < 3; ++c) {
+        br[c] = (double)(rj[k1 * 3 + c] - rj[k0 * 3 + c]);
+        bt[c] = (double)(tj[k1 * 3 + c] - tj[k0 * 3 + c]);
+      }
+      swing_twist_adjoint(br, bt, A, Rbar, Abar, brb, btb);
+      for (int c = 0; c < 3; ++c) {
+        rjb[k1 * 3 + c] += brb[c];
+        rjb[k0 * 3 + c] -= brb[c];
+        tjb[k1 * 3 + c] += btb[c];
+        tjb[k0 * 3 + c] -= btb[c];
+      }
+    } else {
+      proj_so3_adjoint(A, R, Rbar, Abar);
+    }
+    if (type == 1) {  // the sums are those of the part's joints: centres and sums in one go
+      const double inv = 1.0 / (double)n;
+      double tcb[3] = {0, 0, 0}, acb[3] = {0, 0, 0};  // cotangents of the centres
+      for (int q = 0; q < n; ++q) {
+        const int m = tb.cas_flat[c0 + q];
+        const double w = jw ? (double)jw[m] : 1.0;
+        double wb = 0.0;
+        for (int r = 0; r < 3; ++r) {
+          double tb_r = 0.0, ab_r = 0.0;  // Abar (a - ca) w, Abar^T (t - ct) w
+          for (int c = 0; c < 3; ++c) {
+            tb_r += Abar[r * 3 + c] * ((double)rj[m * 3 + c] - ca[c]);
+            ab_r += Abar[c * 3 + r] * ((double)tj[m * 3 + c] - ct[c]);
+          }
+          tjb[m * 3 + r] += tb_r * w;
+          rjb[m * 3 + r] += ab_r * w;
+          tcb[r] -= tb_r * w;
+          acb[r] -= ab_r * w;
+          wb += ab_r * ((double)rj[m * 3 + r] - ca[r]);
+        }
+        if (jw) jwb[m] += wb;
+      }
+      for (int q = 0; q < n; ++q) {
+        const int m = tb.cas_flat[c0 + q];
+        for (int c = 0; c < 3; ++c) {
+          tjb[m * 3 + c] += inv * tcb[c];
+          rjb[m * 3 + c] += inv * acb[c];
+        }
+      }
+    } else {
+      double ctb[3], cab[3];
+      centered_cov_centres_adjoint(Abar, psum + j * kPsum, ct, ca, ctb, cab);
+      const double inv = 1.0 / (double)n;
+      for (int q = 0; q < n; ++q) {
+        const int m = tb.cas_flat[c0 + q];
+        for (int c = 0; c < 3; ++c) {
+          tjb[m * 3 + c] += inv * ctb[c];
+          rjb[m * 3 + c] += inv * cab[c];
+        }
+      }
+      part_cotangent(Abar, ct, ca, pbar + j * kPsum);
+    }
+  }
+}
+
+// Adjoint of partsum_vertex for the vertex's target t, reference a and weight (returned; meaningful when weighted), from
+// the part's record [Abar | ct | ca] (part_cotangent): tbar = w Abar (a - ca), abar = w Abar^T (t - ct),
+// wbar = (t - ct)^T Abar (a - ca).
+SF_HD float partsum_vertex_adjoint(const float* t, const float* a, float w, bool weighted, const float* rec, float* tbar,
+                                   float* abar) {
+  const float ws = weighted ? w : 1.0f;
+  const float dt[3] = {t[0] - rec[9], t[1] - rec[10], t[2] - rec[11]};
+  const float da[3] = {a[0] - rec[12], a[1] - rec[13], a[2] - rec[14]};
+  float wb = 0.f;
+  for (int r = 0; r < 3; ++r) {
+    const float tb_r = (rec[r * 3] * da[0] + rec[r * 3 + 1] * da[1]) + rec[r * 3 + 2] * da[2];
+    const float ab_r = (rec[r] * dt[0] + rec[3 + r] * dt[1]) + rec[6 + r] * dt[2];
+    tbar[r] = tb_r * ws;
+    abar[r] = ab_r * ws;
+    wb += ab_r * da[r];
+  }
+  return wb;
+}
+
+// Centring: the targets enter the fit minus their mean over the N points of the instance and the returned trans is the
+// solve's plus that mean, so the cotangent of a point is that of its centred copy plus (g_trans - sum of those) / N.
+SF_HD float centring_correction(double sum, float g_trans, int N) { return (float)(((double)g_trans - sum) / (double)N); }
+
+SF_HD int fit_tail_adjoint_scratch(int J) { return J * 40; }  // doubles
+// offsets into the scratch of the cotangents the caller reads back: target joints, joint-term reference joints, true
+// reference joints (J,3 each) and joint weights (J)
+SF_HD int fit_tail_tjbar(int J) { return J * 30; }
+SF_HD int fit_tail_rjtbar(int J) { return J * 33; }
+SF_HD int fit_tail_rjbar(int J) { return J * 36; }
+SF_HD int fit_tail_jwbar(int J) { return J * 39; }
+
+// Output stage and refinement of one instance, forward and adjoint.  G (J,9): the rotations in front of the refinement;
+// x (S): every shape unknown (padding and kid included); trans: in the centred frame; psum: the part sums of the targets
+// against the fitted mesh; tj / rj_term: the joints of the joint term; rj_true: the joints of the solve; g_pose (J,3),
+// g_orient, g_rel (J,9): the caller's cotangents or null.  Outputs: Gbar (J,9), xbar (S), tbar (3), pbar (J,kPsum) and
+// the scratch regions named above.  Without final_adjust the refinement is the identity (xbar, tbar, pbar = 0).
+SF_HD void fit_tail_adjoint(const JointTabs& tb, const float* G, const float* x, const float* trans, const double* psum,
+                            const float* tj, const float* rj_term, const float* rj_true, const float* jw,
+                            bool final_adjust, const float* g_pose, const float* g_orient, const float* g_rel,
+                            double* scr, float* Gbar, float* xbar, float* tbar, float* pbar) {
+  const int J = tb.J, S = tb.S, S1 = S + 1;
+  double *Rc = scr, *pos = scr + J * 9, *T = scr + J * 12, *Rcb = scr + J * 15, *posb = scr + J * 24, *auxb = scr + J * 27;
+  double *tjb = scr + fit_tail_tjbar(J), *rjtb = scr + fit_tail_rjtbar(J), *rjb = scr + fit_tail_rjbar(J),
+         *jwb = scr + fit_tail_jwbar(J);
+  for (int k = 0; k < J * 40; ++k) scr[k] = 0.0;
+  for (int k = 0; k < J * kPsum; ++k) pbar[k] = 0.f;
+  for (int s = 0; s < S; ++s) xbar[s] = 0.f;
+  for (int c = 0; c < 3; ++c) tbar[c] = 0.f;
+  for (int k = 0; k < J * 9; ++k) Rc[k] = (double)G[k];
+  // ---- forward of the refinement (refine_stage)
+  if (final_adjust) {
+    double* aux = posb;  // (rest joints: only needed for the bones; posb is zeroed again below)
+    for (int k = 0; k < J * 3; ++k) {
+      double acc = 0.0;
+      for (int s = 0; s < S; ++s) acc += (double)tb.j_ext[k * S1 + 1 + s] * (double)x[s];
+      aux[k] = (double)tb.j_ext[k * S1] + acc;
+    }
+    for (int k = 0; k < J * 3; ++k) {
+      const int j = k / 3, c = k % 3;
+      T[k] = aux[k] - (j > 0 ? aux[tb.parents[j] * 3 + c] : 0.0);
+      if (j == 0) pos[k] = aux[k] + (double)trans[c];
+    }
+    for (int k = 0; k < J * 3; ++k) posb[k] = 0.0;
+    for (int lv = 0; lv <= tb.adj_last_level; ++lv) {
+      const int l0 = tb.fk_level_start[lv], nl = tb.fk_level_start[lv + 1] - l0;
+      for (int q = 0; q < nl; ++q) {
+        const int j = tb.fk_js[l0 + q], p = tb.parents[j];
+        for (int c = 0; c < 3; ++c)
+          pos[j * 3 + c] = pos[p * 3 + c] + (Rc[p * 9 + c * 3] * T[j * 3] + Rc[p * 9 + c * 3 + 1] * T[j * 3 + 1] + Rc[p * 9 + c * 3 + 2] * T[j * 3 + 2]);
+      }
+      const int a0 = tb.adj_level_start[lv], na = tb.adj_level_start[lv + 1] - a0;
+      for (int q = 0; q < na; ++q) {
+        const int i = tb.adj_parts[a0 + q];
+        const double* ps = psum + i * kPsum;
+        float Af[9], Rf[9], Rn[9];
+        for (int r = 0; r < 3; ++r)
+          for (int c = 0; c < 3; ++c) {
+            const double ctr = pos[i * 3 + r], cac = (double)rj_true[i * 3 + c];
+            double a = ps[r * 3 + c] - ps[9 + r] * cac - ctr * ps[12 + c] + ps[15] * (ctr * cac);
+            for (int m0 = tb.cas_start[i]; m0 < tb.cas_start[i + 1]; ++m0) {
+              const int m = tb.cas_flat[m0];
+              a += ((double)tj[m * 3 + r] - ctr) * (((double)rj_term[m * 3 + c] - cac) * (jw ? (double)jw[m] : 1.0));
+            }
+            Af[r * 3 + c] = (float)a;
+          }
+        proj_so3(Af, Rf);
+        m3_mul(Rf, G + i * 9, Rn);
+        for (int k = 0; k < 9; ++k) Rc[i * 9 + k] = (double)Rn[k];
+      }
+    }
+    for (int j = 0; j < J; ++j)
+      if (tb.toe_src[j] >= 0)
+        for (int k = 0; k < 9; ++k) Rc[j * 9 + k] = Rc[tb.toe_src[j] * 9 + k];
+  }
+  // ---- output stage: orientations = Rc, rel_j = Rc_p^T Rc_j, pose_j = log(rel_j)
+  for (int k = 0; k < J * 9; ++k) Rcb[k] = g_orient ? (double)g_orient[k] : 0.0;
+  for (int j = 0; j < J; ++j) {
+    double relb[9];
+    for (int k = 0; k < 9; ++k) relb[k] = g_rel ? (double)g_rel[j * 9 + k] : 0.0;
+    if (g_pose) {
+      double rel[9];
+      float relf[9];
+      if (j > 0) d3_tmul(Rc + tb.parents[j] * 9, Rc + j * 9, rel);
+      else for (int k = 0; k < 9; ++k) rel[k] = Rc[k];
+      for (int k = 0; k < 9; ++k) relf[k] = (float)rel[k];
+      const double gp[3] = {(double)g_pose[j * 3], (double)g_pose[j * 3 + 1], (double)g_pose[j * 3 + 2]};
+      mat2rotvec_adjoint_add(relf, gp, relb);
+    }
+    if (j > 0) {
+      const int p = tb.parents[j];
+      double tmp[9];
+      d3_mult(Rc + j * 9, relb, tmp);  // Rbar_p += R_j relbar^T
+      for (int k = 0; k < 9; ++k) Rcb[p * 9 + k] += tmp[k];
+      d3_mul(Rc + p * 9, relb, tmp);   // Rbar_j += R_p relbar
+      for (int k = 0; k < 9; ++k) Rcb[j * 9 + k] += tmp[k];
+    } else {
+      for (int k = 0; k < 9; ++k) Rcb[k] += relb[k];
+    }
+  }
+  if (!final_adjust) {
+    for (int k = 0; k < J * 9; ++k) Gbar[k] = (float)Rcb[k];
+    return;
+  }
+  // ---- adjoint of the refinement, reverse tree order
+  for (int j = 0; j < J; ++j)
+    if (tb.toe_src[j] >= 0)
+      for (int k = 0; k < 9; ++k) {
+        Rcb[tb.toe_src[j] * 9 + k] += Rcb[j * 9 + k];
+        Rcb[j * 9 + k] = 0.0;
+      }
+  for (int k = 0; k < J * 9; ++k) Gbar[k] = 0.f;
+  for (int lv = tb.adj_last_level; lv >= 0; --lv) {
+    const int a0 = tb.adj_level_start[lv], na = tb.adj_level_start[lv + 1] - a0;
+    for (int q = 0; q < na; ++q) {
+      const int i = tb.adj_parts[a0 + q];
+      const double* ps = psum + i * kPsum;
+      double Gi[9], Rf[9], Rfb[9], tmp[9], A[9], Abar[9], ct[3], ca[3];
+      for (int k = 0; k < 9; ++k) Gi[k] = (double)G[i * 9 + k];
+      d3_mult(Rc + i * 9, Gi, Rf);        // Rf = Rc_i G_i^T
+      d3_mult(Rcb + i * 9, Gi, Rfb);      // Rfbar = Rcbar_i G_i^T
+      d3_tmul(Rf, Rcb + i * 9, tmp);      // Gbar_i = Rf^T Rcbar_i
+      for (int k = 0; k < 9; ++k) Gbar[i * 9 + k] = (float)tmp[k];
+      for (int k = 0; k < 9; ++k) Rcb[i * 9 + k] = 0.0;  // consumed
+      for (int c = 0; c < 3; ++c) ct[c] = pos[i * 3 + c], ca[c] = (double)rj_true[i * 3 + c];
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+          double a = ps[r * 3 + c] - ps[9 + r] * ca[c] - ct[r] * ps[12 + c] + ps[15] * (ct[r] * ca[c]);
+          for (int m0 = tb.cas_start[i]; m0 < tb.cas_start[i + 1]; ++m0) {
+            const int m = tb.cas_flat[m0];
+            a += ((double)tj[m * 3 + r] - ct[r]) * (((double)rj_term[m * 3 + c] - ca[c]) * (jw ? (double)jw[m] : 1.0));
+          }
+          A[r * 3 + c] = a;
+        }
+      proj_so3_adjoint(A, Rf, Rfb, Abar);
+      double ctb[3], cab[3];
+      centered_cov_centres_adjoint(Abar, ps, ct, ca, ctb, cab);
+      part_cotangent(Abar, ct, ca, pbar + i * kPsum);
+      for (int m0 = tb.cas_start[i]; m0 < tb.cas_start[i + 1]; ++m0) {
+        const int m = tb.cas_flat[m0];
+        const double w = jw ? (double)jw[m] : 1.0;
+        double wb = 0.0;
+        for (int r = 0; r < 3; ++r) {
+          double estb = 0.0, dflb = 0.0;  // Abar dfl, Abar^T est
+          for (int c = 0; c < 3; ++c) {
+            estb += Abar[r * 3 + c] * (((double)rj_term[m * 3 + c] - ca[c]) * w);
+            dflb += Abar[c * 3 + r] * ((double)tj[m * 3 + c] - ct[c]);
+          }
+          tjb[m * 3 + r] += estb;
+          ctb[r] -= estb;
+          rjtb[m * 3 + r] += dflb * w;
+          cab[r] -= dflb * w;
+          wb += dflb * ((double)rj_term[m * 3 + r] - ca[r]);
+        }
+        if (jw) jwb[m] += wb;
+      }
+      for (int c = 0; c < 3; ++c) {
+        posb[i * 3 + c] += ctb[c];
+        rjb[i * 3 + c] += cab[c];
+      }
+    }
+    const int l0 = tb.fk_level_start[lv], nl = tb.fk_level_start[lv + 1] - l0;
+    for (int q = 0; q < nl; ++q) {
+      const int j = tb.fk_js[l0 + q], p = tb.parents[j];
+      for (int r = 0; r < 3; ++r) {
+        const double pb = posb[j * 3 + r];
+        posb[p * 3 + r] += pb;
+        double tb_r = 0.0;
+        for (int c = 0; c < 3; ++c) {
+          Rcb[p * 9 + r * 3 + c] += pb * T[j * 3 + c];
+          tb_r += Rc[p * 9 + c * 3 + r] * posb[j * 3 + c];
+        }
+        auxb[j * 3 + r] += tb_r;
+        auxb[p * 3 + r] -= tb_r;
+      }
+    }
+  }
+  for (int c = 0; c < 3; ++c) {
+    auxb[c] += posb[c];
+    tbar[c] = (float)posb[c];
+  }
+  for (int s = 0; s < S; ++s) {
+    double acc = 0.0;
+    for (int k = 0; k < J * 3; ++k) acc += auxb[k] * (double)tb.j_ext[k * S1 + 1 + s];
+    xbar[s] = (float)acc;
+  }
+  // the rotations the refinement left alone
+  for (int k = 0; k < J * 9; ++k) Gbar[k] += (float)Rcb[k];
+}
+
 #undef SF_FOR
 
 }  // namespace sf

@@ -2208,6 +2208,67 @@ AdjointLayout adjoint_layout(const sf::HostTables& t, int B, Arena& ar) {
   return l;
 }
 
+// LAYOUT adjoint of the fit: one region for the calls it is made of (the shape solve, the forward's backward and the
+// shape solve's adjoint each lay out their own workspace in it, one after the other on the stream), the state of every
+// iteration, and the streams of the reverse sweep
+struct FitBackwardLayout {
+  char* sub;
+  size_t sub_bytes;
+  float *G, *betas, *kid, *trans;           // (num_iter, B, ...) rotations and solution of every iteration
+  float *ctv, *ctj, *rj0, *mesh, *joints, *rjreg;
+  double *psum, *scr;
+  FaJointCot jc;
+  float *acc_tv, *acc_tj, *meshbar, *jointsbar;
+  float *Gbar, *Gbar2, *Gtmp, *xb, *kb, *tb, *xb2, *kb2, *tb2;
+  float *tmp_tv, *tmp_tj, *tmp_vw, *tmp_jw;
+};
+FitBackwardLayout fit_backward_layout(const sf::HostTables& t, int B, int num_iter, Arena& ar) {
+  FitBackwardLayout l;
+  {
+    Arena a{nullptr};
+    adjoint_layout(t, B, a);
+    l.sub_bytes = std::max(a.off, chunked_workspace_bytes(t, B));
+  }
+  l.sub = ar.take<char>(l.sub_bytes);
+  const size_t n = (size_t)std::max(num_iter, 1), BJ = (size_t)B * t.J, BV = (size_t)B * t.V;
+  const size_t nb = (size_t)std::max(1, t.num_betas());
+  l.G = ar.take<float>(n * BJ * 9);
+  l.betas = ar.take<float>(n * B * nb);
+  l.kid = ar.take<float>(n * B);
+  l.trans = ar.take<float>(n * B * 3);
+  l.ctv = ar.take<float>(BV * 3);
+  l.ctj = ar.take<float>(BJ * 3);
+  l.rj0 = ar.take<float>((size_t)t.J * 3);
+  l.mesh = ar.take<float>(BV * 3);
+  l.joints = ar.take<float>(BJ * 3);
+  l.rjreg = ar.take<float>(BJ * 3);
+  l.psum = ar.take<double>(BJ * sf::kPsum);
+  l.scr = ar.take<double>((size_t)B * sf::fit_tail_adjoint_scratch(t.J));
+  l.jc.pbar = ar.take<float>(BJ * sf::kPsum);
+  l.jc.tjbar = ar.take<float>(BJ * 3);
+  l.jc.rjtbar = ar.take<float>(BJ * 3);
+  l.jc.rjbar = ar.take<float>(BJ * 3);
+  l.jc.jwbar = ar.take<float>(BJ);
+  l.acc_tv = ar.take<float>(BV * 3);
+  l.acc_tj = ar.take<float>(BJ * 3);
+  l.meshbar = ar.take<float>(BV * 3);
+  l.jointsbar = ar.take<float>(BJ * 3);
+  l.Gbar = ar.take<float>(BJ * 9);
+  l.Gbar2 = ar.take<float>(BJ * 9);
+  l.Gtmp = ar.take<float>(BJ * 9);
+  l.xb = ar.take<float>(B * nb);
+  l.kb = ar.take<float>((size_t)B);
+  l.tb = ar.take<float>((size_t)B * 3);
+  l.xb2 = ar.take<float>(B * nb);
+  l.kb2 = ar.take<float>((size_t)B);
+  l.tb2 = ar.take<float>((size_t)B * 3);
+  l.tmp_tv = ar.take<float>(BV * 3);
+  l.tmp_tj = ar.take<float>(BJ * 3);
+  l.tmp_vw = ar.take<float>(BV);
+  l.tmp_jw = ar.take<float>(BJ);
+  return l;
+}
+
 // LAYOUT flip: the naively flipped pose (B,3J) the warm start reads, then the chunks of the fused conversion's fit
 struct FlipLayout {
   float* init_pose;
@@ -2956,6 +3017,192 @@ int smplfit_shape_solve_backward_f32(const smplfit_handle* h, const smplfit_shap
     hipLaunchKernelGGL(k_adj_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, aw.g1, aw.g2, aw.g3,
                        a->grad_glob_rotmats, n);
   }
+  return post_launch_check();
+}
+
+size_t smplfit_fit_backward_workspace_bytes(const smplfit_handle* h, int batch, int num_iter) {
+  if (!h || batch <= 0 || num_iter <= 0) return 0;
+  Arena ar{nullptr};
+  fit_backward_layout(h->t, batch, num_iter, ar);
+  return ar.off;
+}
+
+int smplfit_fit_backward_f32(const smplfit_handle* h, const smplfit_fit_backward_args* a) {
+  const char* who = "smplfit_fit_backward_f32";
+  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
+  const int B = a->batch, n = a->num_iter;
+  if (n <= 0) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": num_iter must be positive");
+  if (int rc = check_call(who, h, B, a->workspace, a->workspace_bytes, smplfit_fit_backward_workspace_bytes(h, B, n),
+                          "smplfit_fit_backward_workspace_bytes"))
+    return rc;
+  const DevModel& d = h->d;
+  if (d.S > sf::kAdjMaxUnknowns) return fail(SMPLFIT_ERR_UNSUPPORTED, std::string(who) + ": more than 17 shape unknowns");
+  if (!a->target_vertices) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null pointer");
+  const float *tj = a->target_joints, *vw = a->vertex_weights, *jw = a->joint_weights;
+  const bool joints = tj != nullptr, refine = a->final_adjust_rots != 0, kid = d.jt.n_kid != 0;
+  if (!joints && !h->t.has_regressor)
+    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": target_joints omitted but the model has no J_regressor_post_lbs over its vertices");
+  if (!kid && a->grad_kid_factor) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_kid_factor given to a handle without kid");
+  if (a->grad_target_joints && !joints) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_target_joints without target_joints");
+  if (a->grad_vertex_weights && !vw) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_vertex_weights without vertex_weights");
+  if (a->grad_joint_weights && !jw) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_joint_weights without joint_weights");
+  hipStream_t st = (hipStream_t)a->hip_stream;
+  Arena ar{(char*)a->workspace};
+  FitBackwardLayout l = fit_backward_layout(h->t, B, n, ar);
+  const int J = d.J, V = d.V, nb = h->t.num_betas();
+  const size_t BJ = (size_t)B * J, BV = (size_t)B * V, nbs = (size_t)std::max(1, nb);
+  const unsigned gi = (unsigned)((B + 63) / 64);
+  const auto Gk = [&](int k) { return l.G + (size_t)k * BJ * 9; };
+  const auto bk = [&](int k) { return l.betas + (size_t)k * B * nbs; };
+  const auto kk = [&](int k) { return kid ? l.kid + (size_t)k * B : nullptr; };
+  const auto tk = [&](int k) { return l.trans + (size_t)k * B * 3; };
+  const auto add = [&](float* dst, const float* src, size_t cnt) {
+    hipLaunchKernelGGL(k_fa_add, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, dst, src, cnt);
+  };
+  float *acc_vw = a->grad_vertex_weights, *acc_jw = a->grad_joint_weights;  // (accumulated in place)
+  SF_HIP_TRY(hipMemsetAsync(l.acc_tv, 0, BV * 3 * 4, st));
+  SF_HIP_TRY(hipMemsetAsync(l.acc_tj, 0, BJ * 3 * 4, st));
+  if (acc_vw) SF_HIP_TRY(hipMemsetAsync(acc_vw, 0, BV * 4, st));
+  if (acc_jw) SF_HIP_TRY(hipMemsetAsync(acc_jw, 0, BJ * 4, st));
+  // the shape solve at the rotations of iteration k, in the frame of the centred targets; with the fitted mesh and joints
+  const auto solve = [&](int k, bool mesh) {
+    smplfit_shape_solve_args sa{};
+    sa.glob_rotmats = Gk(k);
+    sa.target_vertices = l.ctv;
+    sa.target_joints = joints ? l.ctj : nullptr;
+    sa.vertex_weights = vw;
+    sa.joint_weights = joints ? jw : nullptr;
+    sa.batch = B;
+    sa.beta_regularizer = a->beta_regularizer;
+    sa.beta_regularizer2 = a->beta_regularizer2;
+    sa.kid_regularizer = a->kid_regularizer;
+    sa.shape_betas = bk(k);
+    sa.trans = tk(k);
+    sa.kid_factor = kk(k);
+    sa.vertices_out = mesh ? l.mesh : nullptr;
+    sa.joints_out = mesh ? l.joints : nullptr;
+    sa.workspace = l.sub;
+    sa.workspace_bytes = l.sub_bytes;
+    sa.hip_stream = a->hip_stream;
+    return smplfit_shape_solve_ex_f32(h, &sa);
+  };
+  // the part sums and the reference joints of a stage against the mesh the last solve left
+  const auto against_mesh = [&]() {
+    if (!joints) hipLaunchKernelGGL(k_fa_regress, dim3(B), dim3(64), 0, st, d, (const float*)l.mesh, l.rjreg);
+    hipLaunchKernelGGL(k_fa_partsums, dim3(B), dim3(256), 0, st, d, (const float*)l.ctv, (const float*)l.mesh, vw, l.psum);
+    return FaJoints{l.ctj, joints ? l.joints : l.rjreg, 0, jw};
+  };
+  const auto against_template = [&]() {
+    hipLaunchKernelGGL(k_fa_partsums, dim3(B), dim3(256), 0, st, d, (const float*)l.ctv, (const float*)nullptr, vw, l.psum);
+    return FaJoints{l.ctj, joints ? d.j_template : l.rj0, 1, jw};
+  };
+  const auto vertex_pass = [&](bool with_mesh) {
+    FaVertexArgs va{l.ctv, with_mesh ? l.mesh : nullptr, vw, joints ? 0 : 1, l.acc_tv, l.acc_tj, acc_vw, acc_jw,
+                    with_mesh ? l.meshbar : nullptr, with_mesh ? l.jointsbar : nullptr};
+    hipLaunchKernelGGL(k_fa_vertex, dim3(B), dim3(256), 0, st, d, va, l.jc);
+  };
+  // ---- forward sweep: the rotations and the solution of every iteration
+  hipLaunchKernelGGL(k_fa_center, dim3(B), dim3(256), 0, st, d, a->target_vertices, tj, l.ctv, l.ctj);
+  if (!joints) {
+    hipLaunchKernelGGL(k_fa_regress, dim3(B), dim3(64), 0, st, d, (const float*)l.ctv, l.ctj);
+    hipLaunchKernelGGL(k_fa_regress, dim3(1), dim3(64), 0, st, d, (const float*)nullptr, l.rj0);
+  }
+  hipLaunchKernelGGL(k_fa_rot_fwd, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, against_template(), (const float*)nullptr, Gk(0), B);
+  for (int k = 0; k < n; ++k) {
+    if (int rc = solve(k, k + 1 < n)) return rc;
+    if (k + 1 < n)
+      hipLaunchKernelGGL(k_fa_rot_fwd, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, against_mesh(), (const float*)Gk(k), Gk(k + 1), B);
+  }
+  // ---- reverse sweep.  Output stage and refinement at the last iteration ...
+  {
+    FaJoints jn{l.ctj, l.ctj, 0, jw};
+    if (refine) {
+      if (int rc = solve(n - 1, true)) return rc;
+      jn = against_mesh();
+    }
+    FaTailArgs ta{Gk(n - 1), bk(n - 1), kk(n - 1), tk(n - 1), l.joints, refine ? 1 : 0, nb, a->grad_pose_rotvecs,
+                  a->grad_orientations, a->grad_relative_orientations, a->grad_shape_betas, kid ? a->grad_kid_factor : nullptr,
+                  a->grad_trans, l.Gbar, l.xb, l.kb, l.tb};
+    hipLaunchKernelGGL(k_fa_tail, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, jn, ta, l.scr, l.jc, B);
+    if (refine) vertex_pass(true);
+  }
+  Arena sub{l.sub};
+  const AdjointLayout al = adjoint_layout(h->t, B, sub);
+  bool mesh_cot = refine;
+  for (int k = n - 1; k >= 0; --k) {
+    // ... the mesh cotangent through the forward at (G_k, x_k, t_k) ...
+    if (mesh_cot) {
+      ForwardInputs in{};
+      in.glob = Gk(k);
+      in.betas = nb ? bk(k) : nullptr;
+      in.kid = kk(k);
+      in.given = nb;
+      Cotangents ct;
+      ct.vertices = l.meshbar;
+      ct.joints = l.jointsbar;
+      GradOutputs out{};
+      out.glob = l.Gtmp;
+      out.betas = nb ? l.xb2 : nullptr;
+      out.trans = l.tb2;
+      out.kid = kid ? l.kb2 : nullptr;
+      if (int rc = launch_forward_backward(h, in, nb, ct, out, al.fb, B, st)) return rc;
+      add(l.Gbar, l.Gtmp, BJ * 9);
+      if (nb) add(l.xb, l.xb2, (size_t)B * nb);
+      if (kid) add(l.kb, l.kb2, (size_t)B);
+      add(l.tb, l.tb2, (size_t)B * 3);
+    }
+    // ... the adjoint of the shape solve: the targets' and weights' gradients and its share of the rotations' ...
+    smplfit_shape_solve_backward_args sb{};
+    sb.glob_rotmats = Gk(k);
+    sb.target_vertices = l.ctv;
+    sb.target_joints = joints ? l.ctj : nullptr;
+    sb.vertex_weights = vw;
+    sb.joint_weights = joints ? jw : nullptr;
+    sb.beta_regularizer = a->beta_regularizer;
+    sb.beta_regularizer2 = a->beta_regularizer2;
+    sb.kid_regularizer = a->kid_regularizer;
+    sb.batch = B;
+    sb.shape_betas = bk(k);
+    sb.trans = tk(k);
+    sb.kid_factor = kk(k);
+    sb.grad_shape_betas = l.xb;
+    sb.grad_trans = l.tb;
+    sb.grad_kid_factor = kid ? l.kb : nullptr;
+    sb.grad_target_vertices = l.tmp_tv;
+    sb.grad_target_joints = joints ? l.tmp_tj : nullptr;
+    sb.grad_vertex_weights = acc_vw ? l.tmp_vw : nullptr;
+    sb.grad_joint_weights = (acc_jw && joints) ? l.tmp_jw : nullptr;
+    sb.grad_glob_rotmats = l.Gtmp;
+    sb.workspace = l.sub;
+    sb.workspace_bytes = l.sub_bytes;
+    sb.hip_stream = a->hip_stream;
+    if (int rc = smplfit_shape_solve_backward_f32(h, &sb)) return rc;
+    add(l.acc_tv, l.tmp_tv, BV * 3);
+    if (joints) add(l.acc_tj, l.tmp_tj, BJ * 3);
+    if (sb.grad_vertex_weights) add(acc_vw, l.tmp_vw, BV);
+    if (sb.grad_joint_weights) add(acc_jw, l.tmp_jw, BJ);
+    add(l.Gbar, l.Gtmp, BJ * 9);
+    // ... and the rotation pass that made G_k: against the template (k = 0), or against the mesh of iteration k - 1
+    if (k == 0) {
+      const FaJoints jn = against_template();
+      hipLaunchKernelGGL(k_fa_rot_adj, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, jn, (const float*)nullptr,
+                         (const float*)l.Gbar, (float*)nullptr, l.scr, l.jc, B);
+      vertex_pass(false);
+    } else {
+      if (int rc = solve(k - 1, true)) return rc;
+      const FaJoints jn = against_mesh();
+      hipLaunchKernelGGL(k_fa_rot_adj, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, jn, (const float*)Gk(k - 1),
+                         (const float*)l.Gbar, l.Gbar2, l.scr, l.jc, B);
+      vertex_pass(true);
+      std::swap(l.Gbar, l.Gbar2);
+      SF_HIP_TRY(hipMemsetAsync(l.xb, 0, (size_t)B * nbs * 4, st));
+      SF_HIP_TRY(hipMemsetAsync(l.kb, 0, (size_t)B * 4, st));
+      SF_HIP_TRY(hipMemsetAsync(l.tb, 0, (size_t)B * 3 * 4, st));
+      mesh_cot = true;
+    }
+  }
+  hipLaunchKernelGGL(k_fa_uncenter, dim3(B), dim3(256), 0, st, d, (const float*)l.acc_tv, joints ? (const float*)l.acc_tj : nullptr,
+                     a->grad_trans, a->grad_target_vertices, a->grad_target_joints);
   return post_launch_check();
 }
 

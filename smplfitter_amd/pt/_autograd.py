@@ -1,9 +1,11 @@
-"""Differentiable fit: the algorithm of ``BodyFitter.fit`` written with PyTorch operators, for inputs that require
-gradients (reference behaviour: ``tests/pt/test_fitter_grad.py:31-99`` — the fit is differentiable with respect to the
-target vertices / joints).  The HIP kernels have no backward pass; ``BodyFitter.fit`` routes a call here ONLY when an
-input requires a gradient and the model lives on a ``cuda`` device.  Everything else — every call without gradients —
-runs the HIP path; this module is never a fallback for it (without gradients the HIP path is hundreds of times faster:
-this is a per-part Python loop over dense tensors, written for clarity and for autograd, not for speed).
+"""The fit written with PyTorch operators: the algorithm of ``BodyFitter.fit`` as differentiable tensor code (reference
+behaviour: ``tests/pt/test_fitter_grad.py:31-99`` — the fit is differentiable with respect to the target vertices /
+joints).  ``BodyFitter.fit`` takes its gradients from the HIP adjoint (``smplfit_fit_backward_f32``) and
+routes a call here ONLY when an input requires a gradient AND the native backward does not serve it: more than 17 shape
+unknowns, or ``BodyFitter(..., native_backward=False)``.  Every call without gradients runs the HIP path; this module is
+never a fallback for it (it is a per-part Python loop over dense tensors, written for clarity and for autograd, hundreds
+of times slower than the kernels).  Run with ``dtype=torch.float64`` on the CPU it is the arbiter of the gradient tests
+(tests/fit_grad_util.py).
 
 The steps follow DESIGN.md / SURVEY.md Appendix B (the same restatement the CPU oracle checks the kernels with):
 centring, part rotations (Kabsch on the multi-joint and leaf parts, swing + twist on the bone parts), the shape solve
@@ -84,9 +86,10 @@ def _centered(raw, st, sa, sw, ct, ca):
 class TorchFit:
     """Tables of ``BodyFitter.__init__`` (pt/bodyfitter.py:25-233) for the torch restatement of one body model."""
 
-    def __init__(self, body_model, enable_kid: bool = False):
+    def __init__(self, body_model, enable_kid: bool = False, dtype: torch.dtype = torch.float32):
         bm = self.bm = body_model
         self.enable_kid = enable_kid
+        self.dtype = dtype  # fp32: the differentiable route of BodyFitter.fit; fp64: the arbiter of the gradient tests
         J, par = bm.num_joints, list(bm.kintree_parents)
         self.J, self.par = J, par
         self.smpl = bm.model_name.startswith('smpl')
@@ -128,7 +131,7 @@ class TorchFit:
 
     def _build_consts(self, device):
         bm = self.bm
-        c = {k: getattr(bm, k).to(device) for k in ('v_template', 'shapedirs', 'posedirs', 'weights', 'J_template',
+        c = {k: getattr(bm, k).to(device=device, dtype=self.dtype) for k in ('v_template', 'shapedirs', 'posedirs', 'weights', 'J_template',
                                                     'J_shapedirs', 'J_regressor_post_lbs', 'kid_shapedir', 'kid_J_shapedir')}
         sd, jsd = c['shapedirs'], c['J_shapedirs']
         if self.enable_kid:  # the kid blend shape is one more shape unknown (:52-58, :1139-1149)
@@ -139,7 +142,7 @@ class TorchFit:
         pw = [0] + self.par[1:]
         c['bone_ext'] = c['J_ext'] - c['J_ext'][pw]
         # default mesh = forward(zero pose, zero shape) (:49)
-        eye = torch.eye(3, device=device).reshape(9)
+        eye = torch.eye(3, device=device, dtype=self.dtype).reshape(9)
         feat = eye.repeat(self.J - 1)
         vp = c['v_template'] + (c['posedirs'].reshape(-1, feat.numel()) @ feat).reshape(-1, 3)
         c['default_mesh'] = vp * c['weights'].sum(1, keepdim=True)
@@ -210,7 +213,7 @@ class TorchFit:
         """Shape + translation from the centred normal equations (pt/bodyfitter.py:840-1102)."""
         B, J, par = tv.shape[0], self.J, self.par
         S = c['sd_all'].shape[2]
-        eye = torch.eye(3, device=tv.device).expand(B, 1, 3, 3)
+        eye = torch.eye(3, device=tv.device, dtype=tv.dtype).expand(B, 1, 3, 3)
         rel = torch.cat([eye, G[:, par[1:]]], 1).transpose(-1, -2) @ G
         P = [None] * J  # FK of the joint positions with their beta-Jacobian (:880-907)
         P[0] = c['J_ext'][0].expand(B, -1, -1)
@@ -303,10 +306,10 @@ class TorchFit:
         """The driver (pt/bodyfitter.py:283-549); returns the reference's result dictionary."""
         dev = target_vertices.device
         c = self._consts(dev)
-        tv = target_vertices.to(torch.float32)
-        tj = None if target_joints is None else target_joints.to(torch.float32)
-        vw = None if vertex_weights is None else vertex_weights.to(torch.float32)
-        jw = None if joint_weights is None else joint_weights.to(torch.float32)
+        tv = target_vertices.to(self.dtype)
+        tj = None if target_joints is None else target_joints.to(self.dtype)
+        vw = None if vertex_weights is None else vertex_weights.to(self.dtype)
+        jw = None if joint_weights is None else joint_weights.to(self.dtype)
         B, J, par = tv.shape[0], self.J, self.par
         if tj is None:  # centring (:355-361)
             mean = tv.mean(1)
@@ -321,7 +324,7 @@ class TorchFit:
         r = self._shape(c, G, tv, tj, vw, jw, beta_regularizer, beta_regularizer2, kid_regularizer)
         if final_adjust_rots:
             G = self._refine(c, tv, tj, r['vertices'], r['joints'], vw, jw, G, r['beta_all'], r['trans'])
-        eye = torch.eye(3, device=dev).expand(B, 1, 3, 3)
+        eye = torch.eye(3, device=dev, dtype=tv.dtype).expand(B, 1, 3, 3)
         rel = torch.cat([eye, G[:, par[1:]]], 1).transpose(-1, -2) @ G
         nb = c['shapedirs'].shape[2]
         out = dict(pose_rotvecs=mat2rotvec(rel).reshape(B, J * 3), shape_betas=r['beta_all'][:, :nb],

@@ -1,6 +1,7 @@
 """``BodyFitter`` — same surface as ``smplfitter.pt.BodyFitter`` (reference
 src/smplfitter/pt/bodyfitter.py:15-549); ``fit`` in its default configuration runs entirely in the HIP
-kernels behind ``smplfit_fit_f32``.  Options the kernels do not implement raise
+kernels behind ``smplfit_fit_f32``, and its gradients with respect to the targets and weights in those behind
+``smplfit_fit_backward_f32``.  Options the kernels do not implement raise
 ``NotImplementedError`` — they never silently compute something else.
 """
 
@@ -52,10 +53,13 @@ class BodyFitter(nn.Module):
         body_model: the :class:`BodyModel` to fit.
         enable_kid: adds the kid blend shape (AGORA) as one more shape unknown
             (reference pt/bodyfitter.py:52-58); results then carry ``kid_factor``.
+        native_backward: the gradients of :meth:`fit` come from the HIP adjoint (``smplfit_fit_backward_f32``);
+            ``False`` keeps the PyTorch restatement (pt/_autograd.py), which also serves more than 17 shape unknowns.
     """
 
-    def __init__(self, body_model: BodyModel, enable_kid: bool = False):
+    def __init__(self, body_model: BodyModel, enable_kid: bool = False, native_backward: bool = True):
         super().__init__()
+        self.native_backward = native_backward
         self.body_model = body_model
         self.n_betas = body_model.shapedirs.shape[2]
         self.enable_kid = enable_kid
@@ -110,15 +114,27 @@ class BodyFitter(nn.Module):
         kid_reg = float(beta_regularizer if kid_regularizer is None else kid_regularizer)
         if torch.is_grad_enabled() and not torch.compiler.is_compiling() and any(
                 t is not None and t.requires_grad for t in (target_vertices, target_joints, vertex_weights, joint_weights)):
-            # gradients with respect to the targets / weights (reference: tests/pt/test_fitter_grad.py): the HIP kernels
-            # have no backward pass, so THIS call — and only a call whose inputs require gradients — runs the algorithm
-            # written with PyTorch operators (pt/_autograd.py) on the model's cuda device
-            result = self._fit_differentiable(
-                target_vertices, target_joints, vertex_weights, joint_weights, num_iter, beta_regularizer,
-                beta_regularizer2, kid_regularizer, final_adjust_rots,
-                unsupported=dict(share_beta=share_beta, scale_target=scale_target, scale_fit=scale_fit,
-                                 initial_pose_rotvecs=initial_pose_rotvecs, initial_shape_betas=initial_shape_betas,
-                                 initial_kid_factor=initial_kid_factor))
+            # gradients with respect to the targets / weights (reference: tests/pt/test_fitter_grad.py): the forward is
+            # the HIP fit under an autograd Function whose backward is one native call (smplfit_fit_backward_f32,
+            # DESIGN.md §17); more than 17 shape unknowns, or native_backward=False, run the algorithm written with
+            # PyTorch operators (pt/_autograd.py) on the model's cuda device instead
+            unsupported = dict(share_beta=share_beta, scale_target=scale_target, scale_fit=scale_fit,
+                               initial_pose_rotvecs=initial_pose_rotvecs, initial_shape_betas=initial_shape_betas,
+                               initial_kid_factor=initial_kid_factor)
+            if self.native_backward and self.n_betas + int(self.enable_kid) <= 17:
+                bad = [k for k, v in unsupported.items() if v is not None and v is not False]
+                if bad:
+                    raise NotImplementedError(f'the differentiable fit does not implement {", ".join(bad)}; detach the inputs to use the HIP path')
+                opts = (int(num_iter), float(beta_regularizer), float(beta_regularizer2), kid_reg, bool(final_adjust_rots))
+                res = _FitFn.apply(self, opts, _workspace, target_vertices, target_joints, vertex_weights, joint_weights)
+                result = dict(pose_rotvecs=res[0], shape_betas=res[1], trans=res[2], orientations=res[3],
+                              relative_orientations=res[4])
+                if self.enable_kid:
+                    result['kid_factor'] = res[5]
+            else:
+                result = self._fit_differentiable(
+                    target_vertices, target_joints, vertex_weights, joint_weights, num_iter, beta_regularizer,
+                    beta_regularizer2, kid_regularizer, final_adjust_rots, unsupported=unsupported)
         elif torch.compiler.is_compiling():  # one opaque operator for torch.compile / export
             pose, betas, trans, kid, orient, rel, scale = torch.ops.smplfitter_amd.fit(
                 self.body_model._model_id, self.enable_kid, target_vertices, target_joints,
@@ -179,7 +195,7 @@ class BodyFitter(nn.Module):
         bm = self.body_model
         device = bm.v_template.device
         for t in (target_vertices, target_joints, vertex_weights, joint_weights):
-            if t is not None and t.requires_grad:
+            if t is not None and t.requires_grad and torch.is_grad_enabled():  # (fit() wraps this call in _FitFn instead)
                 raise NotImplementedError('the HIP fit kernels are not differentiable; detach the inputs')
         J, V, S = bm.num_joints, bm.num_vertices, self.n_betas
         if target_vertices.ndim != 3 or tuple(target_vertices.shape[1:]) != (V, 3):
@@ -243,6 +259,44 @@ class BodyFitter(nn.Module):
             result['scale_corr'] = scale
         return result
 
+    FIT_GRAD_NAMES = ('target_vertices', 'target_joints', 'vertex_weights', 'joint_weights')
+
+    def _fit_backward(self, target_vertices, target_joints, vertex_weights, joint_weights, num_iter, beta_regularizer,
+                      beta_regularizer2, kid_regularizer, final_adjust_rots, grad_pose_rotvecs=None, grad_shape_betas=None,
+                      grad_trans=None, grad_kid_factor=None, grad_orientations=None, grad_relative_orientations=None,
+                      want=FIT_GRAD_NAMES):
+        """The C-ABI call behind ``fit``'s backward (``smplfit_fit_backward_f32``): the gradients named in ``want`` (of
+        ``FIT_GRAD_NAMES``; an input that was not given is skipped) as fp32 tensors on the model's device, from the
+        cotangents of the results (each may be None: zero)."""
+        bm = self.body_model
+        device = bm.v_template.device
+        prep = lambda t: None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        tv, tj, vw, jw = prep(target_vertices), prep(target_joints), prep(vertex_weights), prep(joint_weights)
+        B, J, V, S = tv.shape[0], bm.num_joints, bm.num_vertices, self.n_betas
+        cot = dict(grad_pose_rotvecs=(grad_pose_rotvecs, (B, 3 * J)), grad_shape_betas=(grad_shape_betas, (B, S)),
+                   grad_trans=(grad_trans, (B, 3)), grad_kid_factor=(grad_kid_factor if self.enable_kid else None, (B,)),
+                   grad_orientations=(grad_orientations, (B, J, 3, 3)),
+                   grad_relative_orientations=(grad_relative_orientations, (B, J, 3, 3)))
+        cot = {k: None if t is None else prep(t).reshape(sh) for k, (t, sh) in cot.items()}
+        new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=device)  # noqa: E731
+        given = dict(target_vertices=(tv, (B, V, 3)), target_joints=(tj, (B, J, 3)), vertex_weights=(vw, (B, V)),
+                     joint_weights=(jw, (B, J)))
+        out = {k: new(*given[k][1]) for k in want if given[k][0] is not None}
+        if B == 0:
+            return out
+        h = bm._native(device, kid=self.enable_kid)
+        ws = torch.empty(h.fit_backward_workspace_bytes(B, int(num_iter)), dtype=torch.uint8, device=device)
+        p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            args = _lib.FitBackwardArgs(
+                target_vertices=p(tv), target_joints=p(tj), vertex_weights=p(vw), joint_weights=p(jw), batch=B,
+                num_iter=int(num_iter), beta_regularizer=float(beta_regularizer), beta_regularizer2=float(beta_regularizer2),
+                kid_regularizer=float(kid_regularizer), final_adjust_rots=int(bool(final_adjust_rots)),
+                **{k: p(t) for k, t in cot.items()}, **{f'grad_{k}': p(out.get(k)) for k in self.FIT_GRAD_NAMES},
+                workspace=ws.data_ptr(), workspace_bytes=ws.numel(), hip_stream=stream)
+            _lib.check(_lib.load().smplfit_fit_backward_f32(h.ptr, C.byref(args)))
+        return out
 
     def fit_with_known_pose(
         self,
@@ -516,6 +570,36 @@ class BodyFitter(nn.Module):
                 hip_stream=stream)
             _lib.check(_lib.load().smplfit_shape_solve_backward_f32(h.ptr, C.byref(args)))
         return out
+
+
+class _FitFn(torch.autograd.Function):
+    """``fit`` under autograd: the forward is ``BodyFitter._fit_direct`` (the same call, the same bits as without
+    gradients), the backward one ``smplfit_fit_backward_f32``, which keeps nothing from the forward but its inputs."""
+
+    @staticmethod
+    def forward(ctx, fitter, opts, workspace, tv, tj, vw, jw):
+        num_iter, reg, reg2, kid_reg, final_adjust = opts
+        det = lambda t: None if t is None else t.detach()  # noqa: E731
+        r = fitter._fit_direct(det(tv), det(tj), det(vw), det(jw), num_iter, reg, reg2, kid_reg, final_adjust, None, None,
+                               None, workspace)
+        ctx.fitter, ctx.opts = fitter, opts
+        ctx.save_for_backward(tv, tj, vw, jw)
+        ctx.set_materialize_grads(False)
+        res = (r['pose_rotvecs'], r['shape_betas'], r['trans'], r['orientations'], r['relative_orientations'])
+        return res + ((r['kid_factor'],) if fitter.enable_kid else ())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_pose, g_betas, g_trans, g_orient, g_rel, g_kid=None):
+        ins = ctx.saved_tensors
+        names = BodyFitter.FIT_GRAD_NAMES
+        want = tuple(n for n, t, need in zip(names, ins, ctx.needs_input_grad[3:]) if need and t is not None)
+        g = ctx.fitter._fit_backward(*ins, *ctx.opts, grad_pose_rotvecs=g_pose, grad_shape_betas=g_betas, grad_trans=g_trans,
+                                     grad_kid_factor=g_kid, grad_orientations=g_orient, grad_relative_orientations=g_rel,
+                                     want=want)
+        grads = [None if g.get(n) is None else g[n].reshape(t.shape).to(device=t.device, dtype=t.dtype)
+                 for n, t in zip(names, ins)]
+        return (None, None, None, *grads)
 
 
 class _KnownPoseFn(torch.autograd.Function):
