@@ -485,6 +485,48 @@ int smplfit_fit_known_shape_f32(const smplfit_handle* h, const float* shape_beta
                                 float* scale_corr, float* orientations, float* relative_orientations,
                                 void* workspace, size_t workspace_bytes, void* hip_stream);
 
+/* Adjoint of smplfit_fit_known_shape_f32 without scale_fit and without a warm start (the backward of
+ * BodyFitter.fit_with_known_shape under autograd): the gradients of the shape, the targets and the
+ * weights from the cotangents of the results.  Inputs as smplfit_fit_known_shape_f32 takes them.  Cotangents, each may
+ * be NULL (= zero): grad_pose_rotvecs (B,3J), grad_trans (B,3), grad_orientations, grad_relative_orientations
+ * (B,J,3,3).  Outputs, each may be NULL (= not wanted; its share is not computed): the gradients of target_vertices
+ * (B,V,3), target_joints (B,J,3), vertex_weights (B,V), joint_weights (B,J), shape_betas (B,num_betas_given) and
+ * kid_factor (B).  Nothing is kept from the forward call: a forward sweep recomputes the rotations of every
+ * iteration, a reverse sweep runs the adjoints of the output stage, the refinement, the alignment and the rotation
+ * passes, each mesh's cotangent through the vector-Jacobian product of smplfit_forward_backward_f32.  Any number of
+ * skinning weights and joints; up to 17 shape unknowns (betas + padding + kid: the per-instance refinement adjoint
+ * holds them in registers; more: SMPLFIT_ERR_UNSUPPORTED).  Without target_joints the model needs a joint regressor
+ * over its vertices (SMPLFIT_ERR_BAD_ARG otherwise, as the forward).  An instance whose projection is singular gets
+ * non-finite gradients, the others are not touched.  Stream-ordered, no allocation, no synchronisation;
+ * deterministic: no float atomics.  Workspace: smplfit_fit_known_shape_backward_workspace_bytes(h, batch, num_iter). */
+size_t smplfit_fit_known_shape_backward_workspace_bytes(const smplfit_handle* h, int batch, int num_iter);
+typedef struct smplfit_fit_known_shape_backward_args {
+  const float* shape_betas;                 /* (B,num_betas_given) */
+  int32_t num_betas_given;
+  const float* kid_factor;                  /* (B) or NULL */
+  const float* target_vertices;             /* (B,V,3) */
+  const float* target_joints;               /* (B,J,3) or NULL */
+  const float* vertex_weights;              /* (B,V) or NULL */
+  const float* joint_weights;               /* (B,J) or NULL */
+  int32_t batch;
+  int32_t num_iter;
+  int32_t final_adjust_rots;
+  const float* grad_pose_rotvecs;           /* (B,3J) or NULL */
+  const float* grad_trans;                  /* (B,3) or NULL */
+  const float* grad_orientations;           /* (B,J,3,3) or NULL */
+  const float* grad_relative_orientations;  /* (B,J,3,3) or NULL */
+  float* grad_target_vertices;              /* out (B,V,3) or NULL */
+  float* grad_target_joints;                /* out (B,J,3) or NULL */
+  float* grad_vertex_weights;               /* out (B,V) or NULL */
+  float* grad_joint_weights;                /* out (B,J) or NULL */
+  float* grad_shape_betas;                  /* out (B,num_betas_given) or NULL */
+  float* grad_kid_factor;                   /* out (B) or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  void* hip_stream;
+} smplfit_fit_known_shape_backward_args;
+int smplfit_fit_known_shape_backward_f32(const smplfit_handle* h, const smplfit_fit_known_shape_backward_args* args);
+
 /* Stage entry points for parity tests. */
 
 /* First rotation pass of fit (pt/bodyfitter.py:384-394 -> _fit_global_rotations :1321-1416):

@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     'smplfit_replace_hands_workspace_bytes', 'smplfit_replace_hands_f32',
     'smplfit_shape_solve_backward_workspace_bytes', 'smplfit_shape_solve_backward_f32',
     'smplfit_fit_backward_workspace_bytes', 'smplfit_fit_backward_f32',
+    'smplfit_fit_known_shape_backward_workspace_bytes', 'smplfit_fit_known_shape_backward_f32',
 ]  # fmt: skip
 
 _fp = C.POINTER(C.c_float)
@@ -145,6 +146,20 @@ class FitBackwardArgs(C.Structure):
         ('grad_trans', C.c_void_p), ('grad_kid_factor', C.c_void_p), ('grad_orientations', C.c_void_p),
         ('grad_relative_orientations', C.c_void_p), ('grad_target_vertices', C.c_void_p),
         ('grad_target_joints', C.c_void_p), ('grad_vertex_weights', C.c_void_p), ('grad_joint_weights', C.c_void_p),
+        ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('hip_stream', C.c_void_p),
+    ]
+
+
+class FitKnownShapeBackwardArgs(C.Structure):
+    """smplfit_fit_known_shape_backward_args (include/smplfit.h)."""
+    _fields_ = [
+        ('shape_betas', C.c_void_p), ('num_betas_given', C.c_int32), ('kid_factor', C.c_void_p),
+        ('target_vertices', C.c_void_p), ('target_joints', C.c_void_p), ('vertex_weights', C.c_void_p),
+        ('joint_weights', C.c_void_p), ('batch', C.c_int32), ('num_iter', C.c_int32), ('final_adjust_rots', C.c_int32),
+        ('grad_pose_rotvecs', C.c_void_p), ('grad_trans', C.c_void_p), ('grad_orientations', C.c_void_p),
+        ('grad_relative_orientations', C.c_void_p), ('grad_target_vertices', C.c_void_p),
+        ('grad_target_joints', C.c_void_p), ('grad_vertex_weights', C.c_void_p), ('grad_joint_weights', C.c_void_p),
+        ('grad_shape_betas', C.c_void_p), ('grad_kid_factor', C.c_void_p),
         ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('hip_stream', C.c_void_p),
     ]
 
@@ -353,6 +368,10 @@ def load():
     lib.smplfit_fit_backward_workspace_bytes.restype = sz
     lib.smplfit_fit_backward_f32.argtypes = [vp, C.POINTER(FitBackwardArgs)]
     lib.smplfit_fit_backward_f32.restype = i32
+    lib.smplfit_fit_known_shape_backward_workspace_bytes.argtypes = [vp, i32, i32]
+    lib.smplfit_fit_known_shape_backward_workspace_bytes.restype = sz
+    lib.smplfit_fit_known_shape_backward_f32.argtypes = [vp, C.POINTER(FitKnownShapeBackwardArgs)]
+    lib.smplfit_fit_known_shape_backward_f32.restype = i32
     lib.smplfit_reload_options.argtypes = []
     lib.smplfit_reload_options.restype = i32
     if os.environ.get('SMPLFIT_LIB') and not hasattr(lib, 'smplfit_abi_version'):
@@ -475,6 +494,9 @@ class Handle:
 
     def fit_backward_workspace_bytes(self, batch: int, num_iter: int) -> int:
         return int(load().smplfit_fit_backward_workspace_bytes(self._h, int(batch), int(num_iter)))
+
+    def fit_known_shape_backward_workspace_bytes(self, batch: int, num_iter: int) -> int:
+        return int(load().smplfit_fit_known_shape_backward_workspace_bytes(self._h, int(batch), int(num_iter)))
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h.value:

@@ -257,6 +257,8 @@ __global__ __launch_bounds__(256) void k_adj_combine(const float* __restrict__ g
 //   k_fa_vertex      the part-sum adjoint (a gather) and the regressor's transpose
 //   k_fa_uncenter    the centring step, into the caller's outputs
 //   k_fa_add         dst += src
+//   k_fa_align       the alignment of a known-shape fit (§18): t, and the mesh and joints moved by it
+//   k_fa_align_adj   its adjoint: the complete tbar, then the targets', the mesh's and the weights' share of it
 // ================================================================================================
 __device__ __forceinline__ double fa_wave_sum(double v) {  // fixed tree: the total in every lane's view of lane 0
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -388,7 +390,7 @@ __global__ __launch_bounds__(64) void k_fa_tail(DevModel m, const double* __rest
   if (b >= B) return;
   float x[sf::kAdjMaxUnknowns], xbar[sf::kAdjMaxUnknowns], tbar[3];
   for (int s = 0; s < S; ++s) x[s] = s < a.nb ? a.betas[(size_t)b * a.nb + s] : 0.f;
-  if (m.jt.n_kid) x[S - 1] = a.kid[b];
+  if (m.jt.n_kid) x[S - 1] = a.kid ? a.kid[b] : 0.f;
   double* sc = scr + (size_t)b * sf::fit_tail_adjoint_scratch(J);
   const bool fa = a.final_adjust != 0;
   sf::fit_tail_adjoint(m.jt, a.G + (size_t)b * J * 9, x, a.trans + (size_t)b * 3, psum + (size_t)b * J * sf::kPsum,
@@ -494,4 +496,103 @@ __global__ __launch_bounds__(256) void k_fa_uncenter(DevModel m, const float* __
 __global__ __launch_bounds__(256) void k_fa_add(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (e < n) dst[e] += src[e];
+}
+
+// ---- the alignment stage of a known-shape fit and its adjoint (smplfit_fit_known_shape_backward_f32, DESIGN.md §18) ----
+struct FaAlign {
+  const float *ctv, *ctj;  // the centred targets; ctj null (no target joints): the sums run over the vertices alone
+  const float *vw, *jw;    // the weights that count (solve_weights), or null: every point counts once
+};
+
+// the block's fp64 records summed in a fixed order: red (256, kAlign) -> tot (kAlign)
+__device__ __forceinline__ void fa_align_reduce(const double* s, double* red, double* tot) {
+  const int tid = threadIdx.x;
+  for (int k = 0; k < sf::kAlign; ++k) red[tid * sf::kAlign + k] = s[k];
+  __syncthreads();
+  if (tid < sf::kAlign) {
+    double a = 0.0;
+    for (int k = 0; k < 256; ++k) a += red[k * sf::kAlign + tid];
+    tot[tid] = a;
+  }
+  __syncthreads();
+}
+
+// grid B, block 256.  mesh (B, V, 3), joints (B, J, 3): in the model at the last rotations, out moved by t; trans (B, 3) out.
+__global__ __launch_bounds__(256) void k_fa_align(DevModel m, FaAlign a, float* __restrict__ mesh, float* __restrict__ joints,
+                                                  float* __restrict__ trans) {
+  __shared__ double red[256 * sf::kAlign];
+  __shared__ double tot[sf::kAlign];
+  const int b = blockIdx.x, tid = threadIdx.x, V = m.V, J = m.J;
+  double s[sf::kAlign] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < V; i += 256) {
+    const size_t e = (size_t)b * V + i;
+    sf::align_point_d(a.ctv + e * 3, mesh + e * 3, a.vw ? a.vw[e] : 1.f, s);
+  }
+  if (a.ctj)
+    for (int j = tid; j < J; j += 256) {
+      const size_t e = (size_t)b * J + j;
+      sf::align_point_d(a.ctj + e * 3, joints + e * 3, a.jw ? a.jw[e] : 1.f, s);
+    }
+  fa_align_reduce(s, red, tot);
+  float t[3];
+  sf::align_translation(tot, t);
+  if (tid < 3) trans[(size_t)b * 3 + tid] = t[tid];
+  for (int k = tid; k < V * 3; k += 256) mesh[(size_t)b * V * 3 + k] += t[k % 3];
+  for (int k = tid; k < J * 3; k += 256) joints[(size_t)b * J * 3 + k] += t[k % 3];
+}
+
+struct FaAlignAdj {
+  FaAlign in;
+  const float *mesh, *joints;                // the aligned mesh and joints (k_fa_align's)
+  float *meshbar, *jointsbar;                // in: the cotangents of the aligned mesh / joints; out: of the model's
+  float* tb;                                 // (B, 3) in: the refinement's and the caller's; out: the complete tbar
+  float *acc_tv, *acc_tj, *acc_vw, *acc_jw;  // += ; acc_vw / acc_jw may be null
+};
+
+// grid B, block 256.  tbar += sum meshbar + sum jointsbar (the aligned points carry t), q = tbar / W, then per point
+// (one writer each): target += w q, model -= w q, weight += q . (tau - m).
+__global__ __launch_bounds__(256) void k_fa_align_adj(DevModel m, FaAlignAdj a) {
+  __shared__ double red[256 * sf::kAlign];
+  __shared__ double tot[sf::kAlign];
+  const int b = blockIdx.x, tid = threadIdx.x, V = m.V, J = m.J;
+  double s[sf::kAlign] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = tid; i < V; i += 256) {
+    const size_t e = (size_t)b * V + i;
+    for (int c = 0; c < 3; ++c) s[c] += (double)a.meshbar[e * 3 + c];
+    s[3] += a.in.vw ? (double)a.in.vw[e] : 1.0;
+  }
+  for (int j = tid; j < J; j += 256) {
+    const size_t e = (size_t)b * J + j;
+    for (int c = 0; c < 3; ++c) s[c] += (double)a.jointsbar[e * 3 + c];
+    if (a.in.ctj) s[3] += a.in.jw ? (double)a.in.jw[e] : 1.0;
+  }
+  const float tb_in[3] = {a.tb[(size_t)b * 3], a.tb[(size_t)b * 3 + 1], a.tb[(size_t)b * 3 + 2]};
+  fa_align_reduce(s, red, tot);  // (its barriers lie between every thread's read of tb above and the write below)
+  double q[3];
+  for (int c = 0; c < 3; ++c) {
+    const double tbar = (double)tb_in[c] + tot[c];
+    q[c] = tbar / tot[3];
+    if (tid == c) a.tb[(size_t)b * 3 + c] = (float)tbar;
+  }
+  for (int i = tid; i < V; i += 256) {
+    const size_t e = (size_t)b * V + i;
+    float g[3];
+    const float wb = sf::align_point_adjoint(a.in.ctv + e * 3, a.mesh + e * 3, a.in.vw ? a.in.vw[e] : 1.f, q, g);
+    for (int c = 0; c < 3; ++c) {
+      a.acc_tv[e * 3 + c] += g[c];
+      a.meshbar[e * 3 + c] -= g[c];
+    }
+    if (a.in.vw && a.acc_vw) a.acc_vw[e] += wb;
+  }
+  if (!a.in.ctj) return;
+  for (int j = tid; j < J; j += 256) {
+    const size_t e = (size_t)b * J + j;
+    float g[3];
+    const float wb = sf::align_point_adjoint(a.in.ctj + e * 3, a.joints + e * 3, a.in.jw ? a.in.jw[e] : 1.f, q, g);
+    for (int c = 0; c < 3; ++c) {
+      a.acc_tj[e * 3 + c] += g[c];
+      a.jointsbar[e * 3 + c] -= g[c];
+    }
+    if (a.in.jw && a.acc_jw) a.acc_jw[e] += wb;
+  }
 }

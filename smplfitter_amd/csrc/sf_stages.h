@@ -2278,6 +2278,33 @@ SF_HD void fit_tail_adjoint(const JointTabs& tb, const float* G, const float* x,
   for (int k = 0; k < J * 9; ++k) Gbar[k] += (float)Rcb[k];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Alignment of a known-shape fit without scale (fit_scale_and_translation, bodyfitter.py:1628-1681) and its adjoint
+// (smplfit_fit_known_shape_backward_f32): t = sum_i w_i (tau_i - r_i) / W over the vertices (and, with
+// target joints, the joints), W = sum_i w_i, w_i = 1 where the weights do not count (solve_weights).  The sums are
+// fp64 records [sum w (tau - r) | W]; the point functions are shared by k_fa_align / k_fa_align_adj and the host
+// build of tests/hostemu/hostemu_known_shape_adjoint.cpp.
+// ---------------------------------------------------------------------------------------------
+constexpr int kAlign = 4;
+SF_HD void align_point_d(const float* tau, const float* r, float w, double* acc) {
+  const double wd = (double)w;
+  for (int c = 0; c < 3; ++c) acc[c] += wd * ((double)tau[c] - (double)r[c]);
+  acc[3] += wd;
+}
+SF_HD void align_translation(const double* acc, float* t) {
+  for (int c = 0; c < 3; ++c) t[c] = (float)(acc[c] / acc[3]);
+}
+// q = tbar / W (fp64).  For a point with target tau, aligned reference m = r + t and weight w: g = w q is the
+// cotangent added to tau and taken from r; returned: the weight's, q . ((tau - r) - t) = q . (tau - m).
+SF_HD float align_point_adjoint(const float* tau, const float* m, float w, const double* q, float* g) {
+  double wb = 0.0;
+  for (int c = 0; c < 3; ++c) {
+    g[c] = (float)((double)w * q[c]);
+    wb += q[c] * ((double)tau[c] - (double)m[c]);
+  }
+  return (float)wb;
+}
+
 #undef SF_FOR
 
 }  // namespace sf

@@ -2269,6 +2269,58 @@ FitBackwardLayout fit_backward_layout(const sf::HostTables& t, int B, int num_it
   return l;
 }
 
+// LAYOUT adjoint of the known-shape fit: one region for the calls it is made of (the forward and the forward's
+// backward lay out their own workspace in it, one after the other on the stream), the rotations of every iteration,
+// and the streams of the reverse sweep
+struct KnownShapeBackwardLayout {
+  char* sub;
+  size_t sub_bytes;
+  float *G, *trans;  // (num_iter, B, J, 9) rotations of every iteration; (B, 3) the alignment's translation
+  float *ctv, *ctj, *mesh, *joints, *rjreg;
+  double *psum, *scr;
+  FaJointCot jc;
+  float *acc_tv, *acc_tj, *meshbar, *jointsbar;
+  float *Gbar, *Gbar2, *Gtmp, *xb, *kb, *tb, *xb2, *kb2;
+};
+KnownShapeBackwardLayout known_shape_backward_layout(const sf::HostTables& t, int B, int num_iter, Arena& ar) {
+  KnownShapeBackwardLayout l;
+  {
+    Arena a{nullptr};
+    backward_layout(t, B, a);
+    l.sub_bytes = std::max(a.off, chunked_workspace_bytes(t, B));
+  }
+  l.sub = ar.take<char>(l.sub_bytes);
+  const size_t n = (size_t)std::max(num_iter, 1), BJ = (size_t)B * t.J, BV = (size_t)B * t.V;
+  const size_t nb = (size_t)std::max(1, t.num_betas());
+  l.G = ar.take<float>(n * BJ * 9);
+  l.trans = ar.take<float>((size_t)B * 3);
+  l.ctv = ar.take<float>(BV * 3);
+  l.ctj = ar.take<float>(BJ * 3);
+  l.mesh = ar.take<float>(BV * 3);
+  l.joints = ar.take<float>(BJ * 3);
+  l.rjreg = ar.take<float>(BJ * 3);
+  l.psum = ar.take<double>(BJ * sf::kPsum);
+  l.scr = ar.take<double>((size_t)B * sf::fit_tail_adjoint_scratch(t.J));
+  l.jc.pbar = ar.take<float>(BJ * sf::kPsum);
+  l.jc.tjbar = ar.take<float>(BJ * 3);
+  l.jc.rjtbar = ar.take<float>(BJ * 3);
+  l.jc.rjbar = ar.take<float>(BJ * 3);
+  l.jc.jwbar = ar.take<float>(BJ);
+  l.acc_tv = ar.take<float>(BV * 3);
+  l.acc_tj = ar.take<float>(BJ * 3);
+  l.meshbar = ar.take<float>(BV * 3);
+  l.jointsbar = ar.take<float>(BJ * 3);
+  l.Gbar = ar.take<float>(BJ * 9);
+  l.Gbar2 = ar.take<float>(BJ * 9);
+  l.Gtmp = ar.take<float>(BJ * 9);
+  l.xb = ar.take<float>(B * nb);
+  l.kb = ar.take<float>((size_t)B);
+  l.tb = ar.take<float>((size_t)B * 3);
+  l.xb2 = ar.take<float>(B * nb);
+  l.kb2 = ar.take<float>((size_t)B);
+  return l;
+}
+
 // LAYOUT flip: the naively flipped pose (B,3J) the warm start reads, then the chunks of the fused conversion's fit
 struct FlipLayout {
   float* init_pose;
@@ -3201,6 +3253,153 @@ int smplfit_fit_backward_f32(const smplfit_handle* h, const smplfit_fit_backward
       mesh_cot = true;
     }
   }
+  hipLaunchKernelGGL(k_fa_uncenter, dim3(B), dim3(256), 0, st, d, (const float*)l.acc_tv, joints ? (const float*)l.acc_tj : nullptr,
+                     a->grad_trans, a->grad_target_vertices, a->grad_target_joints);
+  return post_launch_check();
+}
+
+size_t smplfit_fit_known_shape_backward_workspace_bytes(const smplfit_handle* h, int batch, int num_iter) {
+  if (!h || batch <= 0 || num_iter <= 0) return 0;
+  Arena ar{nullptr};
+  known_shape_backward_layout(h->t, batch, num_iter, ar);
+  return ar.off;
+}
+
+int smplfit_fit_known_shape_backward_f32(const smplfit_handle* h, const smplfit_fit_known_shape_backward_args* a) {
+  const char* who = "smplfit_fit_known_shape_backward_f32";
+  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
+  const int B = a->batch, n = a->num_iter;
+  if (n <= 0) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": num_iter must be positive");
+  if (int rc = check_call(who, h, B, a->workspace, a->workspace_bytes, smplfit_fit_known_shape_backward_workspace_bytes(h, B, n),
+                          "smplfit_fit_known_shape_backward_workspace_bytes"))
+    return rc;
+  const DevModel& d = h->d;
+  if (d.S > sf::kAdjMaxUnknowns) return fail(SMPLFIT_ERR_UNSUPPORTED, std::string(who) + ": more than 17 shape unknowns");
+  if (!a->shape_betas || !a->target_vertices) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null pointer");
+  const int nb = a->num_betas_given;
+  if (nb < 0 || nb > h->t.num_betas()) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": more betas than the model holds; slice first");
+  const float *tj = a->target_joints, *vw = a->vertex_weights, *jw = a->joint_weights, *kid = a->kid_factor;
+  const bool joints = tj != nullptr, refine = a->final_adjust_rots != 0;
+  if (!joints && !h->t.has_regressor)
+    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": target_joints omitted but the model has no J_regressor_post_lbs over its vertices");
+  if (kid && !d.jt.n_kid) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": kid_factor given to a handle without kid");
+  if (a->grad_kid_factor && !kid) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_kid_factor without kid_factor");
+  if (a->grad_target_joints && !joints) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_target_joints without target_joints");
+  if (a->grad_vertex_weights && !vw) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_vertex_weights without vertex_weights");
+  if (a->grad_joint_weights && !jw) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_joint_weights without joint_weights");
+  hipStream_t st = (hipStream_t)a->hip_stream;
+  Arena ar{(char*)a->workspace};
+  KnownShapeBackwardLayout l = known_shape_backward_layout(h->t, B, n, ar);
+  const int J = d.J, V = d.V;
+  const size_t BJ = (size_t)B * J, BV = (size_t)B * V;
+  const unsigned gi = (unsigned)((B + 63) / 64);
+  const auto Gk = [&](int k) { return l.G + (size_t)k * BJ * 9; };
+  const auto add = [&](float* dst, const float* src, size_t cnt) {
+    hipLaunchKernelGGL(k_fa_add, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, dst, src, cnt);
+  };
+  float *acc_vw = a->grad_vertex_weights, *acc_jw = a->grad_joint_weights;  // (accumulated in place)
+  const bool shape_grads = (a->grad_shape_betas && nb) || a->grad_kid_factor;
+  SF_HIP_TRY(hipMemsetAsync(l.acc_tv, 0, BV * 3 * 4, st));
+  SF_HIP_TRY(hipMemsetAsync(l.acc_tj, 0, BJ * 3 * 4, st));
+  if (acc_vw) SF_HIP_TRY(hipMemsetAsync(acc_vw, 0, BV * 4, st));
+  if (acc_jw) SF_HIP_TRY(hipMemsetAsync(acc_jw, 0, BJ * 4, st));
+  // the model at the given shape and the rotations `glob` (null: the rest pose), without trans: mesh and joints
+  const auto forward = [&](const float* glob) {
+    smplfit_forward_args fa{};
+    fa.glob_rotmats = glob;
+    fa.shape_betas = a->shape_betas;
+    fa.num_betas_given = nb;
+    fa.kid_factor = kid;
+    fa.batch = B;
+    fa.vertices = l.mesh;
+    fa.joints = l.joints;
+    fa.workspace = l.sub;
+    fa.workspace_bytes = l.sub_bytes;
+    fa.hip_stream = a->hip_stream;
+    return smplfit_forward_ex_f32(h, &fa);
+  };
+  // the part sums and the reference joints of a stage against the mesh the last forward left
+  const auto against_mesh = [&]() {
+    if (!joints) hipLaunchKernelGGL(k_fa_regress, dim3(B), dim3(64), 0, st, d, (const float*)l.mesh, l.rjreg);
+    hipLaunchKernelGGL(k_fa_partsums, dim3(B), dim3(256), 0, st, d, (const float*)l.ctv, (const float*)l.mesh, vw, l.psum);
+    return FaJoints{l.ctj, joints ? l.joints : l.rjreg, 0, jw};
+  };
+  const auto vertex_pass = [&]() {
+    FaVertexArgs va{l.ctv, l.mesh, vw, joints ? 0 : 1, l.acc_tv, l.acc_tj, acc_vw, acc_jw, l.meshbar, l.jointsbar};
+    hipLaunchKernelGGL(k_fa_vertex, dim3(B), dim3(256), 0, st, d, va, l.jc);
+  };
+  // the cotangents of the mesh and its joints through the forward at (glob, betas): Gtmp (with glob), xb += , kb +=
+  Arena sub{l.sub};
+  const BackwardLayout bl = backward_layout(h->t, B, sub);
+  const auto mesh_cotangent = [&](const float* glob) {
+    ForwardInputs in{};
+    in.glob = glob;
+    in.betas = nb ? a->shape_betas : nullptr;
+    in.kid = kid;
+    in.given = nb;
+    Cotangents ct;
+    ct.vertices = l.meshbar;
+    ct.joints = l.jointsbar;
+    GradOutputs out{};
+    out.glob = glob ? l.Gtmp : nullptr;
+    out.betas = (shape_grads && nb) ? l.xb2 : nullptr;
+    out.kid = (shape_grads && kid) ? l.kb2 : nullptr;
+    if (int rc = launch_forward_backward(h, in, nb, ct, out, bl, B, st)) return rc;
+    if (out.betas) add(l.xb, l.xb2, (size_t)B * nb);
+    if (out.kid) add(l.kb, l.kb2, (size_t)B);
+    return 0;
+  };
+  // ---- forward sweep: the rotations of every iteration, then the alignment at the last mesh
+  hipLaunchKernelGGL(k_fa_center, dim3(B), dim3(256), 0, st, d, a->target_vertices, tj, l.ctv, l.ctj);
+  if (!joints) hipLaunchKernelGGL(k_fa_regress, dim3(B), dim3(64), 0, st, d, (const float*)l.ctv, l.ctj);
+  for (int k = 0; k < n; ++k) {
+    if (int rc = forward(k ? Gk(k - 1) : nullptr)) return rc;
+    hipLaunchKernelGGL(k_fa_rot_fwd, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, against_mesh(),
+                       k ? (const float*)Gk(k - 1) : (const float*)nullptr, Gk(k), B);
+  }
+  if (int rc = forward(Gk(n - 1))) return rc;
+  const SolveWeights w = solve_weights(joints, vw, jw);
+  const FaAlign al{l.ctv, joints ? l.ctj : nullptr, w.v ? vw : nullptr, w.j ? jw : nullptr};
+  hipLaunchKernelGGL(k_fa_align, dim3(B), dim3(256), 0, st, d, al, l.mesh, l.joints, l.trans);
+  // ---- reverse sweep.  Output stage and refinement against the aligned mesh ...
+  {
+    FaJoints jn{l.ctj, l.ctj, 0, jw};
+    if (refine) jn = against_mesh();
+    FaTailArgs ta{Gk(n - 1), a->shape_betas, kid, l.trans, l.joints, refine ? 1 : 0, nb, a->grad_pose_rotvecs,
+                  a->grad_orientations, a->grad_relative_orientations, nullptr, nullptr, a->grad_trans, l.Gbar, l.xb, l.kb, l.tb};
+    hipLaunchKernelGGL(k_fa_tail, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, jn, ta, l.scr, l.jc, B);
+    if (refine) {
+      vertex_pass();
+    } else {
+      SF_HIP_TRY(hipMemsetAsync(l.meshbar, 0, BV * 3 * 4, st));
+      SF_HIP_TRY(hipMemsetAsync(l.jointsbar, 0, BJ * 3 * 4, st));
+    }
+  }
+  // ... the alignment: the complete tbar, its share of the targets, the weights and the mesh ...
+  {
+    FaAlignAdj aa{al, l.mesh, l.joints, l.meshbar, l.jointsbar, l.tb, l.acc_tv, l.acc_tj, w.v ? acc_vw : nullptr, w.j ? acc_jw : nullptr};
+    hipLaunchKernelGGL(k_fa_align_adj, dim3(B), dim3(256), 0, st, d, aa);
+  }
+  // ... the whole cotangent of the last mesh through the forward at (G_{n-1}, betas) ...
+  if (int rc = mesh_cotangent(Gk(n - 1))) return rc;
+  add(l.Gbar, l.Gtmp, BJ * 9);
+  // ... and the rotation passes: G_k = Rot(targets, mesh_k) G_{k-1}, mesh_k the forward at G_{k-1} (k = 0: the rest pose)
+  for (int k = n - 1; k >= 0; --k) {
+    if (int rc = forward(k ? Gk(k - 1) : nullptr)) return rc;
+    const FaJoints jn = against_mesh();
+    hipLaunchKernelGGL(k_fa_rot_adj, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, jn,
+                       k ? (const float*)Gk(k - 1) : (const float*)nullptr, (const float*)l.Gbar, k ? l.Gbar2 : (float*)nullptr,
+                       l.scr, l.jc, B);
+    vertex_pass();
+    if (k == 0 && !shape_grads) break;  // (the cotangent of mesh_0 reaches the shape alone)
+    if (int rc = mesh_cotangent(k ? Gk(k - 1) : nullptr)) return rc;
+    if (k) {
+      add(l.Gbar2, l.Gtmp, BJ * 9);
+      std::swap(l.Gbar, l.Gbar2);
+    }
+  }
+  if (a->grad_shape_betas && nb) SF_HIP_TRY(hipMemcpyAsync(a->grad_shape_betas, l.xb, (size_t)B * nb * 4, hipMemcpyDeviceToDevice, st));
+  if (a->grad_kid_factor) SF_HIP_TRY(hipMemcpyAsync(a->grad_kid_factor, l.kb, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(k_fa_uncenter, dim3(B), dim3(256), 0, st, d, (const float*)l.acc_tv, joints ? (const float*)l.acc_tj : nullptr,
                      a->grad_trans, a->grad_target_vertices, a->grad_target_joints);
   return post_launch_check();

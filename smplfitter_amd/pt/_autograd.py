@@ -5,7 +5,8 @@ routes a call here ONLY when an input requires a gradient AND the native backwar
 unknowns, or ``BodyFitter(..., native_backward=False)``.  Every call without gradients runs the HIP path; this module is
 never a fallback for it (it is a per-part Python loop over dense tensors, written for clarity and for autograd, hundreds
 of times slower than the kernels).  Run with ``dtype=torch.float64`` on the CPU it is the arbiter of the gradient tests
-(tests/fit_grad_util.py).
+(tests/fit_grad_util.py).  ``TorchFit.fit_with_known_shape`` is the same for ``BodyFitter.fit_with_known_shape`` (DESIGN.md
+§18): the route of ``native_backward=False`` (in fp64) and the arbiter of tests/known_shape_grad_util.py.
 
 The steps follow DESIGN.md / SURVEY.md Appendix B (the same restatement the CPU oracle checks the kernels with):
 centring, part rotations (Kabsch on the multi-joint and leaf parts, swing + twist on the bone parts), the shape solve
@@ -139,6 +140,10 @@ class TorchFit:
             jsd = torch.cat([jsd, c['kid_J_shapedir'][:, :, None]], 2)
         c['sd_all'] = sd
         c['J_ext'] = torch.cat([c['J_template'][:, :, None], jsd], 2)  # (J, 3, S + 1)
+        # the same pair without / with the kid column: a known-shape fit takes the kid factor per call
+        c['known'] = {False: (c['shapedirs'], torch.cat([c['J_template'][:, :, None], c['J_shapedirs']], 2)),
+                      True: (torch.cat([c['shapedirs'], c['kid_shapedir'][:, :, None]], 2),
+                             torch.cat([c['J_template'][:, :, None], c['J_shapedirs'], c['kid_J_shapedir'][:, :, None]], 2))}
         pw = [0] + self.par[1:]
         c['bone_ext'] = c['J_ext'] - c['J_ext'][pw]
         # default mesh = forward(zero pose, zero shape) (:49)
@@ -332,3 +337,82 @@ class TorchFit:
         if self.enable_kid:
             out['kid_factor'] = r['beta_all'][:, nb]
         return out
+
+    def _forward(self, c, G, beta):
+        """The model at the global rotations ``G`` and the shape unknowns ``beta`` (B, S), without trans: vertices and
+        joints (pt/bodymodel.py:95-228 with ``glob_rotmats``)."""
+        B, J, par = G.shape[0], self.J, self.par
+        eye = torch.eye(3, device=G.device, dtype=G.dtype).expand(B, 1, 3, 3)
+        rel = torch.cat([eye, G[:, par[1:]]], 1).transpose(-1, -2) @ G
+        j = c['J_ext'][None, :, :, 0] + torch.einsum('jcs,bs->bjc', c['J_ext'][:, :, 1:], beta)
+        bones = j - torch.cat([j.new_zeros(B, 1, 3), j[:, par[1:]]], 1)
+        P = [None] * J
+        P[0] = j[:, 0]
+        for lv in self.levels:
+            for i in lv:
+                P[i] = P[par[i]] + torch.einsum('bCc,bc->bC', G[:, par[i]], bones[:, i])
+        P = torch.stack(P, 1)
+        T = P - torch.einsum('bjCc,bjc->bjC', G, j)
+        V = c['v_template'].shape[0]
+        feat = rel[:, 1:].reshape(B, (J - 1) * 9)
+        v_posed = (c['v_template'] + torch.einsum('vcs,bs->bvc', c['sd_all'], beta)
+                   + (feat @ c['posedirs'].reshape(V * 3, -1).T).reshape(B, V, 3))
+        Rb = torch.einsum('vj,bjk->bvk', c['weights'], G.reshape(B, J, 9)).reshape(B, V, 3, 3)
+        Tb = torch.einsum('vj,bjc->bvc', c['weights'], T)
+        return torch.einsum('bvCc,bvc->bvC', Rb, v_posed) + Tb, P
+
+    @staticmethod
+    def _alignment(tv, tj, rv, rj, vw, jw):
+        """``fit_scale_and_translation`` without scale (pt/bodyfitter.py:1628-1681): the weighted mean of the targets
+        minus that of the model, over the vertices and — with target joints — the joints; the weights count when both
+        kinds are given (the vertex weights alone without target joints)."""
+        if tj is None:
+            t, r, w = tv, rv, vw
+        else:
+            t, r = torch.cat([tv, tj], 1), torch.cat([rv, rj], 1)
+            w = torch.cat([vw, jw], 1) if vw is not None and jw is not None else None
+        if w is None:
+            return (t - r).mean(1)
+        w = w / w.sum(1, keepdim=True)
+        return (t * w[..., None]).sum(1) - (r * w[..., None]).sum(1)
+
+    def fit_with_known_shape(self, shape_betas: torch.Tensor, target_vertices: torch.Tensor,
+                             target_joints: Optional[torch.Tensor] = None, vertex_weights: Optional[torch.Tensor] = None,
+                             joint_weights: Optional[torch.Tensor] = None, kid_factor: Optional[torch.Tensor] = None,
+                             num_iter: int = 1, final_adjust_rots: bool = True) -> dict:
+        """``fit_with_known_shape`` without ``scale_fit`` and without a warm start (pt/bodyfitter.py:655-838): the
+        rotation passes against the model at the given shape, the alignment, the refinement."""
+        dev = target_vertices.device
+        c = self._consts(dev)
+        sd, jext = c['known'][kid_factor is not None]
+        c = dict(c, sd_all=sd, J_ext=jext)
+        tv = target_vertices.to(self.dtype)
+        tj = None if target_joints is None else target_joints.to(self.dtype)
+        vw = None if vertex_weights is None else vertex_weights.to(self.dtype)
+        jw = None if joint_weights is None else joint_weights.to(self.dtype)
+        B, J, par = tv.shape[0], self.J, self.par
+        nb = c['shapedirs'].shape[2]
+        beta = shape_betas.to(device=dev, dtype=self.dtype)[:, :nb]
+        if beta.shape[1] < nb:
+            beta = torch.cat([beta, beta.new_zeros(B, nb - beta.shape[1])], 1)
+        if kid_factor is not None:
+            kid = torch.as_tensor(kid_factor, device=dev).to(self.dtype).reshape(-1)
+            beta = torch.cat([beta, kid.expand(B)[:, None]], 1)
+        if tj is None:  # centring (:712-719)
+            mean = tv.mean(1)
+            tv = tv - mean[:, None]
+        else:
+            mean = torch.cat([tv, tj], 1).mean(1)
+            tv, tj = tv - mean[:, None], tj - mean[:, None]
+        G = torch.eye(3, device=dev, dtype=tv.dtype).expand(B, J, 3, 3)
+        for _ in range(num_iter):
+            rv, rj = self._forward(c, G, beta)
+            G = self._rotations(c, tv, tj, rv, rj if tj is not None else None, vw, jw) @ G
+        rv, rj = self._forward(c, G, beta)
+        trans = self._alignment(tv, tj, rv, rj, vw, jw)
+        if final_adjust_rots:
+            G = self._refine(c, tv, tj, rv + trans[:, None], rj + trans[:, None], vw, jw, G, beta, trans)
+        eye = torch.eye(3, device=dev, dtype=tv.dtype).expand(B, 1, 3, 3)
+        rel = torch.cat([eye, G[:, par[1:]]], 1).transpose(-1, -2) @ G
+        return dict(pose_rotvecs=mat2rotvec(rel).reshape(B, J * 3), trans=trans + mean, orientations=G,
+                    relative_orientations=rel)

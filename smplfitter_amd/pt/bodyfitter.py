@@ -64,6 +64,7 @@ class BodyFitter(nn.Module):
         self.n_betas = body_model.shapedirs.shape[2]
         self.enable_kid = enable_kid
         self._torchfit = None  # tables of the differentiable restatement (pt/_autograd.py), built on first use
+        self._torchfit64 = None  # the same in fp64 (fit_with_known_shape's PyTorch route)
         self.is_smpl_family = body_model.model_name.startswith('smpl')
 
     def fit(
@@ -163,8 +164,6 @@ class BodyFitter(nn.Module):
 
     def _fit_differentiable(self, target_vertices, target_joints, vertex_weights, joint_weights, num_iter,
                             beta_regularizer, beta_regularizer2, kid_regularizer, final_adjust_rots, unsupported):
-        from ._autograd import TorchFit
-
         bm = self.body_model
         device = bm.v_template.device
         if device.type != 'cuda':
@@ -172,14 +171,7 @@ class BodyFitter(nn.Module):
         bad = [k for k, v in unsupported.items() if v is not None and v is not False]
         if bad:
             raise NotImplementedError(f'the differentiable fit does not implement {", ".join(bad)}; detach the inputs to use the HIP path')
-        if self._torchfit is None:
-            self._torchfit = TorchFit(bm, enable_kid=self.enable_kid)
-            # said once per fitter: a caller that feeds network outputs in training mode without detach() lands here
-            import warnings
-
-            warnings.warn('smplfitter_amd: inputs of BodyFitter.fit require gradients — this call runs the PyTorch '
-                          'restatement (pt/_autograd.py), hundreds of times slower than the HIP kernels; detach() the '
-                          'inputs or call under torch.no_grad() unless the gradients are wanted', RuntimeWarning, stacklevel=3)
+        self._torchfit_route(stacklevel=4)
         mv = lambda t: None if t is None else t.to(device)  # noqa: E731
         return self._torchfit.fit(mv(target_vertices), mv(target_joints), mv(vertex_weights), mv(joint_weights),
                                   num_iter=int(num_iter), beta_regularizer=float(beta_regularizer),
@@ -394,35 +386,92 @@ class BodyFitter(nn.Module):
         ``scale_corr`` with ``scale_fit``, ``relative_orientations`` / ``pose_rotvecs`` when requested.
 
         The reference's ``scale_fit`` branch only runs for a batch of one (a ``(B,)`` scale is multiplied
-        into ``(B,3)`` means, :1675-1676); here every instance gets the scale a batch-of-one call gives."""
+        into ``(B,3)`` means, :1675-1676); here every instance gets the scale a batch-of-one call gives.
+
+        Differentiable: when gradients are enabled and ``shape_betas``, a target, a weight or a tensor ``kid_factor``
+        requires grad, the results carry a ``grad_fn`` whose backward is one native call
+        (``smplfit_fit_known_shape_backward_f32``); once differentiable; up to 17 shape unknowns
+        natively (more, and ``native_backward=False``: the PyTorch restatement); ``scale_fit`` and
+        ``initial_pose_rotvecs`` with gradients raise ``NotImplementedError``."""
         if requested_keys is None:
             requested_keys = ['pose_rotvecs']
         bm = self.body_model
-        device = bm.v_template.device
         for name, arg in (('target_vertices', target_vertices), ('shape_betas', shape_betas)):
             if isinstance(arg, np.ndarray):
                 raise TypeError(f"Expected torch.Tensor for '{name}', got numpy.ndarray.")
         if target_vertices.ndim != 3:
             raise ValueError(f'Expected batched target_vertices (B, V, 3), got {tuple(target_vertices.shape)}')
-        if any(t is not None and t.requires_grad for t in
-               (shape_betas, target_vertices, target_joints, initial_pose_rotvecs)):
-            raise NotImplementedError('the HIP path is not differentiable')
-        prep = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        if torch.is_grad_enabled() and not torch.compiler.is_compiling() and any(
+                isinstance(t, torch.Tensor) and t.requires_grad for t in
+                (shape_betas, target_vertices, target_joints, vertex_weights, joint_weights, kid_factor, initial_pose_rotvecs)):
+            bad = [k for k, v in dict(scale_fit=scale_fit, initial_pose_rotvecs=initial_pose_rotvecs).items()
+                   if v is not None and v is not False]
+            if bad:
+                raise NotImplementedError(f'the differentiable fit does not implement {", ".join(bad)}; detach the inputs to use the HIP path')
+            n_unknowns = bm.num_betas + int(kid_factor is not None)
+            if self.native_backward and n_unknowns <= 17 and target_vertices.shape[0] > 0:
+                opts = (int(num_iter), bool(final_adjust_rots))
+                pose, trans, orient, rel = _KnownShapeFn.apply(self, opts, shape_betas, kid_factor, target_vertices,
+                                                               target_joints, vertex_weights, joint_weights)
+                out = dict(trans=trans, orientations=orient, relative_orientations=rel, pose_rotvecs=pose)
+            else:
+                # the PyTorch restatement, in fp64: in fp32 it leaves the joint-weight gradient of a known-shape fit (of
+                # order 1e-7 .. 1e-4: the joints of a part agree on its rotation whatever their weights) at rounding noise
+                device = bm.v_template.device
+                mv = lambda t: t.to(device) if isinstance(t, torch.Tensor) else t  # noqa: E731
+                out = self._torchfit_route(dtype=torch.float64).fit_with_known_shape(
+                    mv(shape_betas), mv(target_vertices), mv(target_joints), mv(vertex_weights), mv(joint_weights),
+                    mv(kid_factor), num_iter=int(num_iter), final_adjust_rots=bool(final_adjust_rots))
+                out = {k: v.to(target_vertices.dtype) for k, v in out.items()}
+        else:
+            out = self._fit_known_shape_direct(shape_betas, target_vertices, target_joints, vertex_weights, joint_weights,
+                                               kid_factor, num_iter, final_adjust_rots, initial_pose_rotvecs, scale_fit)
+        if 'relative_orientations' not in requested_keys and 'pose_rotvecs' not in requested_keys:
+            out.pop('relative_orientations')
+        if 'pose_rotvecs' not in requested_keys:
+            out.pop('pose_rotvecs')
+        return out
+
+    def _torchfit_route(self, stacklevel=3, dtype=torch.float32):
+        """The PyTorch restatement of this fitter (pt/_autograd.py) in ``dtype``, built on first use; the first one
+        comes with the warning."""
+        from ._autograd import TorchFit
+
+        if self.body_model.v_template.device.type != 'cuda':
+            raise RuntimeError("smplfitter_amd runs on MI355X only: move the model and the inputs to a 'cuda' (ROCm) device")
+        attr = '_torchfit' if dtype == torch.float32 else '_torchfit64'
+        if getattr(self, attr) is None:
+            first = self._torchfit is None and self._torchfit64 is None
+            setattr(self, attr, TorchFit(self.body_model, enable_kid=self.enable_kid, dtype=dtype))
+            if first:
+                # said once per fitter: a caller that feeds network outputs in training mode without detach() lands here
+                import warnings
+
+                warnings.warn('smplfitter_amd: inputs of BodyFitter.fit require gradients — this call runs the PyTorch '
+                              'restatement (pt/_autograd.py), hundreds of times slower than the HIP kernels; detach() the '
+                              'inputs or call under torch.no_grad() unless the gradients are wanted', RuntimeWarning,
+                              stacklevel=stacklevel)
+        return getattr(self, attr)
+
+    def _fit_known_shape_direct(self, shape_betas, target_vertices, target_joints, vertex_weights, joint_weights,
+                                kid_factor, num_iter, final_adjust_rots, initial_pose_rotvecs, scale_fit):
+        """The C-ABI call of ``fit_with_known_shape`` (``smplfit_fit_known_shape_f32``); every result key."""
+        bm = self.body_model
+        device = bm.v_template.device
+        prep = lambda t: None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
         tv, tj, vw, jw = prep(target_vertices), prep(target_joints), prep(vertex_weights), prep(joint_weights)
         B, J = tv.shape[0], bm.num_joints
         betas = prep(shape_betas)[:, :bm.num_betas].contiguous()
         kid = None
         if kid_factor is not None:
-            kid = torch.as_tensor(kid_factor, dtype=torch.float32, device=device).reshape(-1)
+            kid = torch.as_tensor(kid_factor, dtype=torch.float32, device=device).detach().reshape(-1)
             kid = kid.expand(B).contiguous() if kid.numel() == 1 else kid.contiguous()
         init = None if initial_pose_rotvecs is None else prep(initial_pose_rotvecs.reshape(B, J * 3))
         new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)  # noqa: E731
         pose, trans = new(B, J * 3), new(B, 3)
         orient, rel = new(B, J, 3, 3), new(B, J, 3, 3)
         scale = new(B) if scale_fit else None
-        if B == 0:
-            out = dict(trans=trans, orientations=orient)
-        else:
+        if B > 0:
             h = bm._native(device, kid=kid is not None)
             ws = bm._workspace(h, B, device)
             with torch.cuda.device(device):
@@ -432,13 +481,57 @@ class BodyFitter(nn.Module):
                     _ptr(jw), B, int(num_iter), int(bool(final_adjust_rots)), int(bool(scale_fit)),
                     _ptr(pose), _ptr(trans), _ptr(scale), _ptr(orient), _ptr(rel), _ptr(ws), ws.numel(),
                     C.c_void_p(stream)))
-            out = dict(trans=trans, orientations=orient)
+        out = dict(trans=trans, orientations=orient)
         if scale_fit:
             out['scale_corr'] = scale
-        if 'relative_orientations' in requested_keys or 'pose_rotvecs' in requested_keys:
-            out['relative_orientations'] = rel
-        if 'pose_rotvecs' in requested_keys:
-            out['pose_rotvecs'] = pose
+        out['relative_orientations'] = rel
+        out['pose_rotvecs'] = pose
+        return out
+
+    KNOWN_SHAPE_GRAD_NAMES = ('shape_betas', 'kid_factor', 'target_vertices', 'target_joints', 'vertex_weights',
+                              'joint_weights')
+
+    def _fit_known_shape_backward(self, shape_betas, kid_factor, target_vertices, target_joints, vertex_weights,
+                                  joint_weights, num_iter, final_adjust_rots, grad_pose_rotvecs=None, grad_trans=None,
+                                  grad_orientations=None, grad_relative_orientations=None, want=KNOWN_SHAPE_GRAD_NAMES):
+        """The C-ABI call behind ``fit_with_known_shape``'s backward (``smplfit_fit_known_shape_backward_f32``): the
+        gradients named in ``want`` (of ``KNOWN_SHAPE_GRAD_NAMES``; an input that was not given is skipped) as fp32
+        tensors on the model's device, from the cotangents of the results (each may be None: zero).  ``shape_betas``
+        gets the width of the caller's tensor, zero beyond the model's betas; ``kid_factor`` is (B)."""
+        bm = self.body_model
+        device = bm.v_template.device
+        prep = lambda t: None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        tv, tj, vw, jw = prep(target_vertices), prep(target_joints), prep(vertex_weights), prep(joint_weights)
+        B, J, V = tv.shape[0], bm.num_joints, bm.num_vertices
+        given = prep(shape_betas)
+        betas = given[:, :bm.num_betas].contiguous()
+        kid = None
+        if kid_factor is not None:
+            kid = torch.as_tensor(kid_factor, dtype=torch.float32, device=device).detach().reshape(-1)
+            kid = kid.expand(B).contiguous() if kid.numel() == 1 else kid.contiguous()
+        cot = dict(grad_pose_rotvecs=(grad_pose_rotvecs, (B, 3 * J)), grad_trans=(grad_trans, (B, 3)),
+                   grad_orientations=(grad_orientations, (B, J, 3, 3)),
+                   grad_relative_orientations=(grad_relative_orientations, (B, J, 3, 3)))
+        cot = {k: None if t is None else prep(t).reshape(sh) for k, (t, sh) in cot.items()}
+        new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=device)  # noqa: E731
+        ins = dict(shape_betas=(betas, (B, betas.shape[1])), kid_factor=(kid, (B,)), target_vertices=(tv, (B, V, 3)),
+                   target_joints=(tj, (B, J, 3)), vertex_weights=(vw, (B, V)), joint_weights=(jw, (B, J)))
+        out = {k: new(*ins[k][1]) for k in want if ins[k][0] is not None}
+        if B > 0:
+            h = bm._native(device, kid=kid is not None)
+            ws = torch.empty(h.fit_known_shape_backward_workspace_bytes(B, int(num_iter)), dtype=torch.uint8, device=device)
+            p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()  # noqa: E731
+            with torch.cuda.device(device):
+                stream = torch.cuda.current_stream(device).cuda_stream
+                args = _lib.FitKnownShapeBackwardArgs(
+                    shape_betas=betas.data_ptr(), num_betas_given=betas.shape[1], kid_factor=p(kid), target_vertices=p(tv),
+                    target_joints=p(tj), vertex_weights=p(vw), joint_weights=p(jw), batch=B, num_iter=int(num_iter),
+                    final_adjust_rots=int(bool(final_adjust_rots)), **{k: p(t) for k, t in cot.items()},
+                    **{f'grad_{k}': p(out.get(k)) for k in self.KNOWN_SHAPE_GRAD_NAMES},
+                    workspace=ws.data_ptr(), workspace_bytes=ws.numel(), hip_stream=stream)
+                _lib.check(_lib.load().smplfit_fit_known_shape_backward_f32(h.ptr, C.byref(args)))
+        if 'shape_betas' in out and given.shape[1] > betas.shape[1]:  # columns beyond the model's betas
+            out['shape_betas'] = torch.cat([out['shape_betas'], given.new_zeros(B, given.shape[1] - betas.shape[1])], 1)
         return out
 
     # -- stage entry points, used by the parity tests ---------------------------------------------
@@ -600,6 +693,44 @@ class _FitFn(torch.autograd.Function):
         grads = [None if g.get(n) is None else g[n].reshape(t.shape).to(device=t.device, dtype=t.dtype)
                  for n, t in zip(names, ins)]
         return (None, None, None, *grads)
+
+
+class _KnownShapeFn(torch.autograd.Function):
+    """``fit_with_known_shape`` under autograd: the forward is ``BodyFitter._fit_known_shape_direct`` (the same call, the
+    same bits as without gradients), the backward one ``smplfit_fit_known_shape_backward_f32``, which keeps nothing
+    from the forward but its inputs."""
+
+    @staticmethod
+    def forward(ctx, fitter, opts, betas, kid, tv, tj, vw, jw):
+        num_iter, final_adjust = opts
+        r = fitter._fit_known_shape_direct(betas, tv, tj, vw, jw, kid, num_iter, final_adjust, None, False)
+        ctx.fitter, ctx.opts = fitter, opts
+        ctx.kid_scalar = kid if kid is not None and not isinstance(kid, torch.Tensor) else None
+        ctx.save_for_backward(betas, kid if isinstance(kid, torch.Tensor) else None, tv, tj, vw, jw)
+        ctx.set_materialize_grads(False)
+        return r['pose_rotvecs'], r['trans'], r['orientations'], r['relative_orientations']
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_pose, g_trans, g_orient, g_rel):
+        ins = list(ctx.saved_tensors)
+        names = BodyFitter.KNOWN_SHAPE_GRAD_NAMES
+        want = tuple(n for n, t, need in zip(names, ins, ctx.needs_input_grad[2:]) if need and t is not None)
+        call = list(ins)
+        if call[1] is None:
+            call[1] = ctx.kid_scalar
+        g = ctx.fitter._fit_known_shape_backward(*call, *ctx.opts, grad_pose_rotvecs=g_pose, grad_trans=g_trans,
+                                                 grad_orientations=g_orient, grad_relative_orientations=g_rel, want=want)
+        grads = []
+        for n, t in zip(names, ins):
+            v = g.get(n) if n in want else None
+            if v is None:
+                grads.append(None)
+                continue
+            if n == 'kid_factor' and t.numel() == 1 and v.numel() != 1:  # a broadcast kid factor
+                v = v.sum()
+            grads.append(v.reshape(t.shape).to(device=t.device, dtype=t.dtype))
+        return (None, None, *grads)
 
 
 class _KnownPoseFn(torch.autograd.Function):
