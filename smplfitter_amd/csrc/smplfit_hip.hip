@@ -1368,7 +1368,10 @@ int post_launch_check() {
 //   launch_normal_equations   GEMM, joint-row transpose, the vertex block of one shape solve
 //   launch_alignment          scale and translation of a known-shape fit
 //   launch_forward_backward   the forward's vector-Jacobian product (below, behind the layouts it runs in)
-// and the rules that fill their arguments: solve_weights, set_joint_block, refine_args.
+//   RotationSweep             what the adjoints of both differentiable fits share: centring, part sums, rotation passes and
+//                             their adjoints, output stage, vertex pass, mesh cotangent (below, behind its layout)
+// and the rules that fill their arguments: solve_weights, set_joint_block, refine_args; in the sweep against_mesh /
+// against_template (the reference joints of a stage) and rot_adjoint (which of Gbar / Gbar2 is current).
 // ------------------------------------------------------------------------------------------------
 
 // Which weights enter the shape solve and the alignment: both kinds only if both are given (with target joints), the
@@ -2208,37 +2211,28 @@ AdjointLayout adjoint_layout(const sf::HostTables& t, int B, Arena& ar) {
   return l;
 }
 
-// LAYOUT adjoint of the fit: one region for the calls it is made of (the shape solve, the forward's backward and the
-// shape solve's adjoint each lay out their own workspace in it, one after the other on the stream), the state of every
-// iteration, and the streams of the reverse sweep
-struct FitBackwardLayout {
+// LAYOUT rotation sweep: what the adjoints of both differentiable fits share.  One region for the calls
+// they are made of (each lays out its own workspace in it, one after the other on the stream; sub_bytes: the largest
+// of them, the caller's), the rotations of every iteration, and the streams of the reverse sweep
+struct SweepLayout {
   char* sub;
   size_t sub_bytes;
-  float *G, *betas, *kid, *trans;           // (num_iter, B, ...) rotations and solution of every iteration
-  float *ctv, *ctj, *rj0, *mesh, *joints, *rjreg;
+  float* G;  // (num_iter, B, J, 9) rotations of every iteration
+  float *ctv, *ctj, *mesh, *joints, *rjreg;
   double *psum, *scr;
   FaJointCot jc;
   float *acc_tv, *acc_tj, *meshbar, *jointsbar;
-  float *Gbar, *Gbar2, *Gtmp, *xb, *kb, *tb, *xb2, *kb2, *tb2;
-  float *tmp_tv, *tmp_tj, *tmp_vw, *tmp_jw;
+  float *Gbar, *Gbar2, *Gtmp, *xb, *kb, *tb, *xb2, *kb2;
 };
-FitBackwardLayout fit_backward_layout(const sf::HostTables& t, int B, int num_iter, Arena& ar) {
-  FitBackwardLayout l;
-  {
-    Arena a{nullptr};
-    adjoint_layout(t, B, a);
-    l.sub_bytes = std::max(a.off, chunked_workspace_bytes(t, B));
-  }
-  l.sub = ar.take<char>(l.sub_bytes);
+SweepLayout sweep_layout(const sf::HostTables& t, int B, int num_iter, size_t sub_bytes, Arena& ar) {
+  SweepLayout l;
+  l.sub_bytes = sub_bytes;
+  l.sub = ar.take<char>(sub_bytes);
   const size_t n = (size_t)std::max(num_iter, 1), BJ = (size_t)B * t.J, BV = (size_t)B * t.V;
   const size_t nb = (size_t)std::max(1, t.num_betas());
   l.G = ar.take<float>(n * BJ * 9);
-  l.betas = ar.take<float>(n * B * nb);
-  l.kid = ar.take<float>(n * B);
-  l.trans = ar.take<float>(n * B * 3);
   l.ctv = ar.take<float>(BV * 3);
   l.ctj = ar.take<float>(BJ * 3);
-  l.rj0 = ar.take<float>((size_t)t.J * 3);
   l.mesh = ar.take<float>(BV * 3);
   l.joints = ar.take<float>(BJ * 3);
   l.rjreg = ar.take<float>(BJ * 3);
@@ -2261,6 +2255,28 @@ FitBackwardLayout fit_backward_layout(const sf::HostTables& t, int B, int num_it
   l.tb = ar.take<float>((size_t)B * 3);
   l.xb2 = ar.take<float>(B * nb);
   l.kb2 = ar.take<float>((size_t)B);
+  return l;
+}
+
+// LAYOUT adjoint of the fit: the sweep's (in its region: the shape solve, the forward's backward and the shape solve's
+// adjoint), then the solution of every iteration, the template's regressed joints, the second translation cotangent
+// and the shape-solve adjoint's target and weight gradients
+struct FitBackwardLayout {
+  SweepLayout sw;
+  float *betas, *kid, *trans;  // (num_iter, B, ...) solution of every iteration
+  float *rj0, *tb2;
+  float *tmp_tv, *tmp_tj, *tmp_vw, *tmp_jw;
+};
+FitBackwardLayout fit_backward_layout(const sf::HostTables& t, int B, int num_iter, Arena& ar) {
+  FitBackwardLayout l;
+  Arena sub{nullptr};
+  adjoint_layout(t, B, sub);
+  l.sw = sweep_layout(t, B, num_iter, std::max(sub.off, chunked_workspace_bytes(t, B)), ar);
+  const size_t n = (size_t)std::max(num_iter, 1), BJ = (size_t)B * t.J, BV = (size_t)B * t.V;
+  l.betas = ar.take<float>(n * B * std::max(1, t.num_betas()));
+  l.kid = ar.take<float>(n * B);
+  l.trans = ar.take<float>(n * B * 3);
+  l.rj0 = ar.take<float>((size_t)t.J * 3);
   l.tb2 = ar.take<float>((size_t)B * 3);
   l.tmp_tv = ar.take<float>(BV * 3);
   l.tmp_tj = ar.take<float>(BJ * 3);
@@ -2269,55 +2285,18 @@ FitBackwardLayout fit_backward_layout(const sf::HostTables& t, int B, int num_it
   return l;
 }
 
-// LAYOUT adjoint of the known-shape fit: one region for the calls it is made of (the forward and the forward's
-// backward lay out their own workspace in it, one after the other on the stream), the rotations of every iteration,
-// and the streams of the reverse sweep
+// LAYOUT adjoint of the known-shape fit: the sweep's (in its region: the forward and the forward's backward), then the
+// alignment's translation
 struct KnownShapeBackwardLayout {
-  char* sub;
-  size_t sub_bytes;
-  float *G, *trans;  // (num_iter, B, J, 9) rotations of every iteration; (B, 3) the alignment's translation
-  float *ctv, *ctj, *mesh, *joints, *rjreg;
-  double *psum, *scr;
-  FaJointCot jc;
-  float *acc_tv, *acc_tj, *meshbar, *jointsbar;
-  float *Gbar, *Gbar2, *Gtmp, *xb, *kb, *tb, *xb2, *kb2;
+  SweepLayout sw;
+  float* trans;  // (B, 3)
 };
 KnownShapeBackwardLayout known_shape_backward_layout(const sf::HostTables& t, int B, int num_iter, Arena& ar) {
   KnownShapeBackwardLayout l;
-  {
-    Arena a{nullptr};
-    backward_layout(t, B, a);
-    l.sub_bytes = std::max(a.off, chunked_workspace_bytes(t, B));
-  }
-  l.sub = ar.take<char>(l.sub_bytes);
-  const size_t n = (size_t)std::max(num_iter, 1), BJ = (size_t)B * t.J, BV = (size_t)B * t.V;
-  const size_t nb = (size_t)std::max(1, t.num_betas());
-  l.G = ar.take<float>(n * BJ * 9);
+  Arena sub{nullptr};
+  backward_layout(t, B, sub);
+  l.sw = sweep_layout(t, B, num_iter, std::max(sub.off, chunked_workspace_bytes(t, B)), ar);
   l.trans = ar.take<float>((size_t)B * 3);
-  l.ctv = ar.take<float>(BV * 3);
-  l.ctj = ar.take<float>(BJ * 3);
-  l.mesh = ar.take<float>(BV * 3);
-  l.joints = ar.take<float>(BJ * 3);
-  l.rjreg = ar.take<float>(BJ * 3);
-  l.psum = ar.take<double>(BJ * sf::kPsum);
-  l.scr = ar.take<double>((size_t)B * sf::fit_tail_adjoint_scratch(t.J));
-  l.jc.pbar = ar.take<float>(BJ * sf::kPsum);
-  l.jc.tjbar = ar.take<float>(BJ * 3);
-  l.jc.rjtbar = ar.take<float>(BJ * 3);
-  l.jc.rjbar = ar.take<float>(BJ * 3);
-  l.jc.jwbar = ar.take<float>(BJ);
-  l.acc_tv = ar.take<float>(BV * 3);
-  l.acc_tj = ar.take<float>(BJ * 3);
-  l.meshbar = ar.take<float>(BV * 3);
-  l.jointsbar = ar.take<float>(BJ * 3);
-  l.Gbar = ar.take<float>(BJ * 9);
-  l.Gbar2 = ar.take<float>(BJ * 9);
-  l.Gtmp = ar.take<float>(BJ * 9);
-  l.xb = ar.take<float>(B * nb);
-  l.kb = ar.take<float>((size_t)B);
-  l.tb = ar.take<float>((size_t)B * 3);
-  l.xb2 = ar.take<float>(B * nb);
-  l.kb2 = ar.take<float>((size_t)B);
   return l;
 }
 
@@ -2448,6 +2427,294 @@ int objective_impl(const char* who, const smplfit_handle* h, const A& a, const J
     ct.obj_joints = &oj;
   }
   if (int rc = launch_forward_backward(h, in, backward_nb(in), ct, grad_outputs(a), l.fb, B, (hipStream_t)a.hip_stream)) return rc;
+  return post_launch_check();
+}
+
+// STEP rotation sweep, in a laid-out SweepLayout.  tj / vw / jw: the call's target joints and weights, each
+// may be null; acc_vw / acc_jw: the caller's weight-gradient outputs or null, accumulated in place.
+struct OutputCotangents {
+  const float *pose, *orient, *rel, *betas, *kid, *trans;  // the caller's, each may be null
+};
+struct RotationSweep {
+  const smplfit_handle* h;
+  SweepLayout l;
+  hipStream_t st;
+  int B;
+  const float *tj, *vw, *jw;
+  float *acc_vw, *acc_jw;
+
+  bool joints() const { return tj != nullptr; }
+  size_t BJ() const { return (size_t)B * h->d.J; }
+  size_t BV() const { return (size_t)B * h->d.V; }
+  dim3 lanes() const { return dim3((unsigned)((B + 63) / 64)); }  // the joint-level kernels: one lane per instance
+  float* Gk(int k) const { return l.G + (size_t)k * BJ() * 9; }
+  void add(float* dst, const float* src, size_t cnt) const {
+    hipLaunchKernelGGL(k_fa_add, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, dst, src, cnt);
+  }
+  // the joints regressed from `rows` meshes (null: the template)
+  void regress(int rows, const float* verts, float* out) const {
+    hipLaunchKernelGGL(k_fa_regress, dim3(rows), dim3(64), 0, st, h->d, verts, out);
+  }
+  // the four accumulators zeroed and the targets centred; without target joints they are regressed from the centred
+  // vertices, and — rj0 given — the template's once, for against_template
+  int begin(const float* tv, float* rj0) const {
+    SF_HIP_TRY(hipMemsetAsync(l.acc_tv, 0, BV() * 3 * 4, st));
+    SF_HIP_TRY(hipMemsetAsync(l.acc_tj, 0, BJ() * 3 * 4, st));
+    if (acc_vw) SF_HIP_TRY(hipMemsetAsync(acc_vw, 0, BV() * 4, st));
+    if (acc_jw) SF_HIP_TRY(hipMemsetAsync(acc_jw, 0, BJ() * 4, st));
+    hipLaunchKernelGGL(k_fa_center, dim3(B), dim3(256), 0, st, h->d, tv, tj, l.ctv, l.ctj);
+    if (!joints()) regress(B, l.ctv, l.ctj);
+    if (!joints() && rj0) regress(1, nullptr, rj0);
+    return 0;
+  }
+  // the fp64 part sums of a stage and its reference joints (regressed without target joints): against l.mesh / l.joints, or
+  // against the template (rj0: its regressed joints)
+  FaJoints part_sums(const float* mesh, const FaJoints& jn) const {
+    hipLaunchKernelGGL(k_fa_partsums, dim3(B), dim3(256), 0, st, h->d, (const float*)l.ctv, mesh, vw, l.psum);
+    return jn;
+  }
+  FaJoints against_mesh() const {
+    if (!joints()) regress(B, l.mesh, l.rjreg);
+    return part_sums(l.mesh, {l.ctj, joints() ? l.joints : l.rjreg, 0, jw});
+  }
+  FaJoints against_template(const float* rj0) const { return part_sums(nullptr, {l.ctj, joints() ? h->d.j_template : rj0, 1, jw}); }
+  // the part-sum adjoint of the records the last joint-level adjoint left; with_mesh: the stage ran against l.mesh, whose
+  // cotangent and its joints' go to meshbar / jointsbar
+  void vertex_pass(bool with_mesh) const {
+    FaVertexArgs va{l.ctv, with_mesh ? l.mesh : nullptr, vw, joints() ? 0 : 1, l.acc_tv, l.acc_tj, acc_vw, acc_jw,
+                    with_mesh ? l.meshbar : nullptr, with_mesh ? l.jointsbar : nullptr};
+    hipLaunchKernelGGL(k_fa_vertex, dim3(B), dim3(256), 0, st, h->d, va, l.jc);
+  }
+  // G_k = Rot(stage) G_{k-1} (k = 0: the first pass), and its adjoint: Gbar in; k > 0: G_{k-1}'s written to Gbar2, and the
+  // two trade places — Gbar is the cotangent of the rotations the reverse sweep stands at
+  void rot_forward(int k, const FaJoints& jn) const {
+    hipLaunchKernelGGL(k_fa_rot_fwd, lanes(), dim3(64), 0, st, h->d, (const double*)l.psum, jn,
+                       k ? (const float*)Gk(k - 1) : (const float*)nullptr, Gk(k), B);
+  }
+  void rot_adjoint(int k, const FaJoints& jn) {
+    hipLaunchKernelGGL(k_fa_rot_adj, lanes(), dim3(64), 0, st, h->d, (const double*)l.psum, jn,
+                       k ? (const float*)Gk(k - 1) : (const float*)nullptr, (const float*)l.Gbar, k ? l.Gbar2 : (float*)nullptr, l.scr, l.jc, B);
+    if (k) std::swap(l.Gbar, l.Gbar2);
+  }
+  // output stage and — refine — refinement at (G_k, betas, kid, trans) against l.mesh / l.joints: Gbar, xb, kb, tb written
+  void tail(int k, bool refine, int nb, const float* betas, const float* kid, const float* trans, const OutputCotangents& g) const {
+    const FaJoints jn = refine ? against_mesh() : FaJoints{l.ctj, l.ctj, 0, jw};
+    FaTailArgs ta{Gk(k), betas, kid, trans, l.joints, refine ? 1 : 0, nb, g.pose, g.orient, g.rel, g.betas, g.kid, g.trans,
+                  l.Gbar, l.xb, l.kb, l.tb};
+    hipLaunchKernelGGL(k_fa_tail, lanes(), dim3(64), 0, st, h->d, (const double*)l.psum, jn, ta, l.scr, l.jc, B);
+    if (refine) vertex_pass(true);
+  }
+  // meshbar / jointsbar through the forward at (glob or the rest pose, betas, kid) in a laid-out BackwardLayout.  out: the
+  // products wanted (Gtmp, xb2, kb2, a second tb of the caller's) or null; each is added to Gbar / xb / kb / tb, the
+  // rotations' in front of the others (glob_first) or behind them
+  int mesh_cotangent(const float* glob, const float* betas, const float* kid, int nb, const GradOutputs& out, bool glob_first,
+                     const BackwardLayout& bl) const {
+    const ForwardInputs in{nullptr, glob, nullptr, nb ? betas : nullptr, kid, nb};
+    Cotangents ct;
+    ct.vertices = l.meshbar;
+    ct.joints = l.jointsbar;
+    if (int rc = launch_forward_backward(h, in, nb, ct, out, bl, B, st)) return rc;
+    if (out.glob && glob_first) add(l.Gbar, out.glob, BJ() * 9);
+    if (out.betas) add(l.xb, out.betas, (size_t)B * nb);
+    if (out.kid) add(l.kb, out.kid, (size_t)B);
+    if (out.trans) add(l.tb, out.trans, (size_t)B * 3);
+    if (out.glob && !glob_first) add(l.Gbar, out.glob, BJ() * 9);
+    return 0;
+  }
+  // the accumulated target cotangents back through the centring, into the caller's outputs
+  void finish(const float* g_trans, float* g_tv, float* g_tj) const {
+    hipLaunchKernelGGL(k_fa_uncenter, dim3(B), dim3(256), 0, st, h->d, (const float*)l.acc_tv,
+                       joints() ? (const float*)l.acc_tj : nullptr, g_trans, g_tv, g_tj);
+  }
+};
+
+// What smplfit_fit_backward_f32 and smplfit_fit_known_shape_backward_f32 both refuse (behind check_call)
+int check_sweep_call(const char* who, const smplfit_handle* h, int num_iter, const float* tj, const float* vw, const float* jw,
+                     const float* grad_tj, const float* grad_vw, const float* grad_jw) {
+  const auto bad = [who](int code, const char* what) { return fail(code, std::string(who) + ": " + what); };
+  if (num_iter <= 0) return bad(SMPLFIT_ERR_BAD_ARG, "num_iter must be positive");
+  if (h->d.S > sf::kAdjMaxUnknowns) return bad(SMPLFIT_ERR_UNSUPPORTED, "more than 17 shape unknowns");
+  if (!tj && !h->t.has_regressor)
+    return bad(SMPLFIT_ERR_BAD_ARG, "target_joints omitted but the model has no J_regressor_post_lbs over its vertices");
+  if (grad_tj && !tj) return bad(SMPLFIT_ERR_BAD_ARG, "grad_target_joints without target_joints");
+  if (grad_vw && !vw) return bad(SMPLFIT_ERR_BAD_ARG, "grad_vertex_weights without vertex_weights");
+  if (grad_jw && !jw) return bad(SMPLFIT_ERR_BAD_ARG, "grad_joint_weights without joint_weights");
+  return 0;
+}
+
+// The adjoint of the fit: the sweep's steps around the shape solve of every iteration and its adjoint
+int run_fit_backward(const smplfit_handle* h, const smplfit_fit_backward_args& a) {
+  const DevModel& d = h->d;
+  const int B = a.batch, n = a.num_iter, nb = h->t.num_betas();
+  const float *tj = a.target_joints, *vw = a.vertex_weights, *jw = a.joint_weights;
+  const bool joints = tj != nullptr, refine = a.final_adjust_rots != 0, kid = d.jt.n_kid != 0;
+  hipStream_t st = (hipStream_t)a.hip_stream;
+  Arena ar{(char*)a.workspace};
+  const FitBackwardLayout l = fit_backward_layout(h->t, B, n, ar);
+  RotationSweep sw{h, l.sw, st, B, tj, vw, jw, a.grad_vertex_weights, a.grad_joint_weights};
+  const size_t BJ = sw.BJ(), BV = sw.BV(), nbs = (size_t)std::max(1, nb);
+  const auto bk = [&](int k) { return l.betas + (size_t)k * B * nbs; };
+  const auto kk = [&](int k) { return kid ? l.kid + (size_t)k * B : nullptr; };
+  const auto tk = [&](int k) { return l.trans + (size_t)k * B * 3; };
+  // the shape solve at the rotations of iteration k in the frame of the centred targets, as the solve (with the fitted mesh
+  // and joints) and its adjoint name it
+  const auto at_iteration = [&](auto& s, int k) {
+    s.glob_rotmats = sw.Gk(k);
+    s.target_vertices = sw.l.ctv;
+    s.target_joints = joints ? sw.l.ctj : nullptr;
+    s.vertex_weights = vw;
+    s.joint_weights = joints ? jw : nullptr;
+    s.batch = B;
+    s.beta_regularizer = a.beta_regularizer;
+    s.beta_regularizer2 = a.beta_regularizer2;
+    s.kid_regularizer = a.kid_regularizer;
+    s.shape_betas = bk(k);
+    s.trans = tk(k);
+    s.kid_factor = kk(k);
+    s.workspace = sw.l.sub;
+    s.workspace_bytes = sw.l.sub_bytes;
+    s.hip_stream = a.hip_stream;
+  };
+  const auto solve = [&](int k, bool mesh) {
+    smplfit_shape_solve_args sa{};
+    at_iteration(sa, k);
+    sa.vertices_out = mesh ? sw.l.mesh : nullptr;
+    sa.joints_out = mesh ? sw.l.joints : nullptr;
+    return smplfit_shape_solve_ex_f32(h, &sa);
+  };
+  // ---- forward sweep: the rotations and the solution of every iteration
+  if (int rc = sw.begin(a.target_vertices, l.rj0)) return rc;
+  sw.rot_forward(0, sw.against_template(l.rj0));
+  for (int k = 0; k < n; ++k) {
+    if (int rc = solve(k, k + 1 < n)) return rc;
+    if (k + 1 < n) sw.rot_forward(k + 1, sw.against_mesh());
+  }
+  // ---- reverse sweep.  Output stage and refinement at the last iteration ...
+  if (refine)
+    if (int rc = solve(n - 1, true)) return rc;
+  sw.tail(n - 1, refine, nb, bk(n - 1), kk(n - 1), tk(n - 1),
+          {a.grad_pose_rotvecs, a.grad_orientations, a.grad_relative_orientations, a.grad_shape_betas,
+           kid ? a.grad_kid_factor : nullptr, a.grad_trans});
+  Arena sub{sw.l.sub};
+  const AdjointLayout al = adjoint_layout(h->t, B, sub);
+  bool mesh_cot = refine;
+  for (int k = n - 1; k >= 0; --k) {
+    // ... the mesh cotangent through the forward at (G_k, x_k, t_k) ...
+    if (mesh_cot) {
+      GradOutputs out{};
+      out.glob = sw.l.Gtmp;
+      out.betas = nb ? sw.l.xb2 : nullptr;
+      out.trans = l.tb2;
+      out.kid = kid ? sw.l.kb2 : nullptr;
+      if (int rc = sw.mesh_cotangent(sw.Gk(k), bk(k), kk(k), nb, out, true, al.fb)) return rc;
+    }
+    // ... the adjoint of the shape solve: the targets' and weights' gradients and its share of the rotations' ...
+    smplfit_shape_solve_backward_args sb{};
+    at_iteration(sb, k);
+    sb.grad_shape_betas = sw.l.xb;
+    sb.grad_trans = sw.l.tb;
+    sb.grad_kid_factor = kid ? sw.l.kb : nullptr;
+    sb.grad_target_vertices = l.tmp_tv;
+    sb.grad_target_joints = joints ? l.tmp_tj : nullptr;
+    sb.grad_vertex_weights = sw.acc_vw ? l.tmp_vw : nullptr;
+    sb.grad_joint_weights = (sw.acc_jw && joints) ? l.tmp_jw : nullptr;
+    sb.grad_glob_rotmats = sw.l.Gtmp;
+    if (int rc = smplfit_shape_solve_backward_f32(h, &sb)) return rc;
+    sw.add(sw.l.acc_tv, l.tmp_tv, BV * 3);
+    if (joints) sw.add(sw.l.acc_tj, l.tmp_tj, BJ * 3);
+    if (sb.grad_vertex_weights) sw.add(sw.acc_vw, l.tmp_vw, BV);
+    if (sb.grad_joint_weights) sw.add(sw.acc_jw, l.tmp_jw, BJ);
+    sw.add(sw.l.Gbar, sw.l.Gtmp, BJ * 9);
+    // ... and the rotation pass that made G_k: against the template (k = 0), or against the mesh of iteration k - 1
+    if (k == 0) {
+      sw.rot_adjoint(0, sw.against_template(l.rj0));
+      sw.vertex_pass(false);
+    } else {
+      if (int rc = solve(k - 1, true)) return rc;
+      sw.rot_adjoint(k, sw.against_mesh());
+      sw.vertex_pass(true);
+      SF_HIP_TRY(hipMemsetAsync(sw.l.xb, 0, (size_t)B * nbs * 4, st));
+      SF_HIP_TRY(hipMemsetAsync(sw.l.kb, 0, (size_t)B * 4, st));
+      SF_HIP_TRY(hipMemsetAsync(sw.l.tb, 0, (size_t)B * 3 * 4, st));
+      mesh_cot = true;
+    }
+  }
+  sw.finish(a.grad_trans, a.grad_target_vertices, a.grad_target_joints);
+  return post_launch_check();
+}
+
+// The adjoint of the known-shape fit: the sweep's steps around the forward at the given shape, the
+// alignment with its adjoint, and the copy-out of the shape gradient
+int run_known_shape_backward(const smplfit_handle* h, const smplfit_fit_known_shape_backward_args& a) {
+  const DevModel& d = h->d;
+  const int B = a.batch, n = a.num_iter, nb = a.num_betas_given;
+  const float *tj = a.target_joints, *vw = a.vertex_weights, *jw = a.joint_weights, *kid = a.kid_factor;
+  const bool joints = tj != nullptr, refine = a.final_adjust_rots != 0;
+  const bool shape_grads = (a.grad_shape_betas && nb) || a.grad_kid_factor;
+  hipStream_t st = (hipStream_t)a.hip_stream;
+  Arena ar{(char*)a.workspace};
+  const KnownShapeBackwardLayout l = known_shape_backward_layout(h->t, B, n, ar);
+  RotationSweep sw{h, l.sw, st, B, tj, vw, jw, a.grad_vertex_weights, a.grad_joint_weights};
+  // the model at the given shape and the rotations of iteration k (k < 0: the rest pose), without trans: mesh and joints
+  const auto forward = [&](int k) {
+    smplfit_forward_args fa{};
+    fa.glob_rotmats = k < 0 ? nullptr : sw.Gk(k);
+    fa.shape_betas = a.shape_betas;
+    fa.num_betas_given = nb;
+    fa.kid_factor = kid;
+    fa.batch = B;
+    fa.vertices = sw.l.mesh;
+    fa.joints = sw.l.joints;
+    fa.workspace = sw.l.sub;
+    fa.workspace_bytes = sw.l.sub_bytes;
+    fa.hip_stream = a.hip_stream;
+    return smplfit_forward_ex_f32(h, &fa);
+  };
+  // the cotangents of the mesh and its joints through that forward: Gbar += (with rotations), xb +=, kb +=
+  Arena sub{sw.l.sub};
+  const BackwardLayout bl = backward_layout(h->t, B, sub);
+  const auto mesh_cotangent = [&](int k) {
+    GradOutputs out{};
+    out.glob = k < 0 ? nullptr : sw.l.Gtmp;
+    out.betas = (shape_grads && nb) ? sw.l.xb2 : nullptr;
+    out.kid = (shape_grads && kid) ? sw.l.kb2 : nullptr;
+    return sw.mesh_cotangent(k < 0 ? nullptr : sw.Gk(k), a.shape_betas, kid, nb, out, false, bl);
+  };
+  // ---- forward sweep: the rotations of every iteration, then the alignment at the last mesh
+  if (int rc = sw.begin(a.target_vertices, nullptr)) return rc;
+  for (int k = 0; k < n; ++k) {
+    if (int rc = forward(k - 1)) return rc;
+    sw.rot_forward(k, sw.against_mesh());
+  }
+  if (int rc = forward(n - 1)) return rc;
+  const SolveWeights w = solve_weights(joints, vw, jw);
+  const FaAlign al{sw.l.ctv, joints ? sw.l.ctj : nullptr, w.v ? vw : nullptr, w.j ? jw : nullptr};
+  hipLaunchKernelGGL(k_fa_align, dim3(B), dim3(256), 0, st, d, al, sw.l.mesh, sw.l.joints, l.trans);
+  // ---- reverse sweep.  Output stage and refinement against the aligned mesh (without it its cotangent is zero) ...
+  sw.tail(n - 1, refine, nb, a.shape_betas, kid, l.trans,
+          {a.grad_pose_rotvecs, a.grad_orientations, a.grad_relative_orientations, nullptr, nullptr, a.grad_trans});
+  if (!refine) {
+    SF_HIP_TRY(hipMemsetAsync(sw.l.meshbar, 0, sw.BV() * 3 * 4, st));
+    SF_HIP_TRY(hipMemsetAsync(sw.l.jointsbar, 0, sw.BJ() * 3 * 4, st));
+  }
+  // ... the alignment: the complete tbar, its share of the targets, the weights and the mesh ...
+  const FaAlignAdj aa{al, sw.l.mesh, sw.l.joints, sw.l.meshbar, sw.l.jointsbar, sw.l.tb, sw.l.acc_tv, sw.l.acc_tj,
+                      w.v ? sw.acc_vw : nullptr, w.j ? sw.acc_jw : nullptr};
+  hipLaunchKernelGGL(k_fa_align_adj, dim3(B), dim3(256), 0, st, d, aa);
+  // ... the whole cotangent of the last mesh through the forward at (G_{n-1}, betas) ...
+  if (int rc = mesh_cotangent(n - 1)) return rc;
+  // ... and the rotation passes: G_k = Rot(targets, mesh_k) G_{k-1}, mesh_k the forward at G_{k-1} (k = 0: the rest pose)
+  for (int k = n - 1; k >= 0; --k) {
+    if (int rc = forward(k - 1)) return rc;
+    sw.rot_adjoint(k, sw.against_mesh());
+    sw.vertex_pass(true);
+    if (k == 0 && !shape_grads) break;  // (the cotangent of mesh_0 reaches the shape alone)
+    if (int rc = mesh_cotangent(k - 1)) return rc;
+  }
+  if (a.grad_shape_betas && nb)
+    SF_HIP_TRY(hipMemcpyAsync(a.grad_shape_betas, sw.l.xb, (size_t)B * nb * 4, hipMemcpyDeviceToDevice, st));
+  if (a.grad_kid_factor) SF_HIP_TRY(hipMemcpyAsync(a.grad_kid_factor, sw.l.kb, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+  sw.finish(a.grad_trans, a.grad_target_vertices, a.grad_target_joints);
   return post_launch_check();
 }
 
@@ -3082,180 +3349,16 @@ size_t smplfit_fit_backward_workspace_bytes(const smplfit_handle* h, int batch, 
 int smplfit_fit_backward_f32(const smplfit_handle* h, const smplfit_fit_backward_args* a) {
   const char* who = "smplfit_fit_backward_f32";
   if (!a) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
-  const int B = a->batch, n = a->num_iter;
-  if (n <= 0) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": num_iter must be positive");
-  if (int rc = check_call(who, h, B, a->workspace, a->workspace_bytes, smplfit_fit_backward_workspace_bytes(h, B, n),
-                          "smplfit_fit_backward_workspace_bytes"))
+  if (int rc = check_call(who, h, a->batch, a->workspace, a->workspace_bytes,
+                          smplfit_fit_backward_workspace_bytes(h, a->batch, a->num_iter), "smplfit_fit_backward_workspace_bytes"))
     return rc;
-  const DevModel& d = h->d;
-  if (d.S > sf::kAdjMaxUnknowns) return fail(SMPLFIT_ERR_UNSUPPORTED, std::string(who) + ": more than 17 shape unknowns");
+  if (int rc = check_sweep_call(who, h, a->num_iter, a->target_joints, a->vertex_weights, a->joint_weights,
+                                a->grad_target_joints, a->grad_vertex_weights, a->grad_joint_weights))
+    return rc;
   if (!a->target_vertices) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null pointer");
-  const float *tj = a->target_joints, *vw = a->vertex_weights, *jw = a->joint_weights;
-  const bool joints = tj != nullptr, refine = a->final_adjust_rots != 0, kid = d.jt.n_kid != 0;
-  if (!joints && !h->t.has_regressor)
-    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": target_joints omitted but the model has no J_regressor_post_lbs over its vertices");
-  if (!kid && a->grad_kid_factor) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_kid_factor given to a handle without kid");
-  if (a->grad_target_joints && !joints) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_target_joints without target_joints");
-  if (a->grad_vertex_weights && !vw) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_vertex_weights without vertex_weights");
-  if (a->grad_joint_weights && !jw) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_joint_weights without joint_weights");
-  hipStream_t st = (hipStream_t)a->hip_stream;
-  Arena ar{(char*)a->workspace};
-  FitBackwardLayout l = fit_backward_layout(h->t, B, n, ar);
-  const int J = d.J, V = d.V, nb = h->t.num_betas();
-  const size_t BJ = (size_t)B * J, BV = (size_t)B * V, nbs = (size_t)std::max(1, nb);
-  const unsigned gi = (unsigned)((B + 63) / 64);
-  const auto Gk = [&](int k) { return l.G + (size_t)k * BJ * 9; };
-  const auto bk = [&](int k) { return l.betas + (size_t)k * B * nbs; };
-  const auto kk = [&](int k) { return kid ? l.kid + (size_t)k * B : nullptr; };
-  const auto tk = [&](int k) { return l.trans + (size_t)k * B * 3; };
-  const auto add = [&](float* dst, const float* src, size_t cnt) {
-    hipLaunchKernelGGL(k_fa_add, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, dst, src, cnt);
-  };
-  float *acc_vw = a->grad_vertex_weights, *acc_jw = a->grad_joint_weights;  // (accumulated in place)
-  SF_HIP_TRY(hipMemsetAsync(l.acc_tv, 0, BV * 3 * 4, st));
-  SF_HIP_TRY(hipMemsetAsync(l.acc_tj, 0, BJ * 3 * 4, st));
-  if (acc_vw) SF_HIP_TRY(hipMemsetAsync(acc_vw, 0, BV * 4, st));
-  if (acc_jw) SF_HIP_TRY(hipMemsetAsync(acc_jw, 0, BJ * 4, st));
-  // the shape solve at the rotations of iteration k, in the frame of the centred targets; with the fitted mesh and joints
-  const auto solve = [&](int k, bool mesh) {
-    smplfit_shape_solve_args sa{};
-    sa.glob_rotmats = Gk(k);
-    sa.target_vertices = l.ctv;
-    sa.target_joints = joints ? l.ctj : nullptr;
-    sa.vertex_weights = vw;
-    sa.joint_weights = joints ? jw : nullptr;
-    sa.batch = B;
-    sa.beta_regularizer = a->beta_regularizer;
-    sa.beta_regularizer2 = a->beta_regularizer2;
-    sa.kid_regularizer = a->kid_regularizer;
-    sa.shape_betas = bk(k);
-    sa.trans = tk(k);
-    sa.kid_factor = kk(k);
-    sa.vertices_out = mesh ? l.mesh : nullptr;
-    sa.joints_out = mesh ? l.joints : nullptr;
-    sa.workspace = l.sub;
-    sa.workspace_bytes = l.sub_bytes;
-    sa.hip_stream = a->hip_stream;
-    return smplfit_shape_solve_ex_f32(h, &sa);
-  };
-  // the part sums and the reference joints of a stage against the mesh the last solve left
-  const auto against_mesh = [&]() {
-    if (!joints) hipLaunchKernelGGL(k_fa_regress, dim3(B), dim3(64), 0, st, d, (const float*)l.mesh, l.rjreg);
-    hipLaunchKernelGGL(k_fa_partsums, dim3(B), dim3(256), 0, st, d, (const float*)l.ctv, (const float*)l.mesh, vw, l.psum);
-    return FaJoints{l.ctj, joints ? l.joints : l.rjreg, 0, jw};
-  };
-  const auto against_template = [&]() {
-    hipLaunchKernelGGL(k_fa_partsums, dim3(B), dim3(256), 0, st, d, (const float*)l.ctv, (const float*)nullptr, vw, l.psum);
-    return FaJoints{l.ctj, joints ? d.j_template : l.rj0, 1, jw};
-  };
-  const auto vertex_pass = [&](bool with_mesh) {
-    FaVertexArgs va{l.ctv, with_mesh ? l.mesh : nullptr, vw, joints ? 0 : 1, l.acc_tv, l.acc_tj, acc_vw, acc_jw,
-                    with_mesh ? l.meshbar : nullptr, with_mesh ? l.jointsbar : nullptr};
-    hipLaunchKernelGGL(k_fa_vertex, dim3(B), dim3(256), 0, st, d, va, l.jc);
-  };
-  // ---- forward sweep: the rotations and the solution of every iteration
-  hipLaunchKernelGGL(k_fa_center, dim3(B), dim3(256), 0, st, d, a->target_vertices, tj, l.ctv, l.ctj);
-  if (!joints) {
-    hipLaunchKernelGGL(k_fa_regress, dim3(B), dim3(64), 0, st, d, (const float*)l.ctv, l.ctj);
-    hipLaunchKernelGGL(k_fa_regress, dim3(1), dim3(64), 0, st, d, (const float*)nullptr, l.rj0);
-  }
-  hipLaunchKernelGGL(k_fa_rot_fwd, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, against_template(), (const float*)nullptr, Gk(0), B);
-  for (int k = 0; k < n; ++k) {
-    if (int rc = solve(k, k + 1 < n)) return rc;
-    if (k + 1 < n)
-      hipLaunchKernelGGL(k_fa_rot_fwd, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, against_mesh(), (const float*)Gk(k), Gk(k + 1), B);
-  }
-  // ---- reverse sweep.  Output stage and refinement at the last iteration ...
-  {
-    FaJoints jn{l.ctj, l.ctj, 0, jw};
-    if (refine) {
-      if (int rc = solve(n - 1, true)) return rc;
-      jn = against_mesh();
-    }
-    FaTailArgs ta{Gk(n - 1), bk(n - 1), kk(n - 1), tk(n - 1), l.joints, refine ? 1 : 0, nb, a->grad_pose_rotvecs,
-                  a->grad_orientations, a->grad_relative_orientations, a->grad_shape_betas, kid ? a->grad_kid_factor : nullptr,
-                  a->grad_trans, l.Gbar, l.xb, l.kb, l.tb};
-    hipLaunchKernelGGL(k_fa_tail, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, jn, ta, l.scr, l.jc, B);
-    if (refine) vertex_pass(true);
-  }
-  Arena sub{l.sub};
-  const AdjointLayout al = adjoint_layout(h->t, B, sub);
-  bool mesh_cot = refine;
-  for (int k = n - 1; k >= 0; --k) {
-    // ... the mesh cotangent through the forward at (G_k, x_k, t_k) ...
-    if (mesh_cot) {
-      ForwardInputs in{};
-      in.glob = Gk(k);
-      in.betas = nb ? bk(k) : nullptr;
-      in.kid = kk(k);
-      in.given = nb;
-      Cotangents ct;
-      ct.vertices = l.meshbar;
-      ct.joints = l.jointsbar;
-      GradOutputs out{};
-      out.glob = l.Gtmp;
-      out.betas = nb ? l.xb2 : nullptr;
-      out.trans = l.tb2;
-      out.kid = kid ? l.kb2 : nullptr;
-      if (int rc = launch_forward_backward(h, in, nb, ct, out, al.fb, B, st)) return rc;
-      add(l.Gbar, l.Gtmp, BJ * 9);
-      if (nb) add(l.xb, l.xb2, (size_t)B * nb);
-      if (kid) add(l.kb, l.kb2, (size_t)B);
-      add(l.tb, l.tb2, (size_t)B * 3);
-    }
-    // ... the adjoint of the shape solve: the targets' and weights' gradients and its share of the rotations' ...
-    smplfit_shape_solve_backward_args sb{};
-    sb.glob_rotmats = Gk(k);
-    sb.target_vertices = l.ctv;
-    sb.target_joints = joints ? l.ctj : nullptr;
-    sb.vertex_weights = vw;
-    sb.joint_weights = joints ? jw : nullptr;
-    sb.beta_regularizer = a->beta_regularizer;
-    sb.beta_regularizer2 = a->beta_regularizer2;
-    sb.kid_regularizer = a->kid_regularizer;
-    sb.batch = B;
-    sb.shape_betas = bk(k);
-    sb.trans = tk(k);
-    sb.kid_factor = kk(k);
-    sb.grad_shape_betas = l.xb;
-    sb.grad_trans = l.tb;
-    sb.grad_kid_factor = kid ? l.kb : nullptr;
-    sb.grad_target_vertices = l.tmp_tv;
-    sb.grad_target_joints = joints ? l.tmp_tj : nullptr;
-    sb.grad_vertex_weights = acc_vw ? l.tmp_vw : nullptr;
-    sb.grad_joint_weights = (acc_jw && joints) ? l.tmp_jw : nullptr;
-    sb.grad_glob_rotmats = l.Gtmp;
-    sb.workspace = l.sub;
-    sb.workspace_bytes = l.sub_bytes;
-    sb.hip_stream = a->hip_stream;
-    if (int rc = smplfit_shape_solve_backward_f32(h, &sb)) return rc;
-    add(l.acc_tv, l.tmp_tv, BV * 3);
-    if (joints) add(l.acc_tj, l.tmp_tj, BJ * 3);
-    if (sb.grad_vertex_weights) add(acc_vw, l.tmp_vw, BV);
-    if (sb.grad_joint_weights) add(acc_jw, l.tmp_jw, BJ);
-    add(l.Gbar, l.Gtmp, BJ * 9);
-    // ... and the rotation pass that made G_k: against the template (k = 0), or against the mesh of iteration k - 1
-    if (k == 0) {
-      const FaJoints jn = against_template();
-      hipLaunchKernelGGL(k_fa_rot_adj, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, jn, (const float*)nullptr,
-                         (const float*)l.Gbar, (float*)nullptr, l.scr, l.jc, B);
-      vertex_pass(false);
-    } else {
-      if (int rc = solve(k - 1, true)) return rc;
-      const FaJoints jn = against_mesh();
-      hipLaunchKernelGGL(k_fa_rot_adj, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, jn, (const float*)Gk(k - 1),
-                         (const float*)l.Gbar, l.Gbar2, l.scr, l.jc, B);
-      vertex_pass(true);
-      std::swap(l.Gbar, l.Gbar2);
-      SF_HIP_TRY(hipMemsetAsync(l.xb, 0, (size_t)B * nbs * 4, st));
-      SF_HIP_TRY(hipMemsetAsync(l.kb, 0, (size_t)B * 4, st));
-      SF_HIP_TRY(hipMemsetAsync(l.tb, 0, (size_t)B * 3 * 4, st));
-      mesh_cot = true;
-    }
-  }
-  hipLaunchKernelGGL(k_fa_uncenter, dim3(B), dim3(256), 0, st, d, (const float*)l.acc_tv, joints ? (const float*)l.acc_tj : nullptr,
-                     a->grad_trans, a->grad_target_vertices, a->grad_target_joints);
-  return post_launch_check();
+  if (!h->d.jt.n_kid && a->grad_kid_factor)
+    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_kid_factor given to a handle without kid");
+  return run_fit_backward(h, *a);
 }
 
 size_t smplfit_fit_known_shape_backward_workspace_bytes(const smplfit_handle* h, int batch, int num_iter) {
@@ -3268,141 +3371,19 @@ size_t smplfit_fit_known_shape_backward_workspace_bytes(const smplfit_handle* h,
 int smplfit_fit_known_shape_backward_f32(const smplfit_handle* h, const smplfit_fit_known_shape_backward_args* a) {
   const char* who = "smplfit_fit_known_shape_backward_f32";
   if (!a) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
-  const int B = a->batch, n = a->num_iter;
-  if (n <= 0) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": num_iter must be positive");
-  if (int rc = check_call(who, h, B, a->workspace, a->workspace_bytes, smplfit_fit_known_shape_backward_workspace_bytes(h, B, n),
+  if (int rc = check_call(who, h, a->batch, a->workspace, a->workspace_bytes,
+                          smplfit_fit_known_shape_backward_workspace_bytes(h, a->batch, a->num_iter),
                           "smplfit_fit_known_shape_backward_workspace_bytes"))
     return rc;
-  const DevModel& d = h->d;
-  if (d.S > sf::kAdjMaxUnknowns) return fail(SMPLFIT_ERR_UNSUPPORTED, std::string(who) + ": more than 17 shape unknowns");
+  if (int rc = check_sweep_call(who, h, a->num_iter, a->target_joints, a->vertex_weights, a->joint_weights,
+                                a->grad_target_joints, a->grad_vertex_weights, a->grad_joint_weights))
+    return rc;
   if (!a->shape_betas || !a->target_vertices) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null pointer");
-  const int nb = a->num_betas_given;
-  if (nb < 0 || nb > h->t.num_betas()) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": more betas than the model holds; slice first");
-  const float *tj = a->target_joints, *vw = a->vertex_weights, *jw = a->joint_weights, *kid = a->kid_factor;
-  const bool joints = tj != nullptr, refine = a->final_adjust_rots != 0;
-  if (!joints && !h->t.has_regressor)
-    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": target_joints omitted but the model has no J_regressor_post_lbs over its vertices");
-  if (kid && !d.jt.n_kid) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": kid_factor given to a handle without kid");
-  if (a->grad_kid_factor && !kid) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_kid_factor without kid_factor");
-  if (a->grad_target_joints && !joints) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_target_joints without target_joints");
-  if (a->grad_vertex_weights && !vw) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_vertex_weights without vertex_weights");
-  if (a->grad_joint_weights && !jw) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_joint_weights without joint_weights");
-  hipStream_t st = (hipStream_t)a->hip_stream;
-  Arena ar{(char*)a->workspace};
-  KnownShapeBackwardLayout l = known_shape_backward_layout(h->t, B, n, ar);
-  const int J = d.J, V = d.V;
-  const size_t BJ = (size_t)B * J, BV = (size_t)B * V;
-  const unsigned gi = (unsigned)((B + 63) / 64);
-  const auto Gk = [&](int k) { return l.G + (size_t)k * BJ * 9; };
-  const auto add = [&](float* dst, const float* src, size_t cnt) {
-    hipLaunchKernelGGL(k_fa_add, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, dst, src, cnt);
-  };
-  float *acc_vw = a->grad_vertex_weights, *acc_jw = a->grad_joint_weights;  // (accumulated in place)
-  const bool shape_grads = (a->grad_shape_betas && nb) || a->grad_kid_factor;
-  SF_HIP_TRY(hipMemsetAsync(l.acc_tv, 0, BV * 3 * 4, st));
-  SF_HIP_TRY(hipMemsetAsync(l.acc_tj, 0, BJ * 3 * 4, st));
-  if (acc_vw) SF_HIP_TRY(hipMemsetAsync(acc_vw, 0, BV * 4, st));
-  if (acc_jw) SF_HIP_TRY(hipMemsetAsync(acc_jw, 0, BJ * 4, st));
-  // the model at the given shape and the rotations `glob` (null: the rest pose), without trans: mesh and joints
-  const auto forward = [&](const float* glob) {
-    smplfit_forward_args fa{};
-    fa.glob_rotmats = glob;
-    fa.shape_betas = a->shape_betas;
-    fa.num_betas_given = nb;
-    fa.kid_factor = kid;
-    fa.batch = B;
-    fa.vertices = l.mesh;
-    fa.joints = l.joints;
-    fa.workspace = l.sub;
-    fa.workspace_bytes = l.sub_bytes;
-    fa.hip_stream = a->hip_stream;
-    return smplfit_forward_ex_f32(h, &fa);
-  };
-  // the part sums and the reference joints of a stage against the mesh the last forward left
-  const auto against_mesh = [&]() {
-    if (!joints) hipLaunchKernelGGL(k_fa_regress, dim3(B), dim3(64), 0, st, d, (const float*)l.mesh, l.rjreg);
-    hipLaunchKernelGGL(k_fa_partsums, dim3(B), dim3(256), 0, st, d, (const float*)l.ctv, (const float*)l.mesh, vw, l.psum);
-    return FaJoints{l.ctj, joints ? l.joints : l.rjreg, 0, jw};
-  };
-  const auto vertex_pass = [&]() {
-    FaVertexArgs va{l.ctv, l.mesh, vw, joints ? 0 : 1, l.acc_tv, l.acc_tj, acc_vw, acc_jw, l.meshbar, l.jointsbar};
-    hipLaunchKernelGGL(k_fa_vertex, dim3(B), dim3(256), 0, st, d, va, l.jc);
-  };
-  // the cotangents of the mesh and its joints through the forward at (glob, betas): Gtmp (with glob), xb += , kb +=
-  Arena sub{l.sub};
-  const BackwardLayout bl = backward_layout(h->t, B, sub);
-  const auto mesh_cotangent = [&](const float* glob) {
-    ForwardInputs in{};
-    in.glob = glob;
-    in.betas = nb ? a->shape_betas : nullptr;
-    in.kid = kid;
-    in.given = nb;
-    Cotangents ct;
-    ct.vertices = l.meshbar;
-    ct.joints = l.jointsbar;
-    GradOutputs out{};
-    out.glob = glob ? l.Gtmp : nullptr;
-    out.betas = (shape_grads && nb) ? l.xb2 : nullptr;
-    out.kid = (shape_grads && kid) ? l.kb2 : nullptr;
-    if (int rc = launch_forward_backward(h, in, nb, ct, out, bl, B, st)) return rc;
-    if (out.betas) add(l.xb, l.xb2, (size_t)B * nb);
-    if (out.kid) add(l.kb, l.kb2, (size_t)B);
-    return 0;
-  };
-  // ---- forward sweep: the rotations of every iteration, then the alignment at the last mesh
-  hipLaunchKernelGGL(k_fa_center, dim3(B), dim3(256), 0, st, d, a->target_vertices, tj, l.ctv, l.ctj);
-  if (!joints) hipLaunchKernelGGL(k_fa_regress, dim3(B), dim3(64), 0, st, d, (const float*)l.ctv, l.ctj);
-  for (int k = 0; k < n; ++k) {
-    if (int rc = forward(k ? Gk(k - 1) : nullptr)) return rc;
-    hipLaunchKernelGGL(k_fa_rot_fwd, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, against_mesh(),
-                       k ? (const float*)Gk(k - 1) : (const float*)nullptr, Gk(k), B);
-  }
-  if (int rc = forward(Gk(n - 1))) return rc;
-  const SolveWeights w = solve_weights(joints, vw, jw);
-  const FaAlign al{l.ctv, joints ? l.ctj : nullptr, w.v ? vw : nullptr, w.j ? jw : nullptr};
-  hipLaunchKernelGGL(k_fa_align, dim3(B), dim3(256), 0, st, d, al, l.mesh, l.joints, l.trans);
-  // ---- reverse sweep.  Output stage and refinement against the aligned mesh ...
-  {
-    FaJoints jn{l.ctj, l.ctj, 0, jw};
-    if (refine) jn = against_mesh();
-    FaTailArgs ta{Gk(n - 1), a->shape_betas, kid, l.trans, l.joints, refine ? 1 : 0, nb, a->grad_pose_rotvecs,
-                  a->grad_orientations, a->grad_relative_orientations, nullptr, nullptr, a->grad_trans, l.Gbar, l.xb, l.kb, l.tb};
-    hipLaunchKernelGGL(k_fa_tail, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, jn, ta, l.scr, l.jc, B);
-    if (refine) {
-      vertex_pass();
-    } else {
-      SF_HIP_TRY(hipMemsetAsync(l.meshbar, 0, BV * 3 * 4, st));
-      SF_HIP_TRY(hipMemsetAsync(l.jointsbar, 0, BJ * 3 * 4, st));
-    }
-  }
-  // ... the alignment: the complete tbar, its share of the targets, the weights and the mesh ...
-  {
-    FaAlignAdj aa{al, l.mesh, l.joints, l.meshbar, l.jointsbar, l.tb, l.acc_tv, l.acc_tj, w.v ? acc_vw : nullptr, w.j ? acc_jw : nullptr};
-    hipLaunchKernelGGL(k_fa_align_adj, dim3(B), dim3(256), 0, st, d, aa);
-  }
-  // ... the whole cotangent of the last mesh through the forward at (G_{n-1}, betas) ...
-  if (int rc = mesh_cotangent(Gk(n - 1))) return rc;
-  add(l.Gbar, l.Gtmp, BJ * 9);
-  // ... and the rotation passes: G_k = Rot(targets, mesh_k) G_{k-1}, mesh_k the forward at G_{k-1} (k = 0: the rest pose)
-  for (int k = n - 1; k >= 0; --k) {
-    if (int rc = forward(k ? Gk(k - 1) : nullptr)) return rc;
-    const FaJoints jn = against_mesh();
-    hipLaunchKernelGGL(k_fa_rot_adj, dim3(gi), dim3(64), 0, st, d, (const double*)l.psum, jn,
-                       k ? (const float*)Gk(k - 1) : (const float*)nullptr, (const float*)l.Gbar, k ? l.Gbar2 : (float*)nullptr,
-                       l.scr, l.jc, B);
-    vertex_pass();
-    if (k == 0 && !shape_grads) break;  // (the cotangent of mesh_0 reaches the shape alone)
-    if (int rc = mesh_cotangent(k ? Gk(k - 1) : nullptr)) return rc;
-    if (k) {
-      add(l.Gbar2, l.Gtmp, BJ * 9);
-      std::swap(l.Gbar, l.Gbar2);
-    }
-  }
-  if (a->grad_shape_betas && nb) SF_HIP_TRY(hipMemcpyAsync(a->grad_shape_betas, l.xb, (size_t)B * nb * 4, hipMemcpyDeviceToDevice, st));
-  if (a->grad_kid_factor) SF_HIP_TRY(hipMemcpyAsync(a->grad_kid_factor, l.kb, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(k_fa_uncenter, dim3(B), dim3(256), 0, st, d, (const float*)l.acc_tv, joints ? (const float*)l.acc_tj : nullptr,
-                     a->grad_trans, a->grad_target_vertices, a->grad_target_joints);
-  return post_launch_check();
+  if (a->num_betas_given < 0 || a->num_betas_given > h->t.num_betas())
+    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": more betas than the model holds; slice first");
+  if (a->kid_factor && !h->d.jt.n_kid) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": kid_factor given to a handle without kid");
+  if (a->grad_kid_factor && !a->kid_factor) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_kid_factor without kid_factor");
+  return run_known_shape_backward(h, *a);
 }
 
 // ---- topology transfer + fused conversion ---------------------------------------------------------

@@ -413,11 +413,28 @@ WORKSPACE_PINS = {
 }
 
 
+# (model, kid, B) -> smplfit_fit_backward_workspace_bytes and smplfit_fit_known_shape_backward_workspace_bytes at
+# num_iter = 1 and 3 each.  Recorded from the build in front of the commit that lays the sweep both share out once.
+BACKWARD_PINS = {
+    ('smpl', False, 1): (86212096, 86213888, 85929472, 85931264),
+    ('smpl', False, 65): (146670080, 146789632, 128512000, 128624384),
+    ('smpl', False, 129): (292381952, 292619264, 256348416, 256571392),
+    ('smpl', True, 1): (90261504, 90263296, 89978880, 89980672),
+    ('smpl', True, 65): (150767616, 150887168, 132609280, 132721664),
+    ('smpl', True, 129): (300575744, 300813056, 264541696, 264764672),
+    ('smplx', False, 1): (107684352, 107688448, 107253504, 107257600),
+    ('smplx', False, 65): (203666432, 203931136, 175888896, 176146432),
+    ('smplx', False, 129): (405820160, 406345472, 350695936, 351206912),
+}
+
+
 @pytest.mark.parametrize('name,kid', [('smpl', False), ('smpl', True), ('smplx', False)])
 def test_workspace_layout_queries(lib, name, kid, model_root, golden):
-    """The five handle-level workspace queries of a host-only handle at B = 1, 64, 65, 129: the mesh objective takes the
+    """The handle-level workspace queries of a host-only handle at B = 1, 64, 65, 129: the mesh objective takes the
     backward's workspace, the fit objective adds one 256-byte aligned (B, J, 3) cotangent, the adjoint adds its own
-    regions behind the backward's, and the sizes are the recorded ones."""
+    regions behind the backward's, and the sizes are the recorded ones.  The adjoints of fit and of fit_with_known_shape
+    (B = 1, 65, 129; num_iter 1 to 3): both grow with num_iter by exactly their per-iteration regions, the fit's is the
+    larger at equal arguments, and the sizes are the recorded ones."""
     import hostemu_util as H
 
     kind, md = util.load_md(model_root, name, golden(name))
@@ -433,4 +450,15 @@ def test_workspace_layout_queries(lib, name, kid, model_root, golden):
         assert adj > fb
         if (name, kid, B) in WORKSPACE_PINS:
             assert (fit, fb, adj - fb) == WORKSPACE_PINS[name, kid, B], (name, kid, B)
+    # the adjoints of both differentiable fits: the sweep's layout, then what each adds
+    nb, r = max(1, h.info.num_betas), lambda nbytes: (nbytes + 255) // 256 * 256
+    for B in (1, 65, 129):
+        fitb = {n: h.fit_backward_workspace_bytes(B, n) for n in (1, 2, 3)}
+        ksb = {n: h.fit_known_shape_backward_workspace_bytes(B, n) for n in (1, 2, 3)}
+        assert all(fitb[n] > ksb[n] > 0 for n in fitb)
+        for n in (2, 3):  # per iteration: the rotations; the fit also keeps betas, kid and trans
+            grow = r(36 * n * B * J) - r(36 * B * J)
+            assert ksb[n] - ksb[1] == grow
+            assert fitb[n] - fitb[1] == grow + sum(r(4 * n * B * k) - r(4 * B * k) for k in (nb, 1, 3))
+        assert (fitb[1], fitb[3], ksb[1], ksb[3]) == BACKWARD_PINS[name, kid, B], (name, kid, B)
     h.close()
