@@ -608,6 +608,15 @@ int smplfit_transfer_create(int32_t num_vertices_in, int32_t num_vertices_out, c
 void smplfit_transfer_destroy(smplfit_transfer* t);
 int smplfit_transfer_f32(const smplfit_transfer* t, const float* in_vertices, int batch, float* out_vertices,
                          void* hip_stream);
+/* Adjoint of smplfit_transfer_f32: grad_in (B,V_in,3) = M^T grad_out (B,V_out,3); with SMPLFIT_TRANSFER_NEGATE_X the x
+ * component is negated as well (the negation is diagonal and commutes with the product).  The entries of an input
+ * vertex are added in ascending output-row order: deterministic, no float atomics.  An input vertex that no row
+ * uses gets exactly 0.  Device pointers, stream-ordered, no workspace, no allocation, no synchronisation.
+ * Refusals as smplfit_transfer_f32 (null pointer / negative batch: SMPLFIT_ERR_BAD_ARG; a host-only matrix:
+ * SMPLFIT_ERR_HIP), with ONE difference: a batch of 0 returns SMPLFIT_OK before the matrix is looked at, so also for a
+ * host-only matrix, where smplfit_transfer_f32 refuses the host-only matrix first. */
+int smplfit_transfer_backward_f32(const smplfit_transfer* t, const float* grad_out_vertices, int batch,
+                                  float* grad_in_vertices, void* hip_stream);
 
 /*
  * BodyConverter.convert, default branch (pt/bodyconverter.py:49-126: forward of the input model :86, convert_vertices

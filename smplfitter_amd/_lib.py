@@ -40,7 +40,7 @@ EXPORTED_SYMBOLS = [
     'smplfit_forward_f32', 'smplfit_part_rotations_f32', 'smplfit_shape_solve_f32',
     'smplfit_shape_solve_ex_f32', 'smplfit_fit_known_shape_f32', 'smplfit_fit_warm_f32', 'smplfit_fit_ex_f32',
     'smplfit_time_kernel_f32', 'smplfit_primitives_f32', 'smplfit_forward_ex_f32',
-    'smplfit_transfer_create', 'smplfit_transfer_destroy', 'smplfit_transfer_f32',
+    'smplfit_transfer_create', 'smplfit_transfer_destroy', 'smplfit_transfer_f32', 'smplfit_transfer_backward_f32',
     'smplfit_convert_plan_create', 'smplfit_convert_plan_destroy', 'smplfit_convert_workspace_bytes',
     'smplfit_convert_f32', 'smplfit_flip_plan_create', 'smplfit_flip_plan_destroy', 'smplfit_flip_workspace_bytes',
     'smplfit_flip_f32', 'smplfit_reload_options', 'smplfit_get_share_table', 'smplfit_pick_share_mult',
@@ -335,6 +335,8 @@ def load():
     lib.smplfit_transfer_destroy.restype = None
     lib.smplfit_transfer_f32.argtypes = [vp, vp, i32, vp, vp]
     lib.smplfit_transfer_f32.restype = i32
+    lib.smplfit_transfer_backward_f32.argtypes = [vp, vp, i32, vp, vp]
+    lib.smplfit_transfer_backward_f32.restype = i32
     lib.smplfit_convert_plan_create.argtypes = [vp, vp, vp, C.POINTER(vp)]
     lib.smplfit_convert_plan_create.restype = i32
     lib.smplfit_convert_plan_destroy.argtypes = [vp]
@@ -539,6 +541,17 @@ class Transfer:
     @property
     def ptr(self):
         return self._t
+
+    def forward(self, in_vertices: int, batch: int, out_vertices: int, stream: 'int | None' = None):
+        """``smplfit_transfer_f32`` on device addresses: (batch, V_in, 3) -> (batch, V_out, 3)."""
+        vp = C.c_void_p
+        check(load().smplfit_transfer_f32(self._t, vp(in_vertices), int(batch), vp(out_vertices), vp(stream)))
+
+    def backward(self, grad_out_vertices: int, batch: int, grad_in_vertices: int, stream: 'int | None' = None):
+        """``smplfit_transfer_backward_f32`` on device addresses: (batch, V_out, 3) -> (batch, V_in, 3)."""
+        vp = C.c_void_p
+        check(load().smplfit_transfer_backward_f32(self._t, vp(grad_out_vertices), int(batch), vp(grad_in_vertices),
+                                                   vp(stream)))
 
     def close(self):
         if getattr(self, '_t', None) is not None and self._t.value:

@@ -3230,6 +3230,9 @@ __global__ __launch_bounds__(256) void k_transfer_bm(TransferTabs tt, const floa
 // every thread forms output vertices from LDS and the rows go out as contiguous 12-byte pieces.
 // grid B, block 1024, dynamic LDS 12 V_in bytes; STAGED = false (V_in beyond the LDS): gathers from global memory.
 // NEG: x -> -x after the row sum (SMPLFIT_TRANSFER_NEGATE_X).
+// smplfit_transfer_backward_f32 runs the same kernel on the CSR form of the transposed matrix (sf::transpose_csr) with
+// Vin and Vout swapped: `in` is then the cotangent (B, V_out, 3), a "row" an input vertex, whose entries are added in
+// ascending output-row order; a vertex without entries stores its zero accumulators.
 template <bool STAGED, bool NEG>
 __global__ __launch_bounds__(1024) void k_transfer_rows(const float* __restrict__ in, float* __restrict__ out,
                                                         const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices,

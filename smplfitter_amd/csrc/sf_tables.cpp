@@ -949,4 +949,22 @@ void build_tiled_gemm_images(HostTables& t) {
   }
 }
 
+void transpose_csr(int rows, int cols, const std::vector<int32_t>& indptr, const std::vector<int32_t>& indices,
+                   const std::vector<float>& values, std::vector<int32_t>& t_indptr, std::vector<int32_t>& t_indices,
+                   std::vector<float>& t_values) {
+  const int nnz = indptr[rows];
+  t_indptr.assign((size_t)cols + 1, 0);
+  t_indices.assign(nnz, 0);
+  t_values.assign(nnz, 0.f);
+  for (int e = 0; e < nnz; ++e) ++t_indptr[indices[e] + 1];
+  for (int c = 0; c < cols; ++c) t_indptr[c + 1] += t_indptr[c];
+  std::vector<int32_t> next(t_indptr.begin(), t_indptr.end() - 1);  // next free entry of every column
+  for (int r = 0; r < rows; ++r)
+    for (int e = indptr[r]; e < indptr[r + 1]; ++e) {
+      const int32_t at = next[indices[e]]++;
+      t_indices[at] = r;
+      t_values[at] = values[e];
+    }
+}
+
 }  // namespace sf

@@ -274,6 +274,13 @@ std::string build_tables(const smplfit_model_desc& d, HostTables& t, bool* unsup
 int pick_share_mult(const HostTables& t, int kind, int nblocks, int slots, int wg_waves = kBmWaves);
 void build_share_tables(HostTables& t);
 
+// CSR of the transpose of a (rows x cols) CSR matrix (the adjoint of the topology transfer, smplfit_transfer_backward_f32):
+// a stable counting sort by column, so the entries of a column come out in ascending row order and duplicates inside a
+// row stay separate entries in their CSR order.  `indices` must lie in [0, cols) (smplfit_transfer_create checks it).
+void transpose_csr(int rows, int cols, const std::vector<int32_t>& indptr, const std::vector<int32_t>& indices,
+                   const std::vector<float>& values, std::vector<int32_t>& t_indptr, std::vector<int32_t>& t_indices,
+                   std::vector<float>& t_values);
+
 // (n, 3) start, count, part
 inline std::vector<int32_t> flatten(const std::vector<Segment>& segs) {
   std::vector<int32_t> out;

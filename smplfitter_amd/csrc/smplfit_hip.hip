@@ -20,7 +20,8 @@
 // Batch-major kernels (LANE = INSTANCE; the default vertex block where they apply, see route_of): k_layout_targets,
 //   k_mean_finish, k_template_partsum_bm, k_residual_bm, k_pair_gram_bm, k_gram_combine_bm, k_lbs_partsum_bm,
 //   k_psum_combine, k_regress_joints_bm, k_transpose_targets (joint rows) — grid = (vertex group | unit chunk) x
-//   instance blocks of 64; k_transfer_bm / k_transfer_rows: topology transfer (BodyConverter).
+//   instance blocks of 64; k_transfer_bm / k_transfer_rows: topology transfer (BodyConverter), k_transfer_rows on the
+//   transposed matrix: its adjoint (smplfit_transfer_backward_f32).
 // Everything is enqueued on the caller's stream; no host synchronisation, no allocation.
 #include <hip/hip_runtime.h>
 
@@ -160,13 +161,14 @@ struct smplfit_handle {
   mutable std::mutex mu;
 };
 
-// Topology-transfer matrix (BodyConverter's vertex_converter_csr, pt/bodyconverter.py:31-47): host + device CSR.
+// Topology-transfer matrix (BodyConverter's vertex_converter_csr, pt/bodyconverter.py:31-47): host + device CSR, and
+// the CSR of its transpose (t_*, sf::transpose_csr) for smplfit_transfer_backward_f32.
 struct smplfit_transfer {
   int v_in = 0, v_out = 0;
-  std::vector<int32_t> indptr, indices;
-  std::vector<float> values;
-  int32_t *d_indptr = nullptr, *d_indices = nullptr;
-  float* d_values = nullptr;
+  std::vector<int32_t> indptr, indices, t_indptr, t_indices;
+  std::vector<float> values, t_values;
+  int32_t *d_indptr = nullptr, *d_indices = nullptr, *d_t_indptr = nullptr, *d_t_indices = nullptr;
+  float *d_values = nullptr, *d_t_values = nullptr;
   DeviceArrays dev;
   bool negate_x = false;  // SMPLFIT_TRANSFER_NEGATE_X: x -> -x after the product (the mirror of BodyFlipper)
 };
@@ -2109,16 +2111,19 @@ smplfit_fit_args fused_fit_args(const A& a) {
   return f;
 }
 
-// smplfit_transfer_f32: the staged form where the input rows fit the LDS
+// smplfit_transfer_f32 / smplfit_transfer_backward_f32: out (B,Vout,3) = A in (B,Vin,3) with the (Vout x Vin) device CSR
+// A — the matrix, or its transpose with the two vertex counts swapped; the staged form where the input rows fit the LDS
 template <bool NEG>
-void launch_transfer_rows(const smplfit_transfer* t, const float* in, int batch, float* out, size_t lds, hipStream_t st) {
+void launch_transfer_rows(const int32_t* d_indptr, const int32_t* d_indices, const float* d_values, int Vin, int Vout,
+                          const float* in, int batch, float* out, hipStream_t st) {
+  const size_t lds = (size_t)Vin * 12;
   if (lds <= 160 * 1024) {
     ensure_max_lds(reinterpret_cast<const void*>(&k_transfer_rows<true, NEG>));
-    hipLaunchKernelGGL((k_transfer_rows<true, NEG>), dim3(batch), dim3(1024), lds, st, in, out, t->d_indptr, t->d_indices,
-                       t->d_values, t->v_in, t->v_out);
+    hipLaunchKernelGGL((k_transfer_rows<true, NEG>), dim3(batch), dim3(1024), lds, st, in, out, d_indptr, d_indices,
+                       d_values, Vin, Vout);
   } else {
-    hipLaunchKernelGGL((k_transfer_rows<false, NEG>), dim3(batch), dim3(1024), 0, st, in, out, t->d_indptr, t->d_indices,
-                       t->d_values, t->v_in, t->v_out);
+    hipLaunchKernelGGL((k_transfer_rows<false, NEG>), dim3(batch), dim3(1024), 0, st, in, out, d_indptr, d_indices,
+                       d_values, Vin, Vout);
   }
 }
 
@@ -3409,8 +3414,12 @@ int smplfit_transfer_create(int32_t num_vertices_in, int32_t num_vertices_out, c
   t->indices.assign(indices, indices + nnz);
   t->values.assign(values, values + nnz);
   t->negate_x = (flags & SMPLFIT_TRANSFER_NEGATE_X) != 0;
+  sf::transpose_csr(t->v_out, t->v_in, t->indptr, t->indices, t->values, t->t_indptr, t->t_indices, t->t_values);
   if (!(flags & SMPLFIT_CREATE_HOST_ONLY) &&
-      (t->dev.upload(t->indptr, &t->d_indptr) || t->dev.upload(t->indices, &t->d_indices) || t->dev.upload(t->values, &t->d_values))) {
+      (t->dev.upload(t->indptr, &t->d_indptr) || t->dev.upload(t->indices, &t->d_indices) ||
+       t->dev.upload(t->values, &t->d_values) ||
+       t->dev.upload(t->t_indptr, &t->d_t_indptr) || t->dev.upload(t->t_indices, &t->d_t_indices) ||
+       t->dev.upload(t->t_values, &t->d_t_values))) {
     smplfit_transfer_destroy(t);
     return fail(SMPLFIT_ERR_HIP, "smplfit_transfer_create: device upload failed");
   }
@@ -3431,9 +3440,28 @@ int smplfit_transfer_f32(const smplfit_transfer* t, const float* in_vertices, in
   if (!t->d_indptr) return fail(SMPLFIT_ERR_HIP, "smplfit_transfer_f32: the matrix was created host-only (no device)");
   if (batch == 0) return SMPLFIT_OK;
   hipStream_t st = (hipStream_t)hip_stream;
-  const size_t lds = (size_t)t->v_in * 12;
-  if (t->negate_x) launch_transfer_rows<true>(t, in_vertices, batch, out_vertices, lds, st);
-  else launch_transfer_rows<false>(t, in_vertices, batch, out_vertices, lds, st);
+  if (t->negate_x)
+    launch_transfer_rows<true>(t->d_indptr, t->d_indices, t->d_values, t->v_in, t->v_out, in_vertices, batch, out_vertices, st);
+  else
+    launch_transfer_rows<false>(t->d_indptr, t->d_indices, t->d_values, t->v_in, t->v_out, in_vertices, batch, out_vertices, st);
+  return post_launch_check();
+}
+
+// grad_in = M^T grad_out: k_transfer_rows on the transposed CSR, the cotangent on the staged side (12 V_out bytes of LDS)
+int smplfit_transfer_backward_f32(const smplfit_transfer* t, const float* grad_out_vertices, int batch,
+                                  float* grad_in_vertices, void* hip_stream) {
+  if (!t || !grad_out_vertices || !grad_in_vertices || batch < 0)
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_transfer_backward_f32: null pointer / negative batch");
+  if (batch == 0) return SMPLFIT_OK;  // nothing to enqueue: before the host-only check (unlike the forward; see the header)
+  if (!t->d_t_indptr)
+    return fail(SMPLFIT_ERR_HIP, "smplfit_transfer_backward_f32: the matrix was created host-only (no device)");
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (t->negate_x)
+    launch_transfer_rows<true>(t->d_t_indptr, t->d_t_indices, t->d_t_values, t->v_out, t->v_in, grad_out_vertices, batch,
+                               grad_in_vertices, st);
+  else
+    launch_transfer_rows<false>(t->d_t_indptr, t->d_t_indices, t->d_t_values, t->v_out, t->v_in, grad_out_vertices, batch,
+                                grad_in_vertices, st);
   return post_launch_check();
 }
 

@@ -7,6 +7,11 @@ Everything runs in the HIP kernels.  The default ``convert`` branch is ONE C-ABI
 the input model's forward, the topology transfer and the fit hand their meshes to each other in the kernels' own
 instance-innermost stream layout, so no ``(B, V, 3)`` intermediate is written.  ``convert_vertices`` — the
 stand-alone transfer a caller can use on its own — is ``smplfit_transfer_f32`` (``k_transfer_rows``).
+
+Differentiable: ``convert_vertices`` of an input that requires grad runs the same call under an autograd
+``Function`` whose backward is ``smplfit_transfer_backward_f32`` (the transposed matrix through the same kernel), and
+``convert`` with an input that requires grad runs as the three differentiable calls it is made of — the input model's
+forward, ``convert_vertices``, the fit of its branch — so its backward is their native adjoints in turn.
 """
 
 from __future__ import annotations
@@ -107,7 +112,13 @@ class BodyConverter(nn.Module):
         known_output_kid_factor: Optional[torch.Tensor] = None,
         num_iter: int = 1,
     ) -> dict[str, torch.Tensor]:
-        """Same arguments / results as the reference's ``convert`` (pt/bodyconverter.py:49-126)."""
+        """Same arguments / results as the reference's ``convert`` (pt/bodyconverter.py:49-126).
+
+        Differentiable, as the reference's is: when gradients are enabled and ``pose_rotvecs``, ``shape_betas``, ``trans``
+        or the ``known_output_*`` tensor of the branch requires grad, the call runs as ``body_model_in`` ->
+        :meth:`convert_vertices` -> ``fit`` / ``fit_with_known_shape`` / ``fit_with_known_pose`` (the calls the fused
+        one stands for), each with its native backward.  ``kid_factor`` only selects the kid ridge weight and whether
+        ``kid_factor`` is returned, so it gets no gradient."""
         kid_reg = 1e9 if kid_factor is None else 0.0
         if known_output_shape_betas is None and known_output_pose_rotvecs is None:
             fit = self._convert_fused(pose_rotvecs, shape_betas, trans, num_iter, kid_reg)
@@ -146,7 +157,7 @@ class BodyConverter(nn.Module):
         if torch.compiler.is_compiling() or device.type != 'cuda' or pose_rotvecs.shape[0] == 0:
             return None
         if any(t is not None and t.requires_grad for t in (pose_rotvecs, shape_betas, trans)):
-            return None  # the fit raises the NotImplementedError of the unfused path
+            return None  # forward + convert_vertices + fit, each differentiable
         plan = self._plan(device)
         if plan is None:
             return None
@@ -183,21 +194,47 @@ class BodyConverter(nn.Module):
 
     def convert_vertices(self, inp_vertices: torch.Tensor) -> torch.Tensor:
         """Barycentric topology transfer (pt/bodyconverter.py:128-149); identity when the two models share a
-        topology.  ``smplfit_transfer_f32``: (B, V_in, 3) -> (B, V_out, 3)."""
+        topology.  ``smplfit_transfer_f32``: (B, V_in, 3) -> (B, V_out, 3).  With gradients enabled and an input that
+        requires grad the result carries a ``grad_fn`` whose backward is ``smplfit_transfer_backward_f32`` (once
+        differentiable; the gradient comes back in the input's shape, dtype and device)."""
         if self.vertex_converter_csr is None:
             return inp_vertices
         vout, vin = self.vertex_converter_csr.shape
         if inp_vertices.ndim != 3 or tuple(inp_vertices.shape[1:]) != (vin, 3):
             raise ValueError(f'inp_vertices must have shape (batch, {vin}, 3), got {tuple(inp_vertices.shape)}')
-        if inp_vertices.requires_grad:
-            raise NotImplementedError('the HIP transfer kernel is not differentiable; detach the input')
+        if torch.is_grad_enabled() and inp_vertices.requires_grad:
+            if torch.compiler.is_compiling():  # (as before: no gradient is dropped silently in a traced graph)
+                raise NotImplementedError('the HIP transfer kernel is not differentiable under torch.compile; detach the input')
+            return _TransferFn.apply(self, inp_vertices)
+        return self._transfer_direct(inp_vertices.detach(), backward=False)
+
+    def _transfer_direct(self, vertices: torch.Tensor, backward: bool) -> torch.Tensor:
+        """The C-ABI call of ``convert_vertices`` (``smplfit_transfer_f32``) or, with ``backward``, of its adjoint
+        (``smplfit_transfer_backward_f32``: (B, V_out, 3) -> (B, V_in, 3)), on the current stream."""
+        vout, vin = self.vertex_converter_csr.shape
         device = self.body_model_out.v_template.device
-        v = inp_vertices.to(device=device, dtype=torch.float32).contiguous()
-        out = torch.empty((v.shape[0], vout, 3), dtype=torch.float32, device=device)
+        v = vertices.to(device=device, dtype=torch.float32).contiguous()
+        out = torch.empty((v.shape[0], vin if backward else vout, 3), dtype=torch.float32, device=device)
         if v.shape[0] > 0:
             t = self._transfer(device)
+            call = t.backward if backward else t.forward
             with torch.cuda.device(device):
-                _lib.check(_lib.load().smplfit_transfer_f32(
-                    t.ptr, C.c_void_p(v.data_ptr()), v.shape[0], C.c_void_p(out.data_ptr()),
-                    C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+                call(v.data_ptr(), v.shape[0], out.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
         return out
+
+
+class _TransferFn(torch.autograd.Function):
+    """``convert_vertices`` under autograd: the forward is the call made without gradients (the same bits), the backward
+    ``smplfit_transfer_backward_f32``.  The map is linear: nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, converter, vertices):
+        ctx.converter, ctx.like = converter, (vertices.shape, vertices.dtype, vertices.device)
+        return converter._transfer_direct(vertices.detach(), backward=False)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        shape, dtype, device = ctx.like
+        g = ctx.converter._transfer_direct(grad, backward=True)
+        return None, g.reshape(shape).to(device=device, dtype=dtype)
