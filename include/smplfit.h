@@ -742,6 +742,32 @@ typedef struct smplfit_replace_hands_args {
 } smplfit_replace_hands_args;
 int smplfit_replace_hands_f32(const smplfit_replace_hands_plan* plan, const smplfit_replace_hands_args* args);
 
+/* ---- share_beta over segments of the batch: many tracks in one call -----------
+ * A plan of segments cuts the batch into consecutive runs of rows — `sizes`, a HOST array of `count` positive sizes
+ * that sum to the batch — and a call with it solves one shape (and one kid factor) per run, as share_beta does for a
+ * whole batch: the rows of a run get exactly the bits of a share_beta call on those rows alone.  Every option of
+ * share_beta holds (weights, num_iter, ridge weights, warm starts, kid, the scale options: one shape per run, one
+ * scale per row).  The sum of a run's systems has a fixed order that depends on the sizes alone (blocks of 64 rows
+ * counted from the run's first row, then the run's partial rows; no atomics).
+ *   smplfit_share_segments_create: SMPLFIT_ERR_BAD_ARG for count < 1, a size < 1 or a sum beyond INT32_MAX; flags:
+ *   SMPLFIT_CREATE_HOST_ONLY builds the tables without a device (the calls below then refuse the plan).  The plan
+ *   owns device copies of its tables on the device that was current at creation and may serve any handle there.
+ *   smplfit_share_segments_get_table: `what` 0 the run of every row (batch), 1 per run (first partial block, blocks),
+ *   2 per partial block (first row, rows); the calling convention of smplfit_get_table.
+ *   smplfit_fit_segments_f32 / smplfit_shape_solve_segments_f32: the _ex calls with a plan.  share_beta is implied;
+ *   args->batch must equal the plan's and share_allreduce must be NULL (SMPLFIT_ERR_BAD_ARG).  With a NULL plan they
+ *   ARE the _ex calls.  Workspace: smplfit_share_segments_workspace_bytes(h, batch, plan) — with a NULL plan the value
+ *   of smplfit_workspace_bytes(h, batch); 0 for a batch that is not the plan's. */
+typedef struct smplfit_share_segments smplfit_share_segments;
+int smplfit_share_segments_create(const int32_t* sizes, int32_t count, int32_t flags, smplfit_share_segments** out);
+void smplfit_share_segments_destroy(smplfit_share_segments* plan);
+int32_t smplfit_share_segments_batch(const smplfit_share_segments* plan);
+int smplfit_share_segments_get_table(const smplfit_share_segments* plan, int what, int32_t* dst, size_t cap, size_t* n);
+size_t smplfit_share_segments_workspace_bytes(const smplfit_handle* h, int batch, const smplfit_share_segments* plan);
+int smplfit_fit_segments_f32(const smplfit_handle* h, const smplfit_fit_args* args, const smplfit_share_segments* plan);
+int smplfit_shape_solve_segments_f32(const smplfit_handle* h, const smplfit_shape_solve_args* args,
+                                     const smplfit_share_segments* plan);
+
 /* Re-reads the SMPLFIT_* tuning variables (INTEGRATION.md lists them).  They are read once, at first use; tests and
  * the A/B tools that switch kernel paths inside one process call this after changing the environment.  Not to be
  * called while other threads are inside the library. */

@@ -52,6 +52,9 @@ EXPORTED_SYMBOLS = [
     'smplfit_shape_solve_backward_workspace_bytes', 'smplfit_shape_solve_backward_f32',
     'smplfit_fit_backward_workspace_bytes', 'smplfit_fit_backward_f32',
     'smplfit_fit_known_shape_backward_workspace_bytes', 'smplfit_fit_known_shape_backward_f32',
+    'smplfit_share_segments_create', 'smplfit_share_segments_destroy', 'smplfit_share_segments_batch',
+    'smplfit_share_segments_get_table', 'smplfit_share_segments_workspace_bytes', 'smplfit_fit_segments_f32',
+    'smplfit_shape_solve_segments_f32',
 ]  # fmt: skip
 
 _fp = C.POINTER(C.c_float)
@@ -376,6 +379,21 @@ def load():
     lib.smplfit_fit_known_shape_backward_f32.restype = i32
     lib.smplfit_reload_options.argtypes = []
     lib.smplfit_reload_options.restype = i32
+    if hasattr(lib, 'smplfit_share_segments_create'):  # (an older build loaded through SMPLFIT_LIB has none of them)
+        lib.smplfit_share_segments_create.argtypes = [_ip, i32, i32, C.POINTER(vp)]
+        lib.smplfit_share_segments_create.restype = i32
+        lib.smplfit_share_segments_destroy.argtypes = [vp]
+        lib.smplfit_share_segments_destroy.restype = None
+        lib.smplfit_share_segments_batch.argtypes = [vp]
+        lib.smplfit_share_segments_batch.restype = i32
+        lib.smplfit_share_segments_get_table.argtypes = [vp, i32, _ip, sz, C.POINTER(sz)]
+        lib.smplfit_share_segments_get_table.restype = i32
+        lib.smplfit_share_segments_workspace_bytes.argtypes = [vp, i32, vp]
+        lib.smplfit_share_segments_workspace_bytes.restype = sz
+        lib.smplfit_fit_segments_f32.argtypes = [vp, C.POINTER(FitArgs), vp]
+        lib.smplfit_fit_segments_f32.restype = i32
+        lib.smplfit_shape_solve_segments_f32.argtypes = [vp, C.POINTER(ShapeSolveArgs), vp]
+        lib.smplfit_shape_solve_segments_f32.restype = i32
     if os.environ.get('SMPLFIT_LIB') and not hasattr(lib, 'smplfit_abi_version'):
         _lib = lib  # an older build loaded by the A/B tools (tools/ab_fit.py): no version / share-table exports
         return lib
@@ -557,6 +575,49 @@ class Transfer:
         if getattr(self, '_t', None) is not None and self._t.value:
             load().smplfit_transfer_destroy(self._t)
             self._t = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ShareSegments:
+    """Owns a ``smplfit_share_segments*``: the tables of a ``share_beta`` batch cut into consecutive runs of rows
+    (``sizes``), on the current device unless ``host_only``.  Raises ``ValueError`` for sizes the library refuses."""
+
+    TABLES = dict(row_seg=0, seg_blk=1, blk_rows=2)
+
+    def __init__(self, sizes, host_only: bool = False):
+        sz = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1)
+        self._p = C.c_void_p()
+        check(load().smplfit_share_segments_create(sz.ctypes.data_as(_ip), sz.shape[0],
+                                                   SMPLFIT_CREATE_HOST_ONLY if host_only else 0, C.byref(self._p)))
+
+    @property
+    def ptr(self):
+        return self._p
+
+    @property
+    def batch(self) -> int:
+        return int(load().smplfit_share_segments_batch(self._p))
+
+    def table(self, name: str) -> np.ndarray:
+        lib = load()
+        n = C.c_size_t()
+        check(lib.smplfit_share_segments_get_table(self._p, self.TABLES[name], None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        check(lib.smplfit_share_segments_get_table(self._p, self.TABLES[name], out.ctypes.data_as(_ip), n.value, C.byref(n)))
+        return out
+
+    def workspace_bytes(self, h: 'Handle') -> int:
+        return int(load().smplfit_share_segments_workspace_bytes(h.ptr, self.batch, self._p))
+
+    def close(self):
+        if getattr(self, '_p', None) is not None and self._p.value:
+            load().smplfit_share_segments_destroy(self._p)
+            self._p = C.c_void_p()
 
     def __del__(self):
         try:

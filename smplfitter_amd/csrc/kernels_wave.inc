@@ -1254,9 +1254,11 @@ __global__ __launch_bounds__(64) void k_pair_gram(DevModel m, Workspace ws) {
 template <int N, bool GEN = false>
 __global__ __launch_bounds__(GEN ? 1024 : 64) void k_shape_solve(DevModel m, Workspace ws, int B, float beta_reg,
                                                     float beta_reg2, float kid_reg, int pair_form,
-                                                    int use_ref, int mode, int b0, int cen_b0 = 0) {
+                                                    int use_ref, int mode, int b0, int cen_b0 = 0,
+                                                    const int32_t* __restrict__ row_seg = nullptr) {
   // cen_b0: the instance whose system is row 0 of ws.cen (general path: the rows of a share_beta solve are written and
-  // summed chunk by chunk, the workspace holds one chunk of them)
+  // summed chunk by chunk, the workspace holds one chunk of them).  row_seg: mode 2 reads the sum of the instance's own
+  // segment, row row_seg[b] of ws.censum (null: the batch is one segment)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int half = GEN ? 0 : (int)threadIdx.x / N, J = m.J, S = m.S;
   const int b = GEN ? min(b0 + (int)blockIdx.x, B - 1) : min(b0 + (int)blockIdx.x * (64 / N) + half, B - 1);
@@ -1272,7 +1274,7 @@ __global__ __launch_bounds__(GEN ? 1024 : 64) void k_shape_solve(DevModel m, Wor
                   pair_form ? ws.mbj + (size_t)b * J * 3 : nullptr, beta_reg, beta_reg2, kid_reg,
                   ws.beta + (size_t)b * S, ws.trans + (size_t)b * 3, ws.rjoints + (size_t)b * J * 3,
                   ws.jb + (size_t)b * J * 4, use_ref ? ws.regref + (size_t)b * S : nullptr, mode,
-                  mode == 1 ? ws.cen + (size_t)(b - cen_b0) * (S * S + S) : ws.censum,
+                  mode == 1 ? ws.cen + (size_t)(b - cen_b0) * (S * S + S) : ws.censum + (size_t)(row_seg ? row_seg[b] : 0) * (S * S + S),
                   ws.jbT ? ws.jbT + ((size_t)(b >> 6) * J * 4) * 64 + (b & 63) : nullptr,
                   GEN ? reinterpret_cast<double*>(smem) : nullptr);
 }
@@ -1313,6 +1315,7 @@ struct ScaledSolveArgs {
   float beta_reg, beta_reg2, kid_reg, scale_reg;
   int share, B;  // share_beta with a scale unknown: 1 assemble the reduced system, 2 solve the sum
   int b0, cen_b0;  // first instance of the launch; the instance whose reduced system is row 0 of ws.cen (see k_shape_solve)
+  const int32_t* row_seg;  // share 2: the segment of an instance, its row of ws.censum (null: one segment)
 };
 
 // GEN (general path): the scratch in global memory (ws.gsolve), the panel of ldlt_solve in LDS, the extra sums from the
@@ -1334,7 +1337,8 @@ __global__ __launch_bounds__(GEN ? 1024 : 64) void k_shape_solve_scaled(DevModel
                          a.use_ref ? ws.regref + (size_t)b * S : nullptr, ws.beta_out + (size_t)b * S,
                          ws.beta + (size_t)b * S, ws.trans + (size_t)b * 3, ws.scale + b,
                          ws.rjoints + (size_t)b * J * 3, ws.jb + (size_t)b * J * 4, a.share,
-                         a.share == 1 ? ws.cen + (size_t)(b - a.cen_b0) * (S * S + S) : ws.censum,
+                         a.share == 1 ? ws.cen + (size_t)(b - a.cen_b0) * (S * S + S)
+                                      : ws.censum + (size_t)(a.row_seg ? a.row_seg[b] : 0) * (S * S + S),
                          GEN ? reinterpret_cast<double*>(smem) : nullptr,
                          GEN ? ws.gvex + (size_t)b * (S + sf::kScaleExtras) : nullptr);
   // the instance-innermost copy of the skinning translations for the batch-major LBS pass that may follow
@@ -1383,33 +1387,36 @@ __global__ __launch_bounds__(64) void k_scale_refs(DevModel m, Workspace ws, con
   if (lane < 3) ws.mean[b * 3 + lane] = mode == 1 ? ws.mean[b * 3 + lane] * s : ws.mean[b * 3 + lane] / s;
 }
 
-// share_beta: sum of the per-instance systems over the batch (deterministic: a fixed two-level order that depends on
-// B alone).  k_share_partial: grid ceil(B/64), thread = entry of the (S*S + S) record: the sum of 64 consecutive
-// instances, eight interleaved accumulators (eight loads in flight; one workgroup walking all B rows, as in rounds
-// 1-3, took 270 us per solve at B = 4096: a latency-bound chain of 1024 dependent rounds); k_share_reduce: one
-// workgroup adds the partial sums the same way; the sum lands in row B of ws.cen.
-__device__ __forceinline__ double sum_rows_f64(const double* __restrict__ p, int n, size_t stride) {
-  double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int i = 0;
-  for (; i + 8 <= n; i += 8) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) a[u] += p[(size_t)(i + u) * stride];
-  }
-  for (int u = 0; i < n; ++i, ++u) a[u] += p[(size_t)i * stride];
-  return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+// share_beta: the sums of the per-instance systems over the SEGMENTS of the batch — consecutive runs of rows, one shared
+// shape per run (sf::ShareSegments; the batch as one run without a plan).  Deterministic: a fixed two-level order that
+// depends on the run sizes alone.  k_share_partial: a workgroup per PARTIAL BLOCK (64 consecutive rows counted from the
+// run's first row), thread = entry of the (S*S + S) record: the sum of the block's rows, eight interleaved accumulators
+// (sf::sum_rows_f64: eight loads in flight; one workgroup walking all B rows, as in rounds 1-3, took 270 us per solve at
+// B = 4096: a latency-bound chain of 1024 dependent rounds); k_share_reduce: one workgroup per run adds the run's partial
+// rows the same way into the run's row of ws.censum.
+// The tables of a plan on the device, all null for the single run [B]: a block is then (64 p, min(64, B - 64 p)), the one
+// run holds every block, every row belongs to run 0.
+struct ShareSegs {
+  const int32_t* row_seg;   // (B)
+  const int32_t* seg_blk;   // (runs, 2) first partial block, blocks
+  const int32_t* blk_rows;  // (blocks, 2) first row, rows
+  int nseg, nblk;
+};
+// grid (blocks of this launch, ceil(NC / 512)); p0: the first partial block of the launch; cen_b0: the instance whose
+// system is row 0 of ws.cen (general path: the workspace holds the rows of one group of blocks).
+__global__ __launch_bounds__(512) void k_share_partial(Workspace ws, ShareSegs sg, int B, int NC, int p0, int cen_b0) {
+  const int e = blockIdx.y * 512 + threadIdx.x, p = p0 + blockIdx.x;
+  if (e >= NC || p >= sg.nblk) return;
+  const int r0 = sg.blk_rows ? sg.blk_rows[2 * p] : 64 * p;
+  const int n = sg.blk_rows ? sg.blk_rows[2 * p + 1] : min(64, B - r0);
+  ws.cenP[(size_t)p * NC + e] = sf::sum_rows_f64(ws.cen + (size_t)(r0 - cen_b0) * NC + e, n, (size_t)NC);
 }
-// nrows: the rows of ws.cen to sum (a chunk of the batch on the general path, the batch otherwise); p0: the partial
-// row of the chunk's first 64 instances.  grid (ceil(nrows / 64), ceil(NC / 512)).
-__global__ __launch_bounds__(512) void k_share_partial(Workspace ws, int nrows, int NC, int p0) {
-  const int e = blockIdx.y * 512 + threadIdx.x, r0 = blockIdx.x * 64;
-  if (e >= NC) return;
-  ws.cenP[(size_t)(p0 + blockIdx.x) * NC + e] = sum_rows_f64(ws.cen + (size_t)r0 * NC + e, min(64, nrows - r0), (size_t)NC);
-}
-// grid ceil(NC / 512): the sum of the nparts partial rows into ws.censum
-__global__ __launch_bounds__(512) void k_share_reduce(Workspace ws, int nparts, int NC) {
-  const int e = blockIdx.x * 512 + threadIdx.x;
-  if (e >= NC) return;
-  ws.censum[e] = sum_rows_f64(ws.cenP + e, nparts, (size_t)NC);
+// grid (runs, ceil(NC / 512)): the sum of a run's partial rows into its row of ws.censum
+__global__ __launch_bounds__(512) void k_share_reduce(Workspace ws, ShareSegs sg, int NC) {
+  const int e = blockIdx.y * 512 + threadIdx.x, g = blockIdx.x;
+  if (e >= NC || g >= sg.nseg) return;
+  const int pf = sg.seg_blk ? sg.seg_blk[2 * g] : 0, np = sg.seg_blk ? sg.seg_blk[2 * g + 1] : sg.nblk;
+  ws.censum[(size_t)g * NC + e] = sf::sum_rows_f64(ws.cenP + (size_t)pf * NC + e, np, (size_t)NC);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 // structure (reference src/smplfitter/pt/rotation.py).  All matrices are row-major float[9].
 #pragma once
 #include <math.h>
+#include <stddef.h>
 
 #if defined(__HIPCC__)
 #define SF_HD __host__ __device__ __forceinline__
@@ -27,6 +28,20 @@
 #endif
 
 namespace sf {
+
+// The sum of n doubles `stride` apart, in the one order every share_beta sum uses (k_share_partial / k_share_reduce and
+// their host emulation): eight interleaved accumulators (eight loads in flight on the device), the first n / 8 * 8
+// elements dealt to them in turn, the tail to the first n % 8, then a fixed tree over the eight.
+SF_HD double sum_rows_f64(const double* __restrict__ p, int n, size_t stride) {
+  double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int i = 0;
+  for (; i + 8 <= n; i += 8) {
+    SF_UNROLL_FULL
+    for (int u = 0; u < 8; ++u) a[u] += p[(size_t)(i + u) * stride];
+  }
+  for (int u = 0; i < n; ++i, ++u) a[u] += p[(size_t)i * stride];
+  return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+}
 
 // a / b, 0 where b == 0 (rotation.py:8-11)
 SF_HD float divide_no_nan(float a, float b) { return b == 0.f ? 0.f : a / b; }

@@ -967,4 +967,31 @@ void transpose_csr(int rows, int cols, const std::vector<int32_t>& indptr, const
     }
 }
 
+std::string build_share_segments(const int32_t* sizes, int count, ShareSegments& s) {
+  s = ShareSegments();
+  if (!sizes || count < 1) return "at least one segment is required";
+  int64_t total = 0;
+  for (int g = 0; g < count; ++g) {
+    if (sizes[g] < 1) return "segment " + std::to_string(g) + " has size " + std::to_string(sizes[g]) + ": sizes must be >= 1";
+    total += sizes[g];
+    if (total > INT32_MAX) return "the segment sizes sum to more than INT32_MAX rows";
+  }
+  s.batch = (int)total;
+  s.row_seg.reserve((size_t)total);
+  s.seg_blk.reserve((size_t)count * 2);
+  int32_t row = 0;
+  for (int g = 0; g < count; ++g) {
+    const int32_t n = sizes[g], nb = (n + kShareBlock - 1) / kShareBlock;
+    s.seg_blk.push_back(s.nblk());
+    s.seg_blk.push_back(nb);
+    for (int32_t k = 0; k < nb; ++k) {
+      s.blk_rows.push_back(row + k * kShareBlock);
+      s.blk_rows.push_back(std::min(kShareBlock, n - k * kShareBlock));
+    }
+    s.row_seg.insert(s.row_seg.end(), (size_t)n, g);
+    row += n;
+  }
+  return "";
+}
+
 }  // namespace sf

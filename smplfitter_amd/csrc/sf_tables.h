@@ -281,6 +281,22 @@ void transpose_csr(int rows, int cols, const std::vector<int32_t>& indptr, const
                    const std::vector<float>& values, std::vector<int32_t>& t_indptr, std::vector<int32_t>& t_indices,
                    std::vector<float>& t_values);
 
+// Segments of a share_beta batch (smplfit_share_segments): consecutive runs of rows, one shared shape per run.  The sum
+// of a run's systems is two-level, as the whole batch's has always been: PARTIAL BLOCKS of kShareBlock consecutive rows
+// counted from the run's first row (the last one takes the remainder), then the run's partial rows.  The blocks of all
+// runs are numbered in row order, so they tile [0, batch) without gap or overlap.
+constexpr int kShareBlock = 64;
+struct ShareSegments {
+  int batch = 0;
+  std::vector<int32_t> row_seg;   // (batch)   the run of a row
+  std::vector<int32_t> seg_blk;   // (runs, 2) first partial block, number of blocks = ceil(size / kShareBlock)
+  std::vector<int32_t> blk_rows;  // (blocks, 2) first row, rows (1 .. kShareBlock)
+  int nseg() const { return (int)seg_blk.size() / 2; }
+  int nblk() const { return (int)blk_rows.size() / 2; }
+};
+// Returns "" on success, else what is wrong with the sizes (count < 1, a size < 1, a sum beyond INT32_MAX).
+std::string build_share_segments(const int32_t* sizes, int count, ShareSegments& s);
+
 // (n, 3) start, count, part
 inline std::vector<int32_t> flatten(const std::vector<Segment>& segs) {
   std::vector<int32_t> out;

@@ -202,6 +202,15 @@ struct smplfit_replace_hands_plan {
   DeviceArrays dev;
 };
 
+// Segments of a share_beta batch (smplfit_fit_segments_f32 / smplfit_shape_solve_segments_f32): the tables of
+// sf::build_share_segments on the host and, unless the plan is host-only, on the device.
+struct smplfit_share_segments {
+  sf::ShareSegments t;
+  int32_t *d_row_seg = nullptr, *d_seg_blk = nullptr, *d_blk_rows = nullptr;
+  DeviceArrays dev;
+  bool has_device = false;
+};
+
 namespace {
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -282,8 +291,10 @@ struct Workspace {
   float* scale;    // (B) scale_corr of the known-shape fit
   float* regref;   // (B,S) ridge reference of the warm-started fit
   double* cen;     // (B, S*S+S) centred regularised systems of a share_beta fit (general path: one chunk of share_chunk() rows)
-  double* cenP;    // (ceil(B/64), S*S+S) partial sums of the rows above (k_share_partial)
-  double* censum;  // (S*S+S) their sum (row B of cen; general path: a row of its own)
+  double* cenP;    // (partial blocks, S*S+S) partial sums of the rows above (k_share_partial); ceil(B/64) rows here,
+                   // a plan of segments brings its own (segments_layout)
+  double* censum;  // (segments, S*S+S) their sums per segment; one row here (row B of cen; general path: a row of its
+                   // own), a plan of segments brings its own
   double* gvex;    // (B, S+6) general path: extra sums of the scaled solve (target column of k_gen_accum_mfma)
   float* vextra;   // (B,32) extra vertex sums of the scaled solve (scale_extras_vertex)
   float* beta_out; // (B,S) undivided shape of the scaled solve (ws.beta holds the evaluated one)
@@ -1099,22 +1110,22 @@ void launch_refine(const DevModel& d, RefineArgs ra, const Workspace& ws, int B,
 // other paths always launch the whole batch
 void launch_shape_solve(const DevModel& d, const Workspace& ws, int B, hipStream_t st, float beta_reg, float beta_reg2,
                         float kid_reg, int pair_form, int use_ref, int mode = 0, int first = 0, int count = -1,
-                        int cen_b0 = 0) {
+                        int cen_b0 = 0, const int32_t* row_seg = nullptr) {
   if (count < 0) count = B;
   if (d.general) {
     ensure_max_lds(reinterpret_cast<const void*>(&k_shape_solve<64, true>));
     hipLaunchKernelGGL((k_shape_solve<64, true>), dim3(count), dim3(d.S > 128 ? 1024 : d.S > 64 ? 256 : 64), solve_lds(d), st, d,
-                       ws, B, beta_reg, beta_reg2, kid_reg, pair_form, use_ref, mode, first, cen_b0);
+                       ws, B, beta_reg, beta_reg2, kid_reg, pair_form, use_ref, mode, first, cen_b0, row_seg);
   } else if (stage_half(d, 2, B)) {
     if (B / 2 > 0)
       hipLaunchKernelGGL(k_shape_solve<32>, dim3(B / 2), dim3(64), 2 * solve_lds(d), st, d, ws, B, beta_reg,
-                         beta_reg2, kid_reg, pair_form, use_ref, mode, 0, 0);
+                         beta_reg2, kid_reg, pair_form, use_ref, mode, 0, 0, row_seg);
     if (B & 1)
       hipLaunchKernelGGL(k_shape_solve<64>, dim3(1), dim3(64), solve_lds(d), st, d, ws, B, beta_reg, beta_reg2,
-                         kid_reg, pair_form, use_ref, mode, B - 1, 0);
+                         kid_reg, pair_form, use_ref, mode, B - 1, 0, row_seg);
   } else {
     hipLaunchKernelGGL(k_shape_solve<64>, dim3(B), dim3(64), solve_lds(d), st, d, ws, B, beta_reg, beta_reg2,
-                       kid_reg, pair_form, use_ref, mode, 0, 0);
+                       kid_reg, pair_form, use_ref, mode, 0, 0, row_seg);
   }
 }
 
@@ -1609,6 +1620,7 @@ struct FitOptions {
   int share_beta = 0;                 // one shape for the whole batch (pt/lstsq.py:24-26)
   smplfit_share_allreduce_fn share_allreduce = nullptr;  // completes the sum over the ranks of a sharded batch
   void* share_user = nullptr;
+  const smplfit_share_segments* segments = nullptr;  // share_beta: one shape per segment of the batch (null: one segment)
   int scale_mode = 0;                 // 1 scale_target, 2 scale_fit: the last solve has a scale unknown
   float scale_reg = 0.f;
 };
@@ -1627,20 +1639,33 @@ FitOptions fit_options(const smplfit_fit_args& a, bool rotations_only) {
 // scaled solve (one more unknown; extra vertex sums first) or the shared solve (assemble, sum over the
 // batch [and the ranks], solve the sum).  The all-shared branch of the reference's lstsq_partial_share
 // drops the ridge reference (pt/lstsq.py:45-47): so does this.
-// the sum of the instances' systems of a share_beta solve into ws.censum: `assemble(first, count, cen_b0)` launches the
-// kernel that writes the systems of the instances [first, first + count) to the rows [first - cen_b0, ...) of ws.cen.
-// The partial sums are those of 64 consecutive instances whatever the chunking (general path: the workspace holds
-// share_chunk(B) rows), so the sum does not depend on it.
+// the sums of the instances' systems of a share_beta solve, one per segment of the batch, into the rows of ws.censum:
+// `assemble(first, count, cen_b0)` launches the kernel that writes the systems of the instances [first, first + count)
+// to the rows [first - cen_b0, ...) of ws.cen.  The partial sums are those of the segments' blocks (sf::ShareSegments;
+// without a plan the blocks of the single segment [B]) whatever the grouping of the launches — the general path, whose
+// workspace holds share_chunk(B) rows, walks the block list in groups of whole blocks that fit them — so the sums
+// depend on the segment sizes alone.
+ShareSegs share_segs(const smplfit_share_segments* p, int B) {
+  if (p) return {p->d_row_seg, p->d_seg_blk, p->d_blk_rows, p->t.nseg(), p->t.nblk()};
+  return {nullptr, nullptr, nullptr, 1, (B + sf::kShareBlock - 1) / sf::kShareBlock};
+}
 template <class Assemble>
 int share_sum(const DevModel& d, const Workspace& ws, int B, const FitOptions& o, hipStream_t st, Assemble assemble) {
   const int NC = d.S * d.S + d.S, ey = (NC + 511) / 512;
-  const int chunk = d.general ? share_chunk(B) : B;
-  for (int c0 = 0; c0 < B; c0 += chunk) {
-    const int cnt = std::min(chunk, B - c0);
-    assemble(c0, cnt, d.general ? c0 : 0);
-    hipLaunchKernelGGL(k_share_partial, dim3((cnt + 63) / 64, ey), dim3(512), 0, st, ws, cnt, NC, c0 / 64);
+  const ShareSegs sg = share_segs(o.segments, B);
+  const int room = d.general ? share_chunk(B) : B;  // rows of ws.cen (>= one block)
+  const auto rows_of = [&](int p) {
+    return o.segments ? o.segments->t.blk_rows[2 * p + 1] : std::min(sf::kShareBlock, B - p * sf::kShareBlock);
+  };
+  for (int p0 = 0, first = 0; p0 < sg.nblk;) {
+    int p1 = p0, cnt = 0;
+    while (p1 < sg.nblk && cnt + rows_of(p1) <= room) cnt += rows_of(p1++);
+    assemble(first, cnt, d.general ? first : 0);
+    hipLaunchKernelGGL(k_share_partial, dim3(p1 - p0, ey), dim3(512), 0, st, ws, sg, B, NC, p0, d.general ? first : 0);
+    p0 = p1;
+    first += cnt;
   }
-  hipLaunchKernelGGL(k_share_reduce, dim3(ey), dim3(512), 0, st, ws, (B + 63) / 64, NC);
+  hipLaunchKernelGGL(k_share_reduce, dim3(sg.nseg, ey), dim3(512), 0, st, ws, sg, NC);
   if (o.share_allreduce && o.share_allreduce(o.share_user, ws.censum, NC, (void*)st) != 0)
     return fail(SMPLFIT_ERR_HIP, "the share_allreduce callback failed");
   return 0;
@@ -1688,6 +1713,7 @@ int enqueue_solve(const smplfit_handle* h, const Route& r, const Workspace& ws, 
       }
     };
     if (o.share_beta) {  // shared shape, own scale: reduced systems, their sum, solve (pt/lstsq.py:50-90)
+      sa.row_seg = o.segments ? o.segments->d_row_seg : nullptr;
       sa.share = 1;
       if (int rc = share_sum(d, ws, B, o, st, launch)) return rc;
       sa.share = 2;
@@ -1698,7 +1724,8 @@ int enqueue_solve(const smplfit_handle* h, const Route& r, const Workspace& ws, 
       launch_shape_solve(d, ws, B, st, o.beta_reg, o.beta_reg2, o.kid_reg, pair_in, 0, 1, first, count, cen_b0);
     };
     if (int rc = share_sum(d, ws, B, o, st, assemble)) return rc;
-    launch_shape_solve(d, ws, B, st, o.beta_reg, o.beta_reg2, o.kid_reg, pair_in, 0, 2);
+    launch_shape_solve(d, ws, B, st, o.beta_reg, o.beta_reg2, o.kid_reg, pair_in, 0, 2, 0, -1, 0,
+                       o.segments ? o.segments->d_row_seg : nullptr);
   } else if (r.solve_bm) {
     launch_solve_bm(h, r.solve_plan, ws, B, st, o.beta_reg, o.beta_reg2, o.kid_reg, use_ref, r.prologue_bm);
   } else {
@@ -1712,7 +1739,8 @@ int enqueue_solve(const smplfit_handle* h, const Route& r, const Workspace& ws, 
 // of the input model on the batch-major kernels, topology transfer straight into this fit's target stream — instead
 // of being read from target_vertices).
 int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_only, const ConvertSource* source,
-            const Workspace& ws, hipStream_t st, int ph_lo = 0, int ph_hi = 1 << 30, bool vw_shared = false) {
+            const Workspace& ws, hipStream_t st, int ph_lo = 0, int ph_hi = 1 << 30, bool vw_shared = false,
+            const smplfit_share_segments* segments = nullptr) {
   // PHASES.  The launches of a fit are numbered in phases — 0: the prologue up to the first rotation pass; 1 + 2 it:
   // the vertex block of iteration `it` up to the normal equations; 2 + 2 it: solve, vertices at the solution, next
   // rotation pass; 1 + 2 num_iter: refinement and epilogue — and a call enqueues the phases [ph_lo, ph_hi) only (the
@@ -1725,7 +1753,8 @@ int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_o
   const bool joints = tj != nullptr;
   const bool vweighted = vw != nullptr;
   const SolveWeights w = solve_weights(joints, vw, jw);
-  const FitOptions o = fit_options(a, rotations_only);
+  FitOptions o = fit_options(a, rotations_only);
+  o.segments = segments;  // (fit_impl has set a.share_beta)
   // warm start (bodyfitter.py:363-382): the first rotation pass runs against the model posed with the initial values
   // instead of the template — only when a pose or a shape is given —; the ridge references reach EVERY shape solve
   // whenever they are given — also an initial_kid_factor on its own (:413-414, :448-449)
@@ -1993,10 +2022,48 @@ smplfit_fit_args chunk_view(const smplfit_fit_args& a, const sf::HostTables& t, 
   return v;
 }
 
+// LAYOUT segments: behind the workspace of a call with a plan of segments (its own query's size), the plan's partial
+// rows and per-segment sums; point_segments hands them to the call's Workspace in place of the single segment's
+struct SegmentsLayout {
+  double *cenP, *censum;
+};
+SegmentsLayout segments_layout(const sf::HostTables& t, const smplfit_share_segments& p, Arena& ar) {
+  const size_t NC = (size_t)t.S * t.S + t.S;
+  SegmentsLayout l{};
+  l.cenP = ar.take<double>((size_t)p.t.nblk() * NC);
+  l.censum = ar.take<double>((size_t)p.t.nseg() * NC);
+  return l;
+}
+size_t segments_workspace_bytes(const smplfit_handle* h, const smplfit_share_segments& p) {
+  Arena ar{nullptr};
+  ar.take<char>(chunked_workspace_bytes(h->t, p.t.batch));
+  segments_layout(h->t, p, ar);
+  return ar.off;
+}
+Workspace point_segments(Workspace ws, const smplfit_handle* h, const smplfit_share_segments& p, void* workspace) {
+  Arena ar{(char*)workspace};
+  ar.take<char>(chunked_workspace_bytes(h->t, p.t.batch));
+  const SegmentsLayout l = segments_layout(h->t, p, ar);
+  ws.cenP = l.cenP;
+  ws.censum = l.censum;
+  return ws;
+}
+// What the two entry points with a plan of segments check before anything else (NULL plan: nothing)
+int check_segments(const char* who, const smplfit_share_segments* p, int batch, smplfit_share_allreduce_fn share_allreduce) {
+  if (!p) return 0;
+  if (batch != p->t.batch)
+    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": batch " + std::to_string(batch) + " is not the plan's " + std::to_string(p->t.batch));
+  if (share_allreduce) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": share_allreduce cannot be combined with segments");
+  if (!p->has_device) return fail(SMPLFIT_ERR_HIP, std::string(who) + ": the plan of segments is host-only");
+  return 0;
+}
+
 // vw_shared: args->vertex_weights is one (V) row for the whole batch (smplfit_replace_hands_f32).  The entry has run
 // check_call against its own query, which holds chunked_workspace_bytes from a.workspace on: a.workspace_bytes is not
 // read here.
-int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const ConvertJob* job, bool vw_shared = false) {
+// segments: the plan of smplfit_fit_segments_f32 (a.share_beta set; a.workspace holds segments_workspace_bytes).
+int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const ConvertJob* job, bool vw_shared = false,
+             const smplfit_share_segments* segments = nullptr) {
   const smplfit_fit_args& a = *args;
   const int batch = a.batch;
   int rc = 0;
@@ -2038,7 +2105,9 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
     }
     smplfit_fit_args v = chunk_view(a, h->t, b0, nb);
     if (vw_shared) v.vertex_weights = a.vertex_weights;  // (every chunk reads the one row)
-    return run_fit(h, v, false, job ? &src : nullptr, lay[c].ws, cs, ph_lo, ph_hi, vw_shared);
+    // (a plan of segments: share_beta, so the one chunk)
+    const Workspace ws = segments ? point_segments(lay[c].ws, h, *segments, a.workspace) : lay[c].ws;
+    return run_fit(h, v, false, job ? &src : nullptr, ws, cs, ph_lo, ph_hi, vw_shared, segments);
   };
   if (nchunk <= 1) return run_chunk(0, st, 0, 1 << 30);
   // fork: every chunk is an independent fit with its own workspace slice; chunk 0 stays on the
@@ -2982,6 +3051,52 @@ size_t smplfit_workspace_bytes(const smplfit_handle* h, int batch) {
   return chunked_workspace_bytes(h->t, batch);
 }
 
+// ---- segments of a share_beta batch -----------------------------------------------------------------
+int smplfit_share_segments_create(const int32_t* sizes, int32_t count, int32_t flags, smplfit_share_segments** out) {
+  if (!sizes || !out) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_share_segments_create: null argument");
+  *out = nullptr;
+  auto* p = new smplfit_share_segments();
+  const std::string err = sf::build_share_segments(sizes, count, p->t);
+  if (!err.empty()) {
+    delete p;
+    return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_share_segments_create: " + err);
+  }
+  if (!(flags & SMPLFIT_CREATE_HOST_ONLY)) {
+    if (p->dev.upload(p->t.row_seg, &p->d_row_seg) || p->dev.upload(p->t.seg_blk, &p->d_seg_blk) ||
+        p->dev.upload(p->t.blk_rows, &p->d_blk_rows)) {
+      smplfit_share_segments_destroy(p);
+      return fail(SMPLFIT_ERR_HIP, "smplfit_share_segments_create: device upload failed");
+    }
+    p->has_device = true;
+  }
+  *out = p;
+  return SMPLFIT_OK;
+}
+
+void smplfit_share_segments_destroy(smplfit_share_segments* p) {
+  if (!p) return;
+  p->dev.free_all();
+  delete p;
+}
+
+int32_t smplfit_share_segments_batch(const smplfit_share_segments* p) { return p ? p->t.batch : 0; }
+
+int smplfit_share_segments_get_table(const smplfit_share_segments* p, int what, int32_t* dst, size_t cap, size_t* n) {
+  if (!p || !n) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_share_segments_get_table: null argument");
+  const std::vector<int32_t>* const tabs[] = {&p->t.row_seg, &p->t.seg_blk, &p->t.blk_rows};
+  if (what < 0 || what > 2) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_share_segments_get_table: unknown table");
+  const std::vector<int32_t>* src = tabs[what];
+  *n = src->size();
+  if (dst && !src->empty()) std::memcpy(dst, src->data(), std::min(cap, src->size()) * sizeof(int32_t));
+  return SMPLFIT_OK;
+}
+
+size_t smplfit_share_segments_workspace_bytes(const smplfit_handle* h, int batch, const smplfit_share_segments* p) {
+  if (!p) return smplfit_workspace_bytes(h, batch);
+  if (!h || batch <= 0 || batch != p->t.batch) return 0;
+  return segments_workspace_bytes(h, *p);
+}
+
 int smplfit_fit_f32(const smplfit_handle* h, const float* target_vertices,
                     const float* target_joints, const float* vertex_weights,
                     const float* joint_weights, int batch, int num_iter, float beta_regularizer,
@@ -3019,12 +3134,19 @@ int smplfit_fit_warm_f32(const smplfit_handle* h, const float* target_vertices,
   return smplfit_fit_ex_f32(h, &a);
 }
 
-int smplfit_fit_ex_f32(const smplfit_handle* h, const smplfit_fit_args* args) {
+int smplfit_fit_ex_f32(const smplfit_handle* h, const smplfit_fit_args* args) { return smplfit_fit_segments_f32(h, args, nullptr); }
+
+int smplfit_fit_segments_f32(const smplfit_handle* h, const smplfit_fit_args* args, const smplfit_share_segments* segments) {
   if (!args) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_fit_ex_f32: null arguments");
+  if (int rc = check_segments("smplfit_fit_segments_f32", segments, args->batch, args->share_allreduce)) return rc;
   if (int rc = check_call("smplfit_fit_f32", h, args->batch, args->workspace, args->workspace_bytes,
-                          smplfit_workspace_bytes(h, args->batch), "smplfit_workspace_bytes"))
+                          smplfit_share_segments_workspace_bytes(h, args->batch, segments),
+                          segments ? "smplfit_share_segments_workspace_bytes" : "smplfit_workspace_bytes"))
     return rc;
-  return fit_impl(h, args, nullptr);
+  if (!segments) return fit_impl(h, args, nullptr);
+  smplfit_fit_args a = *args;
+  a.share_beta = 1;  // segments imply shared shapes within them
+  return fit_impl(h, &a, nullptr, false, segments);
 }
 
 int smplfit_fit_known_shape_f32(const smplfit_handle* h, const float* shape_betas,
@@ -3175,10 +3297,21 @@ int smplfit_shape_solve_f32(const smplfit_handle* h, const float* glob_rotmats,
 }
 
 int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solve_args* args) {
-  if (!args) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_shape_solve_ex_f32: null arguments");
+  return smplfit_shape_solve_segments_f32(h, args, nullptr);
+}
+
+int smplfit_shape_solve_segments_f32(const smplfit_handle* h, const smplfit_shape_solve_args* args_in,
+                                     const smplfit_share_segments* segments) {
+  if (!args_in) return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_shape_solve_ex_f32: null arguments");
+  smplfit_shape_solve_args with_share = *args_in;
+  if (segments) with_share.share_beta = 1;  // segments imply shared shapes within them
+  const smplfit_shape_solve_args* args = &with_share;
   const int batch = args->batch;
-  int rc = check_call("smplfit_shape_solve_f32", h, batch, args->workspace, args->workspace_bytes, smplfit_workspace_bytes(h, batch),
-                      "smplfit_workspace_bytes");
+  int rc = check_segments("smplfit_shape_solve_segments_f32", segments, batch, args->share_allreduce);
+  if (rc) return rc;
+  rc = check_call("smplfit_shape_solve_f32", h, batch, args->workspace, args->workspace_bytes,
+                  smplfit_share_segments_workspace_bytes(h, batch, segments),
+                  segments ? "smplfit_share_segments_workspace_bytes" : "smplfit_workspace_bytes");
   if (rc) return rc;
   if (!args->glob_rotmats || !args->target_vertices || !args->shape_betas || !args->trans)
     return fail(SMPLFIT_ERR_BAD_ARG, "smplfit_shape_solve_f32: null pointer");
@@ -3194,11 +3327,13 @@ int smplfit_shape_solve_ex_f32(const smplfit_handle* h, const smplfit_shape_solv
   const DevModel& d = h->d;
   const float *vertex_weights = args->vertex_weights, *joint_weights = args->joint_weights;
   hipStream_t st = (hipStream_t)args->hip_stream;
-  const Workspace ws = fit_workspace(h, batch, args->workspace);
+  const Workspace ws = segments ? point_segments(fit_workspace(h, batch, args->workspace), h, *segments, args->workspace)
+                                : fit_workspace(h, batch, args->workspace);
   const bool joints = args->target_joints != nullptr;
   const SolveWeights w = solve_weights(joints, vertex_weights, joint_weights);
   FitOptions o{1, args->beta_regularizer, args->beta_regularizer2, args->kid_regularizer, 0, 0};
   o.share_beta = args->share_beta ? 1 : 0;
+  o.segments = segments;
   o.share_allreduce = args->share_allreduce;
   o.share_user = args->share_user;
   o.scale_mode = args->scale_mode;

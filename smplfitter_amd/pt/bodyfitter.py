@@ -7,6 +7,7 @@ kernels behind ``smplfit_fit_f32``, and its gradients with respect to the target
 
 from __future__ import annotations
 
+import collections
 import ctypes as C
 from typing import Optional
 
@@ -46,6 +47,20 @@ def _share_callback(ws: torch.Tensor, group):
     return _lib.ShareAllreduceFn(allreduce_sums), failure
 
 
+def _segment_sizes(segments, batch: int) -> tuple:
+    """``share_beta_segments`` as a tuple of ints, checked on the host: positive sizes that sum to the batch."""
+    if isinstance(segments, torch.Tensor):
+        if segments.device.type != 'cpu' or segments.is_floating_point() or segments.is_complex() or segments.dtype == torch.bool:
+            raise ValueError('share_beta_segments must be a sequence of ints or a CPU integer tensor')
+        segments = segments.reshape(-1).tolist()
+    sizes = tuple(int(n) for n in segments)
+    if any(n < 1 for n in sizes):
+        raise ValueError(f'share_beta_segments: every segment needs at least one row, got {list(sizes)}')
+    if sum(sizes) != batch:
+        raise ValueError(f'share_beta_segments sum to {sum(sizes)}, the batch has {batch} rows')
+    return sizes
+
+
 class BodyFitter(nn.Module):
     """Fits SMPL-family parameters (pose, shape, translation) to target vertices (and joints).
 
@@ -66,6 +81,39 @@ class BodyFitter(nn.Module):
         self._torchfit = None  # tables of the differentiable restatement (pt/_autograd.py), built on first use
         self._torchfit64 = None  # the same in fp64 (fit_with_known_shape's PyTorch route)
         self.is_smpl_family = body_model.model_name.startswith('smpl')
+        # (device index, segment sizes) -> _lib.ShareSegments, least recently used first; bounded: the track layout of
+        # a caller changes from call to call
+        self._segment_plans = collections.OrderedDict()
+
+    MAX_SEGMENT_PLANS = 16
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['_segment_plans'] = collections.OrderedDict()
+        return state
+
+    def __deepcopy__(self, memo):
+        import copy
+
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = collections.OrderedDict() if k == '_segment_plans' else copy.deepcopy(v, memo)
+        return new
+
+    def _segment_plan(self, device: torch.device, sizes: tuple) -> _lib.ShareSegments:
+        """The native tables of a layout of segments on ``device`` (``smplfit_share_segments_create``), cached."""
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        key = (idx, sizes)
+        plan = self._segment_plans.pop(key, None)
+        if plan is None:
+            with torch.cuda.device(device):
+                plan = _lib.ShareSegments(sizes)
+            while len(self._segment_plans) >= self.MAX_SEGMENT_PLANS:
+                # (its device tables go with the last reference: hipFree waits for the work that reads them)
+                self._segment_plans.popitem(last=False)
+        self._segment_plans[key] = plan
+        return plan
 
     def fit(
         self,
@@ -88,6 +136,7 @@ class BodyFitter(nn.Module):
         requested_keys: Optional[list[str]] = None,
         _workspace: Optional[torch.Tensor] = None,
         share_beta_group=None,
+        share_beta_segments=None,
     ) -> dict[str, torch.Tensor]:
         """Same arguments and returned keys as the reference's ``fit`` (pt/bodyfitter.py:283-549):
         ``shape_betas, trans, orientations, relative_orientations`` and ``pose_rotvecs`` when
@@ -97,9 +146,25 @@ class BodyFitter(nn.Module):
         ``share_beta_group`` (not in the reference): a ``torch.distributed`` process group over which
         a ``share_beta`` batch is sharded, one block of instances per rank — the summed normal
         equations of every shape solve are all-reduced over it, so all ranks get the shape of the
-        WHOLE batch (``smplfitter_amd.dist.fit_sharded`` passes it)."""
+        WHOLE batch (``smplfitter_amd.dist.fit_sharded`` passes it).
+
+        ``share_beta_segments`` (not in the reference): the sizes of consecutive runs of rows — a sequence of ints or
+        a CPU integer tensor, positive, summing to the batch — for many tracks in one call: every run gets one shape
+        (and one kid factor), and its rows are bit for bit those of ``fit(rows of the run, share_beta=True)`` with the
+        same options (to the bit while the batch and the run take the same cell tables — both up to 768
+        rows or both above —, to rounding otherwise).  Implies ``share_beta``; not with ``share_beta_group``, gradients or
+        ``torch.compile``."""
         if requested_keys is None:
             requested_keys = ['pose_rotvecs']
+        segments = None
+        if share_beta_segments is not None:
+            if share_beta_group is not None:
+                raise ValueError('share_beta_segments cannot be combined with share_beta_group')
+            segments = _segment_sizes(share_beta_segments, target_vertices.shape[0])
+            if torch.compiler.is_compiling():
+                raise NotImplementedError('share_beta_segments cannot be traced (the smplfitter_amd::fit operator has no '
+                                          'argument for them); call the fit outside the compiled region')
+            share_beta = True
         if scale_target and scale_fit:  # same check, same message as pt/bodyfitter.py:858-859
             raise ValueError('Only one of estim_scale_target and estim_scale_fit can be True')
         scale_mode = 1 if scale_target else 2 if scale_fit else 0
@@ -154,7 +219,7 @@ class BodyFitter(nn.Module):
                                       num_iter, beta_regularizer, beta_regularizer2, kid_reg,
                                       final_adjust_rots, initial_pose_rotvecs, initial_shape_betas,
                                       initial_kid_factor, _workspace, share_beta, scale_mode,
-                                      scale_regularizer, share_beta_group)
+                                      scale_regularizer, share_beta_group, segments)
         # relative_orientations = parent^T @ global of the FINAL rotations (pt/bodyfitter.py:523-533);
         # returned always (the reference returns the pre-refinement ones when neither
         # 'relative_orientations' nor 'pose_rotvecs' is requested)
@@ -181,9 +246,9 @@ class BodyFitter(nn.Module):
     def _fit_direct(self, target_vertices, target_joints, vertex_weights, joint_weights, num_iter,
                     beta_regularizer, beta_regularizer2, kid_reg, final_adjust_rots,
                     initial_pose_rotvecs, initial_shape_betas, initial_kid_factor, _workspace,
-                    share_beta=False, scale_mode=0, scale_regularizer=0.0, share_beta_group=None):
+                    share_beta=False, scale_mode=0, scale_regularizer=0.0, share_beta_group=None, segments=None):
         """The C-ABI call behind ``fit`` (and behind the ``smplfitter_amd::fit`` operator): every result
-        tensor, ``pose_rotvecs`` included."""
+        tensor, ``pose_rotvecs`` included.  ``segments``: the checked sizes of ``share_beta_segments``."""
         bm = self.body_model
         device = bm.v_template.device
         for t in (target_vertices, target_joints, vertex_weights, joint_weights):
@@ -218,7 +283,8 @@ class BodyFitter(nn.Module):
             raise ValueError('every rank of a sharded share_beta fit needs at least one instance')
         if B > 0:
             h = bm._native(device, kid=self.enable_kid)
-            ws = _workspace if _workspace is not None else bm._workspace(h, B, device)
+            plan = self._segment_plan(device, segments) if segments is not None else None
+            ws = _workspace if _workspace is not None else self._segments_workspace(h, B, device, plan)
             callback, failure = _share_callback(ws, share_beta_group)
             with torch.cuda.device(device):
                 stream = torch.cuda.current_stream(device).cuda_stream
@@ -239,7 +305,7 @@ class BodyFitter(nn.Module):
                     relative_orientations=rel.data_ptr(),
                     scale_corr=scale.data_ptr() if scale is not None else None, workspace=ws.data_ptr(),
                     workspace_bytes=ws.numel(), hip_stream=stream, share_allreduce=callback)
-                rc = _lib.load().smplfit_fit_ex_f32(h.ptr, C.byref(args))
+                rc = _lib.load().smplfit_fit_segments_f32(h.ptr, C.byref(args), plan.ptr if plan is not None else None)
                 if failure:
                     raise failure[0]
                 _lib.check(rc)
@@ -250,6 +316,12 @@ class BodyFitter(nn.Module):
         if scale_mode:
             result['scale_corr'] = scale
         return result
+
+    @staticmethod
+    def _segments_workspace(h, batch, device, plan):
+        """The workspace of a fit or a shape solve: with a plan of segments, its own query's size."""
+        nbytes = h.workspace_bytes(batch) if plan is None else plan.workspace_bytes(h)
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
     FIT_GRAD_NAMES = ('target_vertices', 'target_joints', 'vertex_weights', 'joint_weights')
 
@@ -308,6 +380,7 @@ class BodyFitter(nn.Module):
         kid_regularizer_reference: Optional[torch.Tensor] = None,
         requested_keys: Optional[list[str]] = None,
         share_beta_group=None,
+        share_beta_segments=None,
     ) -> dict[str, torch.Tensor]:
         """Shape and translation (and possibly scale) for a known pose (reference
         pt/bodyfitter.py:552-653): global rotations by forward kinematics of ``pose_rotvecs`` (the HIP
@@ -317,9 +390,17 @@ class BodyFitter(nn.Module):
         solve in HIP (``smplfit_shape_solve_backward_f32``); once differentiable; up to 17 shape
         unknowns; ``share_beta`` and the scale options with gradients raise ``NotImplementedError``.
         ``share_beta`` ignores the ridge references, as the reference's all-shared solve does
-        (pt/lstsq.py:45-47).  ``share_beta_group``: as in :meth:`fit`."""
+        (pt/lstsq.py:45-47).  ``share_beta_group``, ``share_beta_segments``: as in :meth:`fit`."""
         if scale_target and scale_fit:  # same check, same message as pt/bodyfitter.py:858-859
             raise ValueError('Only one of estim_scale_target and estim_scale_fit can be True')
+        segments = None
+        if share_beta_segments is not None:
+            if share_beta_group is not None:
+                raise ValueError('share_beta_segments cannot be combined with share_beta_group')
+            segments = _segment_sizes(share_beta_segments, target_vertices.shape[0])
+            if torch.compiler.is_compiling():
+                raise NotImplementedError('share_beta_segments cannot be traced; call the fit outside the compiled region')
+            share_beta = True
         if share_beta_group is not None and not share_beta:
             raise ValueError('share_beta_group needs share_beta=True')
         if kid_regularizer_reference is not None and not self.enable_kid:
@@ -354,7 +435,8 @@ class BodyFitter(nn.Module):
                                   add_mean=True, want_mesh=False, share_beta=share_beta,
                                   scale_mode=1 if scale_target else 2 if scale_fit else 0,
                                   scale_regularizer=scale_regularizer, beta_ref=beta_regularizer_reference,
-                                  kid_ref=kid_regularizer_reference, share_beta_group=share_beta_group)
+                                  kid_ref=kid_regularizer_reference, share_beta_group=share_beta_group,
+                                  segments=segments)
         parents = bm.kintree_parents_tensor[1:].to(G.device)
         parent_glob = torch.cat(
             [torch.eye(3, device=G.device).expand(B, 1, 3, 3), G.index_select(1, parents)], dim=1)
@@ -555,7 +637,7 @@ class BodyFitter(nn.Module):
     def _shape_solve(self, glob_rotmats, target_vertices, target_joints=None, vertex_weights=None,
                      joint_weights=None, beta_regularizer=1.0, beta_regularizer2=0.0,
                      kid_regularizer=None, add_mean=False, want_mesh=True, share_beta=False, scale_mode=0,
-                     scale_regularizer=0.0, beta_ref=None, kid_ref=None, share_beta_group=None):
+                     scale_regularizer=0.0, beta_ref=None, kid_ref=None, share_beta_group=None, segments=None):
         """One shape solve for given global rotations; targets are centred internally and the returned
         trans / vertices / joints live in the centred frame; ``add_mean`` adds the target mean back to
         trans alone (vertices / joints stay centred)."""
@@ -578,7 +660,8 @@ class BodyFitter(nn.Module):
         scale = torch.empty((B,), dtype=torch.float32, device=device) if scale_mode else None
         kid_reg = float(beta_regularizer if kid_regularizer is None else kid_regularizer)
         h = bm._native(device, kid=self.enable_kid)
-        ws = bm._workspace(h, B, device)
+        plan = self._segment_plan(device, segments) if segments is not None else None
+        ws = self._segments_workspace(h, B, device, plan)
         callback, failure = _share_callback(ws, share_beta_group)
         p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         with torch.cuda.device(device):
@@ -594,7 +677,7 @@ class BodyFitter(nn.Module):
                 kid_factor=p(kid), scale_corr=p(scale), vertices_out=p(verts), joints_out=p(joints),
                 workspace=ws.data_ptr(), workspace_bytes=ws.numel(), hip_stream=stream,
                 share_allreduce=callback)
-            rc = _lib.load().smplfit_shape_solve_ex_f32(h.ptr, C.byref(args))
+            rc = _lib.load().smplfit_shape_solve_segments_f32(h.ptr, C.byref(args), plan.ptr if plan is not None else None)
             if failure:
                 raise failure[0]
             _lib.check(rc)
