@@ -27,6 +27,12 @@ constexpr int kGenBlk = 4;       // 4 x 4 blocks of the Gramian per thread and p
 constexpr int kGenQ = 4;         // unknowns per thread for the right-hand side: S <= kGenQ * (threads of the workgroup)
 constexpr int kGenMaxS = kGenQ * 256 - 1;  // (smplfit_create refuses more shape unknowns)
 inline int gen_accum_threads(int S) { return S <= 88 ? 64 : 256; }
+// vertices between two additions of the accumulate kernels' fp32 sums to the fp64 record (both forms).  A longer chain
+// costs the solve its floor: with 2048 vertices (6144 rows) per chain the betas of a target far from the template (betas
+// of +-5: residuals of a metre) sat 5e-4 from the fp64 solve and a weighted solve without a ridge 1e-3 on the one-chain
+// form below, where the reference's fp32 — a blocked product — stays within 2.5e-4; emulated on the host in fp32: 6-8e-4
+// with one chain, 1.4-2.0e-4 at 2048 vertices, 5-7e-5 at 512, 1.5e-5 at 128 (tests/test_gpu_general_shapes.py)
+constexpr int kGenFlushVertices = 512;
 
 __host__ __device__ inline int gen_s4(int S) { return (S + 3) & ~3; }
 // dynamic LDS of k_gen_accum (bytes): rows [3 TV][S4] | b [3 TV] | w [3 TV] | R~ [TV][12] | joint ids [TV][KW] | weights [TV][KW]
@@ -53,8 +59,10 @@ inline size_t gen_accum_lds(int J, int S, int KW) {
 // eight such workgroups share a CU where two 256-thread ones would leave most of their lanes idle)
 // STAGE: the instance's joint rows are copied to LDS first (a template flag, not a run-time pointer select: with one
 // pointer that may be LDS or global every access becomes a FLAT one)
+// flush_tiles: every so many tiles the fp32 sums are ADDED to the fp64 record and restart from zero (kGenFlushVertices
+// above: one fp32 accumulator per entry over all 3 V rows is a chain of 20 k additions)
 template <bool WEIGHTED, int kGenTV, int kGenThreads, bool STAGE>
-__global__ __launch_bounds__(kGenThreads, 2) void k_gen_accum(DevModel m, Workspace ws, int B) {
+__global__ __launch_bounds__(kGenThreads, 2) void k_gen_accum(DevModel m, Workspace ws, int B, int flush_tiles) {
   constexpr int kGenRows = 3 * kGenTV;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int S = m.S, S4 = gen_s4(S), J = m.J, Vp = m.Vp, V = m.V, KW = m.KW;
@@ -113,8 +121,49 @@ __global__ __launch_bounds__(kGenThreads, 2) void k_gen_accum(DevModel m, Worksp
       ar[q] = 0.f;
       asa[q][0] = asa[q][1] = asa[q][2] = 0.f;
     }
+    // the sums leave the registers for the record: each entry has ONE owner (a thread and a pass), so the additions of a
+    // later flush need no atomics.  (The block indices pass through an empty asm: the addresses of a thread's 64 entries
+    // do not change from one flush to the next, and hoisted out of the tile loop they are 128 registers — spilled.)
+    bool first_flush = true;
+    auto flush = [&]() {
+      auto put = [&](double* o, float& v) {
+        *o = first_flush ? (double)v : *o + (double)v;
+        v = 0.f;
+      };
+#pragma unroll
+      for (int k = 0; k < kGenBlk; ++k) {
+        if (bi[k] < 0) continue;
+        int i0 = 4 * bi[k], j0 = 4 * bj[k];
+        asm volatile("" : "+v"(i0), "+v"(j0));
+#pragma unroll
+        for (int x = 0; x < 4; ++x)
+#pragma unroll
+          for (int y = 0; y < 4; ++y) {
+            const int i = i0 + x, j = j0 + y;
+            if (i <= j && j < S) put(out + sf::ne_g(S, i, j), acc[k][x * 4 + y]);
+          }
+      }
+      if (pass == 0) {
+#pragma unroll
+        for (int q = 0; q < kGenQ; ++q) {
+          const int s2 = tid + kGenThreads * q;
+          if (s2 < S) {
+            put(out + NG + s2, ar[q]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) put(out + NG + S + c * S + s2, asa[q][c]);
+          }
+        }
+        if (tid == 0) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) put(out + NG + 4 * S + c, asb[c]);
+          put(out + NE, aw);
+        }
+      }
+      first_flush = false;
+    };
     for (int t = 0; t < ntile; ++t) {
       const int v0 = t * kGenTV;
+      if (t > 0 && t % flush_tiles == 0) flush();
       __syncthreads();  // (the previous tile's rows have been consumed)
       if (tid < kGenTV) {  // the vertex's skinning pairs, blended rotation, position and residual
         const int i = v0 + tid;
@@ -223,33 +272,7 @@ __global__ __launch_bounds__(kGenThreads, 2) void k_gen_accum(DevModel m, Worksp
           }
       }
     }
-#pragma unroll
-    for (int k = 0; k < kGenBlk; ++k) {
-      if (bi[k] < 0) continue;
-#pragma unroll
-      for (int x = 0; x < 4; ++x)
-#pragma unroll
-        for (int y = 0; y < 4; ++y) {
-          const int i = 4 * bi[k] + x, j = 4 * bj[k] + y;
-          if (i <= j && j < S) out[sf::ne_g(S, i, j)] = (double)acc[k][x * 4 + y];
-        }
-    }
-    if (pass == 0) {
-#pragma unroll
-      for (int q = 0; q < kGenQ; ++q) {
-        const int s2 = tid + kGenThreads * q;
-        if (s2 < S) {
-          out[NG + s2] = (double)ar[q];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) out[NG + S + c * S + s2] = (double)asa[q][c];
-        }
-      }
-      if (tid == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[NG + 4 * S + c] = (double)asb[c];
-        out[NE] = (double)aw;
-      }
-    }
+    flush();
   }
 }
 
@@ -655,9 +678,10 @@ __global__ __launch_bounds__(64 * NW) void k_gen_accum_mfma(DevModel m, Workspac
   // ---- the entries leave the accumulators for the record (and the scale unknown's extra sums), as fp64 sums of fp32
   // partial sums: every flush_every blend passes (64 / 128 vertices each) the accumulators are ADDED to the record and
   // restart from zero.  One fp32 accumulator per entry over all 3 V rows is a chain of 20 k additions: good for the
-  // plain fit (2e-5 m), not for the scale unknown, whose column is nearly a combination of the others — scale_corr
-  // 2.3e-4 from the fp64 evaluation where the reference's own fp32 is within 1e-4; a scaled iteration flushes after
-  // every pass (the sums of <= 128 vertices, as the lanes of the other paths' kernels keep them).
+  // plain fit on ordinary targets (2e-5 m), not for the betas of hard ones (kGenFlushVertices) nor for the scale
+  // unknown, whose column is nearly a combination of the others — scale_corr 2.3e-4 from the fp64 evaluation where the
+  // reference's own fp32 is within 1e-4; a scaled iteration flushes after every pass (the sums of <= 128 vertices, as
+  // the lanes of the other paths' kernels keep them).
   const int NG = sf::ne_ng(S), NE = sf::ne_size(S);
   double* out = ws.gramv + (size_t)b * (NE + 1);
   double* vex = vextra ? vextra + (size_t)b * (S + sf::kScaleExtras) : nullptr;

@@ -824,8 +824,9 @@ int launch_gen_accum_mfma(const DevModel& d, const Workspace& ws, int B, bool we
   const int nw = gen2_nw(d.S), nbw = gen2_nbw(d.S);
   const dim3 grid(B, gen2_groups(d.S));
   // blend passes (64 / 128 vertices) between two additions of the fp32 accumulators to the fp64 record: a scaled
-  // iteration after every pass, the others after 2048 vertices (k_gen_accum_mfma; +2.5 % of its time, 1024: +5 %)
-  const int flush_every = vextra ? 1 : std::max(1, 2048 / gen2_sv(d.S));
+  // iteration after every pass, the others after kGenFlushVertices (k_gen_accum_mfma; at S = 300 a flush every 2048
+  // vertices cost +2.5 % of its time, every 1024 +5 %)
+  const int flush_every = vextra ? 1 : std::max(1, kGenFlushVertices / gen2_sv(d.S));
 #define SF_GEN2(W_, NW_, NBW_, ST_)                                                                                   \
   do {                                                                                                                \
     ensure_max_lds(reinterpret_cast<const void*>(&k_gen_accum_mfma<W_, NW_, NBW_, ST_>)); \
@@ -859,11 +860,12 @@ int launch_gen_accum(const DevModel& d, const Workspace& ws, int B, bool weighte
   if (lds > 160 * 1024) return fail(SMPLFIT_ERR_UNSUPPORTED, "general path: too many shape unknowns for the accumulate kernel's LDS tile");
   const bool stage = gen_accum_stage_joints(d.J, d.S, d.KW);
   const int tv = gen_tile_vertices(d.S), nt = gen_accum_threads(d.S);
+  const int flush_tiles = std::max(1, kGenFlushVertices / tv);
   // (weighted, vertices per tile, threads, staged joint rows) -> instantiation
 #define SF_GEN(W_, TV_, NT_, ST_)                                                                              \
   do {                                                                                                         \
     ensure_max_lds(reinterpret_cast<const void*>(&k_gen_accum<W_, TV_, NT_, ST_>)); \
-    hipLaunchKernelGGL((k_gen_accum<W_, TV_, NT_, ST_>), dim3(B), dim3(NT_), lds, st, d, ws, B);               \
+    hipLaunchKernelGGL((k_gen_accum<W_, TV_, NT_, ST_>), dim3(B), dim3(NT_), lds, st, d, ws, B, flush_tiles);  \
   } while (0)
 #define SF_GEN_W(TV_, NT_, ST_)              \
   do {                                       \
