@@ -773,6 +773,11 @@ int smplfit_shape_solve_segments_f32(const smplfit_handle* h, const smplfit_shap
  * called while other threads are inside the library. */
 int smplfit_reload_options(void);
 
+/* Posedirs GEMM launches of this process that read the pose features as the split-bf16 planes the fit's prologue
+ * kernel wrote (the default where it applies; SMPLFIT_GEMM_PLANES=0: none).  Both front ends give the same bits, so
+ * this count is the one way to tell which ran: tests and A/B tools read it before and after a call. */
+uint64_t smplfit_gemm_plane_launches(void);
+
 /* Measurement hook (bench.py's roofline leg): launches ONE kernel of the fit `reps` times on
  * `hip_stream` between two HIP events recorded on that same stream and returns the average
  * duration in milliseconds.  The workspace must hold the state a preceding smplfit_fit_f32 call on

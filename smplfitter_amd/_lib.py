@@ -54,7 +54,7 @@ EXPORTED_SYMBOLS = [
     'smplfit_fit_known_shape_backward_workspace_bytes', 'smplfit_fit_known_shape_backward_f32',
     'smplfit_share_segments_create', 'smplfit_share_segments_destroy', 'smplfit_share_segments_batch',
     'smplfit_share_segments_get_table', 'smplfit_share_segments_workspace_bytes', 'smplfit_fit_segments_f32',
-    'smplfit_shape_solve_segments_f32',
+    'smplfit_shape_solve_segments_f32', 'smplfit_gemm_plane_launches',
 ]  # fmt: skip
 
 _fp = C.POINTER(C.c_float)
@@ -394,6 +394,9 @@ def load():
         lib.smplfit_fit_segments_f32.restype = i32
         lib.smplfit_shape_solve_segments_f32.argtypes = [vp, C.POINTER(ShapeSolveArgs), vp]
         lib.smplfit_shape_solve_segments_f32.restype = i32
+    if hasattr(lib, 'smplfit_gemm_plane_launches'):  # (as above)
+        lib.smplfit_gemm_plane_launches.argtypes = []
+        lib.smplfit_gemm_plane_launches.restype = C.c_uint64
     if os.environ.get('SMPLFIT_LIB') and not hasattr(lib, 'smplfit_abi_version'):
         _lib = lib  # an older build loaded by the A/B tools (tools/ab_fit.py): no version / share-table exports
         return lib
@@ -534,6 +537,12 @@ def reload_options():
     """Re-read the SMPLFIT_* tuning variables (they are read once, at first use): for tests and A/B tools that
     switch kernel paths inside one process."""
     check(load().smplfit_reload_options())
+
+
+def gemm_plane_launches() -> int:
+    """Posedirs GEMM launches of this process that read the prologue kernel's split-bf16 feature planes
+    (``SMPLFIT_GEMM_PLANES=0``: none); the results do not show which front end ran, this count does."""
+    return int(load().smplfit_gemm_plane_launches())
 
 
 class Transfer:

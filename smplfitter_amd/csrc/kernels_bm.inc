@@ -1172,6 +1172,7 @@ struct PrologueArgs {
   const float* tj;  // (B, J, 3) centred target joints (given or regressed)
   const float* jw;  // (B, J) or null
   int joint_block, joint_block_weighted, sa_closed_form, B;
+  int planes;  // the pose features go to the GEMM's split-bf16 planes ws.rpP instead of ws.rp (Route::gemm_planes)
 };
 constexpr int kProChain = 5;  // ancestors' rotations requested together
 
@@ -1259,16 +1260,31 @@ __global__ __launch_bounds__(64 * kProWaves) void k_prologue_bm(DevModel m, Prol
         for (int s = 0; s < S1; ++s) pe[(size_t)(c * S1 + s) * pitch] = P[c][s];
     }
     // ---- relative rotations -> pose features (:869-876, :913); the constant features behind them by the root's wave
-    if (bcol < a.B) {
-      float* rp = ws.rp + (size_t)b * tb.Kp;
-      if (j > 0) {
-        float rel[9];
-        sf::m3_tmul(Gp, Gj, rel);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) rp[sf::rp_pos((j - 1) * 9 + k, tb.Kp)] = rel[k];
+    // a.planes: as the split-bf16 planes the GEMM multiplies (ws.rpP, sf::plane_off: the bits its own front end would
+    // split from ws.rp) INSTEAD of the fp32 rows, which only that front end reads behind this kernel — the row stores
+    // are the expensive ones (a cache line per lane and feature; a plane store covers 32 lanes with four); the pad
+    // lanes up to Mp write zeros there (every lane of a GEMM wave reads its run)
+    const bool live = bcol < a.B;
+    float* rp = ws.rp + (size_t)b * tb.Kp;
+    char* pl = reinterpret_cast<char*>(ws.rpP);
+    auto feature = [&](int p, float x) {
+      const int pos = sf::rp_pos(p, tb.Kp);
+      if (!a.planes) {
+        if (live) rp[pos] = x;
       } else {
-        for (int k = 0; k < tb.Kp - tb.P; ++k) rp[sf::rp_pos(tb.P + k, tb.Kp)] = k == 0 ? 1.f : 0.f;
+        const sf::Bf16x3 t = sf::split_bf16x3(live ? x : 0.f);
+        *reinterpret_cast<__bf16*>(pl + sf::plane_off(bcol, pos, 0)) = t.h;
+        *reinterpret_cast<__bf16*>(pl + sf::plane_off(bcol, pos, 1)) = t.m;
+        if ((pos >> 4) == sf::kPlaneSteps - 1) *reinterpret_cast<__bf16*>(pl + sf::plane_off(bcol, pos, 2)) = t.l;
       }
+    };
+    if (j > 0) {
+      float rel[9];
+      sf::m3_tmul(Gp, Gj, rel);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) feature((j - 1) * 9 + k, rel[k]);
+    } else {
+      for (int k = 0; k < tb.Kp - tb.P; ++k) feature(tb.P + k, k == 0 ? 1.f : 0.f);
     }
     // ---- this joint's rows of the joint block (sf::joint_gram_by_joint: the same per-row terms) + the closed-form vertex SA
     const float w = a.joint_block_weighted ? a.jw[(size_t)b * J + j] : 1.0f;

@@ -644,11 +644,21 @@ __device__ __forceinline__ void lds_dma16(const char* src, uint32_t lane_off, ch
 // so the 8 waves of two of its workgroups (or of one 8-wave workgroup) own the whole register file of the
 // CU and no other wave — of this fit's other chunk or of any other stream of the process — can become
 // resident next to them.
-template <bool TRANSPOSED>
+//
+// FRONT END.  PLANES = false: the wave loads its instances' fp32 feature rows (A: ws.rp) and splits them itself -- 26
+// float4 requests per lane that use 32 bytes of every 832-byte row, and 104 three-way splits, repeated by each of the
+// nchunk workgroups of an instance block.  PLANES = true: the producer of the features has written the split planes in
+// fragment order INSTEAD of the fp32 rows (Apl: ws.rpP, sf::plane_off) and the wave fills f1 / f2 / f3[KS - 1] with 27
+// requests of one contiguous 1 KB run each, no arithmetic (Route::gemm_planes: where k_prologue_bm made the features).
+// The planes hold the bits the split below produces (sf::split_bf16x3 on both sides), and from the first barrier on
+// the kernel is the same code: the results are bit-identical (tests/test_gpu_gemm_planes.py).
+template <bool TRANSPOSED, bool PLANES>
 __global__ __launch_bounds__(64 * kGemmWaves, 2) void k_posedirs_gemm_bf16x3(const float* __restrict__ A,
+                                                                           const uint16_t* __restrict__ Apl,
                                                                            const uint16_t* __restrict__ Bimg,
                                                                            float* __restrict__ C, int N,
                                                                            int tiles_per_chunk, int Mp) {
+  static_assert(!PLANES || (kGemm3 && kGemmKS == sf::kPlaneSteps), "the planes are those of the three-product form");
   constexpr int KS = kGemmKS, KP = 16 * KS, NW = kGemmWaves;
   constexpr int NDMA = kGemmTileBytes / 1024;  // 1 KB per wave-instruction: 39
   extern __shared__ __attribute__((aligned(16))) char smem_b[];  // [kGemmRing][kGemmTileBytes]
@@ -683,7 +693,16 @@ __global__ __launch_bounds__(64 * kGemmWaves, 2) void k_posedirs_gemm_bf16x3(con
   for (int q = 0; q < LEAD; ++q) dma_tile(min(t_begin + q, t_end - 1), q);
   // features of this lane's instance, its k-octet of every k-step, split into three bf16 planes
   bf16x8 f1[KS], f2[KS], f3[KS];
-  {
+  if constexpr (PLANES) {
+    // (lane = 32 kg + l31 is the lane order of a run; f3 of the other k-steps is never read, see the products below)
+    const char* src = reinterpret_cast<const char*>(Apl) + (size_t)((active ? m0 : 0) >> 5) * sf::kPlaneGroupBytes + lane * 16;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      f1[s] = *reinterpret_cast<const bf16x8*>(src + (2 * s) * 1024);
+      f2[s] = *reinterpret_cast<const bf16x8*>(src + (2 * s + 1) * 1024);
+    }
+    f3[KS - 1] = *reinterpret_cast<const bf16x8*>(src + (sf::kPlaneRuns - 1) * 1024);
+  } else {
     const float* src = A + (size_t)((active ? m0 : 0) + l31) * KP + kg * 8;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
@@ -692,13 +711,10 @@ __global__ __launch_bounds__(64 * kGemmWaves, 2) void k_posedirs_gemm_bf16x3(con
       const float x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const __bf16 h = (__bf16)x[j];
-        const float r1 = x[j] - (float)h;
-        const __bf16 m = (__bf16)r1;
-        const __bf16 l = (__bf16)(r1 - (float)m);
-        f1[s][j] = h;
-        f2[s][j] = m;
-        f3[s][j] = l;
+        const sf::Bf16x3 t = sf::split_bf16x3(x[j]);
+        f1[s][j] = t.h;
+        f2[s][j] = t.m;
+        f3[s][j] = t.l;
       }
     }
   }
@@ -843,11 +859,8 @@ __global__ __launch_bounds__(256) void k_split_features(const float* __restrict_
     bf16x8 h, m, l;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float v = x[sl * 8 + j];
-      const __bf16 hh = (__bf16)v;
-      const float r1 = v - (float)hh;
-      const __bf16 mm = (__bf16)r1;
-      h[j] = hh; m[j] = mm; l[j] = (__bf16)(r1 - (float)mm);
+      const sf::Bf16x3 t = sf::split_bf16x3(x[sl * 8 + j]);
+      h[j] = t.h; m[j] = t.m; l[j] = t.l;
     }
     const int ps = sl ^ ((r >> 2) & 3);
     uint16_t* d = base + (size_t)r * 32 + ps * 8;

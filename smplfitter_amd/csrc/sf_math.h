@@ -43,6 +43,22 @@ SF_HD double sum_rows_f64(const double* __restrict__ p, int n, size_t stride) {
   return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
 }
 
+#if defined(__HIPCC__)
+// Error-free split of an fp32 into three bf16 terms x = h + m + l (3 x 8 mantissa bits), the operand form of the
+// split-bf16 posedirs GEMMs.  Stated once: whoever produces feature planes (the GEMM's own front end,
+// k_split_features, k_prologue_bm) gets the same bits.
+struct Bf16x3 {
+  __bf16 h, m, l;
+};
+SF_HD Bf16x3 split_bf16x3(float x) {
+  const __bf16 h = (__bf16)x;
+  const float r1 = x - (float)h;
+  const __bf16 m = (__bf16)r1;
+  const __bf16 l = (__bf16)(r1 - (float)m);
+  return {h, m, l};
+}
+#endif
+
 // a / b, 0 where b == 0 (rotation.py:8-11)
 SF_HD float divide_no_nan(float a, float b) { return b == 0.f ? 0.f : a / b; }
 

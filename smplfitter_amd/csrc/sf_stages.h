@@ -37,6 +37,21 @@ SF_HD constexpr int cpack_stride(int S, int KW) {
 // (HostTables::pdT) are stored in the same order.
 SF_HD constexpr int rp_pos(int p, int Kp) { return (p & 1) * (Kp / 2) + (p >> 1); }
 
+// Split-bf16 planes of the pose features (Workspace::rpP; Kp == 208, three-product form), in the FRAGMENT ORDER of
+// k_posedirs_gemm_bf16x3: per group of 32 instances kPlaneRuns runs of 1 KB, run (2 s + plane) = k-step s of the hi
+// (plane 0) / mid (plane 1) plane, the last run the lo plane of the last k-step (the bias row's step, the only one whose
+// third term the GEMM takes); inside a run the 16 bytes of lane (k-octet kg, instance l31) = 32 kg + l31 — the eight
+// bf16 at positions 16 s + 8 kg .. + 7 of the K axis (rp_pos order) — follow each other: a wave reads a run with one
+// 16-byte request per lane.  -> the byte offset of feature position `pos` of instance `inst` in `plane` (0, 1; 2: the
+// lo plane, pos in the last k-step only).
+constexpr int kPlaneSteps = 13;                    // k-steps of 16 (Kp == 208)
+constexpr int kPlaneRuns = 2 * kPlaneSteps + 1;
+constexpr int kPlaneGroupBytes = kPlaneRuns * 1024;  // per 32 instances: 864 B per instance
+SF_HD constexpr size_t plane_off(int inst, int pos, int plane) {
+  return (size_t)(inst >> 5) * kPlaneGroupBytes + (size_t)(plane == 2 ? kPlaneRuns - 1 : 2 * (pos >> 4) + plane) * 1024 +
+         (size_t)((((pos >> 3) & 1) * 32 + (inst & 31)) * 16 + (pos & 7) * 2);
+}
+
 constexpr int kPsum = 16;  // part-sum record: raw 9, s_t 3, s_a 3, s_w 1
 constexpr int kScaleExtras = 6;  // scaled solve: entries after u in the extra-sum record (tt, tb, bb, St)
 

@@ -315,6 +315,9 @@ struct Workspace {
   float* GT;       // (J*9, Mp) global rotations, instance-innermost (written by k_joint_stage beside ws.G)
   float* pextT;    // (J*3*(S+1), Mp) FK positions with their beta-Jacobian, instance-innermost
   float* gramjP;   // (prologue workgroups per instance block, NE+1, Mp) partial sums of the joint block
+  uint16_t* rpP;   // (Mp/32, sf::kPlaneRuns, 64, 8) the pose features as split-bf16 planes in the fragment order of
+                   // k_posedirs_gemm_bf16x3 (sf::plane_off), written by k_prologue_bm instead of ws.rp on the route
+                   // gemm_planes; Kp == 208 only.  No region of its own: the head of ws.vposed (carve)
 };
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -453,6 +456,12 @@ Workspace carve(const sf::HostTables& t, int B, Arena& ar, bool fwd_only = false
   ws.GT = (float*)take(pro ? Mp * J * 9 * 4 : 0);
   ws.pextT = (float*)take(pro ? Mp * J * 3 * (S + 1) * 4 : 0);
   ws.gramjP = (float*)take(pro ? (size_t)prologue_splits((int)J) * NE1 * Mp * 4 : 0);
+  // the feature planes of the route gemm_planes live in ws.vposed, which only the wave-per-instance vertex kernels
+  // read and no batch-major fit touches (as the feature images of the tiled GEMM, launch_gemm): 864 of its 12 Vp bytes
+  // per instance.  Every 16 bytes of them are written by k_prologue_bm before the GEMM reads them, the pad instances'
+  // as zeros.
+  ws.rpP = pro && !fwd_only && sf::kGemm3 && t.Kp == 16 * sf::kPlaneSteps && 12 * Vp >= sf::kPlaneGroupBytes / 32
+               ? reinterpret_cast<uint16_t*>(ws.vposed) : nullptr;
   return ws;
 }
 
@@ -513,6 +522,7 @@ struct Tuning {
   bool refine_bm = true;   // SMPLFIT_REFINE_BM=0: the refinement + epilogue as the wave-per-instance k_refine_epilogue behind a part-sum combine instead of k_refine_bm (A/B)
   bool prologue_bm = true; // SMPLFIT_PROLOGUE_BM=0: the shape prologue inside k_joint_stage + the joint-row transpose instead of k_prologue_bm (A/B)
   bool solve_bm = true;    // SMPLFIT_SOLVE_BM=0: normal-equation combine + wave-per-instance solve as two launches instead of k_solve_bm (A/B)
+  bool gemm_planes = true; // SMPLFIT_GEMM_PLANES=0: k_prologue_bm writes the fp32 feature rows and k_posedirs_gemm_bf16x3 splits them itself, instead of the split planes (A/B, bit-identical)
 };
 // The current options: an immutable snapshot behind an atomic pointer.  smplfit_reload_options() publishes a new
 // snapshot; a launch that is reading the old one on another thread keeps a valid object (snapshots are never freed:
@@ -536,6 +546,7 @@ Tuning read_tuning() {
   if (const char* e = env("SMPLFIT_BM_SLOTS")) t.share_slots = std::min(std::max(atoi(e), 256), 16384);
   if (const char* e = env("SMPLFIT_GEN_MFMA")) t.gen_mfma = e[0] != '0';
   if (const char* e = env("SMPLFIT_SOLVE_BM")) t.solve_bm = e[0] != '0';
+  if (const char* e = env("SMPLFIT_GEMM_PLANES")) t.gemm_planes = e[0] != '0';
   if (const char* e = env("SMPLFIT_PROLOGUE_BM")) t.prologue_bm = e[0] != '0';
   if (const char* e = env("SMPLFIT_REFINE_BM")) t.refine_bm = e[0] != '0';
   if (const char* e = env("SMPLFIT_ROT_BM")) t.rot_bm = e[0] != '0';
@@ -998,26 +1009,54 @@ ForwardArgs forward_args(const ForwardInputs& in, int nb, const float* trans, fl
 // which on gfx950 shares the vector ALUs with ordinary VALU work.
 bool gemm_bf16x3() { return !tune().gemm_f32; }
 
-int launch_gemm(const DevModel& d, const Workspace& ws, int B, hipStream_t st, bool transposed = false) {
+// Residency rounds of k_posedirs_gemm_bf16x3: its workgroups per CU (256 CUs) over a launch.  1 (default): 16 column
+// chunks at B = 4096, every CU starts one workgroup; 2 (up to this round): 32 chunks, every workgroup start — tile
+// request, features, first barrier — twice per CU.  A/B builds (-DSMPLFIT_GEMM_ROUNDS=2), measured alternating on one
+// box with both front ends: profiles/README.md, profiles/gemm_planes_mi355x.json
+#ifndef SMPLFIT_GEMM_ROUNDS
+#define SMPLFIT_GEMM_ROUNDS 1
+#endif
+constexpr int kGemmRounds = SMPLFIT_GEMM_ROUNDS;
+
+// GEMM launches on feature planes since the process started (smplfit_gemm_plane_launches: the route is not otherwise
+// visible to a caller, and the results are the same bits either way)
+std::atomic<uint64_t> g_gemm_plane_launches{0};
+
+// The models k_posedirs_gemm_bf16x3 serves (route_of asks it for Route::gemm_planes)
+bool gemm_bf16x3_stationary(const DevModel& d) { return d.Kp == 208 && gemm_bf16x3() && d.gemm_exclusive; }
+
+// planes: Route::gemm_planes — the features are the split planes ws.rpP (k_prologue_bm wrote them, and not ws.rp)
+int launch_gemm(const DevModel& d, const Workspace& ws, int B, hipStream_t st, bool transposed = false, bool planes = false) {
   const int Mp = (int)align_up((size_t)B, 128), N = 3 * d.Vp;
-  if (d.Kp == 208 && gemm_bf16x3() && d.gemm_exclusive) {
+  if (planes && !(sf::kGemm3 && transposed && gemm_bf16x3_stationary(d)))
+    return fail(SMPLFIT_ERR_UNSUPPORTED, "posedirs GEMM: no kernel reads feature planes on this route");
+  if (gemm_bf16x3_stationary(d)) {
     // Workgroup = 8 waves x 32 instances = one whole CU (see k_posedirs_gemm_bf16x3).  XCD-aware tiling: block
     // id = y * nchunk + x runs on XCD id % 8, so with nchunk a multiple of 8 a tile chunk x lives on ONE XCD,
-    // and with nchunk * ny ~ 512 (two residency rounds) the instance blocks y of a chunk walk its tiles
+    // and with nchunk * ny ~ 256 kGemmRounds (one workgroup per CU) the instance blocks y of a chunk walk its tiles
     // together: the 39 KB tile images come out of that XCD's L2 and posedirs is fetched from HBM about twice
     // per launch instead of once per instance block (FETCH_SIZE: 444 -> 72 MB per launch at B = 4096).
     const int ntiles = N / 32, ny = (Mp + 32 * kGemmWaves - 1) / (32 * kGemmWaves);
-    const int nchunk = std::min(std::max(8, (2 * 256 / ny + 4) / 8 * 8), ntiles);
+    const int nchunk = std::min(std::max(8, (kGemmRounds * 256 / ny + 4) / 8 * 8), ntiles);
     const int per = (ntiles + nchunk - 1) / nchunk;  // trailing chunks may be empty (they return at once)
     const size_t lds = (size_t)kGemmRing * kGemmTileBytes;
-    ensure_max_lds(reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<true>));
-    ensure_max_lds(reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<false>));
+    if constexpr (sf::kGemm3) {
+      if (planes) {
+        g_gemm_plane_launches.fetch_add(1, std::memory_order_relaxed);
+        ensure_max_lds(reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<true, true>));
+        hipLaunchKernelGGL((k_posedirs_gemm_bf16x3<true, true>), dim3(nchunk, ny), dim3(64 * kGemmWaves), lds, st, ws.rp,
+                           ws.rpP, d.pdB, ws.vpT, N, per, Mp);
+        return 0;
+      }
+    }
+    ensure_max_lds(reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<true, false>));
+    ensure_max_lds(reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<false, false>));
     if (transposed)
-      hipLaunchKernelGGL((k_posedirs_gemm_bf16x3<true>), dim3(nchunk, ny), dim3(64 * kGemmWaves), lds, st, ws.rp,
-                         d.pdB, ws.vpT, N, per, Mp);
+      hipLaunchKernelGGL((k_posedirs_gemm_bf16x3<true, false>), dim3(nchunk, ny), dim3(64 * kGemmWaves), lds, st, ws.rp,
+                         ws.rpP, d.pdB, ws.vpT, N, per, Mp);
     else
-      hipLaunchKernelGGL((k_posedirs_gemm_bf16x3<false>), dim3(nchunk, ny), dim3(64 * kGemmWaves), lds, st, ws.rp,
-                         d.pdB, ws.vposed, N, per, Mp);
+      hipLaunchKernelGGL((k_posedirs_gemm_bf16x3<false, false>), dim3(nchunk, ny), dim3(64 * kGemmWaves), lds, st, ws.rp,
+                         ws.rpP, d.pdB, ws.vposed, N, per, Mp);
     return 0;
   }
   if (d.Kp != 208 && transposed && d.kc32 > 0 && gemm_bf16x3() && d.gemm_exclusive) {
@@ -1200,10 +1239,11 @@ void launch_solve_bm(const smplfit_handle* h, SolveBmPlan p, const Workspace& ws
 // K1p (k_prologue_bm): the shape prologue of the joint stage on the batch-major path — k_joint_stage then fits the
 // rotations only and leaves ws.GT.  Applies when every shape solve of the call is k_solve_bm (the one consumer of its
 // ws.gramjP / ws.pextT): route_of.
-void launch_prologue_bm(const smplfit_handle* h, const JointStageArgs& ja, const Workspace& ws, int B, hipStream_t st) {
+void launch_prologue_bm(const smplfit_handle* h, const JointStageArgs& ja, const Workspace& ws, int B, hipStream_t st,
+                        bool planes) {
   const DevModel& d = h->d;
   const int Mp = (int)align_up((size_t)B, 128);
-  PrologueArgs pa{ja.tj, ja.jw, ja.joint_block, ja.joint_block_weighted, ja.vertex_sa_closed_form, B};
+  PrologueArgs pa{ja.tj, ja.jw, ja.joint_block, ja.joint_block_weighted, ja.vertex_sa_closed_form, B, planes ? 1 : 0};
   const size_t lds = (size_t)(kProWaves / 2) * (sf::ne_size(d.S) + 1) * 64 * 4;
   const dim3 grid(Mp / 64, prologue_splits(d.J));
   if (d.S == 11) {
@@ -1235,8 +1275,9 @@ void launch_rotations_bm(const smplfit_handle* h, const JointStageArgs& ja, int 
     hipLaunchKernelGGL(k_rotations_bm_rounds, dim3((B + 63) / 64), dim3(64 * kRefWaves), lds, st, d, ra, share_view(h, rot_kind, B), ws, Mp);
   }
 }
+// planes: Route::gemm_planes (with pro)
 void launch_joint_stage_fit(const smplfit_handle* h, JointStageArgs ja, const Workspace& ws, int B, hipStream_t st, bool pro,
-                            int rot_kind = -1, int gprev_mode = 0) {
+                            int rot_kind = -1, int gprev_mode = 0, bool planes = false) {
   if (pro && ja.do_prologue) {
     if (rot_kind >= 0) {
       launch_rotations_bm(h, ja, rot_kind, gprev_mode, ws, B, st);
@@ -1246,7 +1287,7 @@ void launch_joint_stage_fit(const smplfit_handle* h, JointStageArgs ja, const Wo
       launch_joint_stage(h->d, ja, ws, B, st);
       ja.do_prologue = 1;
     }
-    launch_prologue_bm(h, ja, ws, B, st);
+    launch_prologue_bm(h, ja, ws, B, st, planes);
   } else {
     launch_joint_stage(h->d, ja, ws, B, st);
   }
@@ -1276,7 +1317,8 @@ void launch_refine_bm(const smplfit_handle* h, RefineArgs ra, const ShareView& s
 // ------------------------------------------------------------------------------------------------
 // Kernel route of one call: which kernel family serves its vertex passes and which stage kernels run inside the
 // batch-major one, decided once per call by route_of() from the handle, the batch and the call's shape.  Nothing else
-// reads the routing switches (SMPLFIT_BM, SMPLFIT_BM_*, _ROT_BM, _REFINE_BM, _PROLOGUE_BM, _SOLVE_BM, _SHAPE_FORM).
+// reads the routing switches (SMPLFIT_BM, SMPLFIT_BM_*, _ROT_BM, _REFINE_BM, _PROLOGUE_BM, _SOLVE_BM, _GEMM_PLANES,
+// _SHAPE_FORM).
 //
 //   condition                                                      -> kernels
 //   <= 8 skinning weights summing to one, 10 / 16 betas +- kid,      -> bm: the batch-major vertex passes; otherwise
@@ -1286,6 +1328,9 @@ void launch_refine_bm(const smplfit_handle* h, RefineArgs ra, const ShareView& s
 //   bm, no weights in the solve, no share_beta, 10 / 11 unknowns,   -> unscaled solves: k_solve_bm on the partial sums;
 //     coarse tables, buffers < 2 GB (solve_bm_plan); SOLVE_BM           else k_gram_combine_bm + k_shape_solve
 //   a fit with k_solve_bm, no scale unknown; PROLOGUE_BM             -> k_prologue_bm, which writes ws.jdT: no k_jd_transpose
+//   k_prologue_bm, Kp == 208, split-bf16 GEMM on an exclusive CU,     -> gemm_planes: k_prologue_bm writes the features as bf16
+//     three products; GEMM_PLANES                                      planes, not as fp32 rows; the GEMM of a shape solve
+//                                                                      reads those
 //   k_prologue_bm, <= 64 joints, toe sources fit; ROT_BM             -> k_rotations_bm: no k_psum_combine behind the passes
 //                                                                      in front of a rotation pass
 //   k_prologue_bm, <= 32 joints, <= 4 adjustable parts a wave; REFINE_BM -> k_refine_bm: no k_psum_combine behind the last
@@ -1316,6 +1361,8 @@ struct Route {
   bool solve_bm = false;             // unscaled, unshared solves are k_solve_bm (on solve_plan)
   SolveBmPlan solve_plan{};
   bool prologue_bm = false;          // k_prologue_bm
+  bool gemm_planes = false;          // k_prologue_bm writes the features as split-bf16 planes (ws.rpP) instead of ws.rp
+                                     // and the GEMMs behind it (launch_normal_equations) read those
   bool jd_transpose = false;         // k_jd_transpose in front of a fit iteration's vertex passes
   bool rot_bm = false;               // k_rotations_bm, on the rows of the tables rot_kind_first / _next (else -1)
   int rot_kind_first = -1, rot_kind_next = -1;
@@ -1347,6 +1394,7 @@ Route route_of(const smplfit_handle* h, int B, const CallShape& c) {
   }
   const bool fit = c.entry == Entry::kFit || c.entry == Entry::kConvert;
   r.prologue_bm = fit && r.solve_bm && !c.scale_mode && tn.prologue_bm;
+  r.gemm_planes = r.prologue_bm && tn.gemm_planes && sf::kGemm3 && gemm_bf16x3_stationary(d) && 12 * d.Vp >= sf::kPlaneGroupBytes / 32;
   r.jd_transpose = r.bm && !r.prologue_bm;
   // (once k_rotations_bm runs nothing writes the instance-major ws.G any more: a model whose refinement stays on
   // k_refine_epilogue — more than 32 joints — gets it from k_gt_to_g in front of that kernel)
@@ -1568,7 +1616,8 @@ int launch_posed_pass(const smplfit_handle* h, const Route& r, const PosedPass& 
 int launch_normal_equations(const smplfit_handle* h, const Route& r, bool joints, SolveWeights w, const float* tj, const float* jw,
                             bool scaled, const Workspace& ws, int B, hipStream_t st) {
   const DevModel& d = h->d;
-  if (int rc = launch_gemm(d, ws, B, st, r.bm)) return rc;
+  // (the features of a shape solve are those of the joint stage in front of it: k_prologue_bm's planes where it ran)
+  if (int rc = launch_gemm(d, ws, B, st, r.bm, r.gemm_planes)) return rc;
   if (!r.bm) {
     const bool gjr = gen_joint_rows(d) && joints;
     return launch_accum_any(d, ws, B, w.v, r.pair_in, st, gjr ? tj : nullptr, gjr && w.j ? jw : nullptr, scaled);
@@ -1809,7 +1858,7 @@ int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_o
   // (first rotations: the rows of the template pass — or of the warm start's LBS pass —; previous rotations: the
   // instance-major ws.G of the warm start's forward stage, if any)
   if (on(0))
-    launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_first, ja.Gprev ? 2 : 0);
+    launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_first, ja.Gprev ? 2 : 0, r.gemm_planes);
   if (o.rotations_only) {
     if (on(0)) hipLaunchKernelGGL(k_copy, dim3(256), dim3(256), 0, st, ws.G, a.orientations, (size_t)B * d.J * 9);
     return post_launch_check();
@@ -1830,7 +1879,7 @@ int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_o
     ja.rj = joints ? ws.rjoints : ws.rjreg;
     ja.rj_shared = 0;
     ja.Gprev = ws.G;
-    if (pb) launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_next, 1);
+    if (pb) launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_next, 1, r.gemm_planes);
   }
   if (!on(1 + 2 * o.num_iter)) return post_launch_check();
   RefineArgs ra = refine_args(tj_rot, joints, jw, o.final_adjust, ws, a.pose_rotvecs, a.shape_betas, a.trans, a.kid_factor,
@@ -2904,9 +2953,11 @@ int smplfit_create(const smplfit_model_desc* desc, int flags, smplfit_handle** o
   }
   {
     int regs = 1 << 20;
-    for (const void* fn : {reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<true>),
-                           reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<false>),
-                           reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3_tiled)}) {
+    std::vector<const void*> fns{reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<true, false>),
+                                 reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<false, false>),
+                                 reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3_tiled)};
+    if constexpr (sf::kGemm3) fns.push_back(reinterpret_cast<const void*>(&k_posedirs_gemm_bf16x3<true, true>));
+    for (const void* fn : fns) {
       hipFuncAttributes fa{};
       regs = std::min(regs, hipFuncGetAttributes(&fa, fn) == hipSuccess ? fa.numRegs : 0);
     }
@@ -3842,6 +3893,8 @@ int smplfit_reload_options(void) {
   return SMPLFIT_OK;
 }
 
+uint64_t smplfit_gemm_plane_launches(void) { return g_gemm_plane_launches.load(std::memory_order_relaxed); }
+
 int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, int reps,
                             void* workspace, size_t workspace_bytes, void* hip_stream,
                             float* avg_ms) {
@@ -3860,7 +3913,8 @@ int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, i
   const int Mp = (int)align_up((size_t)batch, 128);
   auto once = [&]() -> int {
     switch (kernel_id) {
-      case SMPLFIT_KERNEL_POSEDIRS_GEMM: return launch_gemm(d, ws, batch, st, r.bm);
+      // (a shape solve's GEMM, on the features the last fit's prologue left: planes on the route gemm_planes)
+      case SMPLFIT_KERNEL_POSEDIRS_GEMM: return launch_gemm(d, ws, batch, st, r.bm, r.gemm_planes);
       case SMPLFIT_KERNEL_PAIR_GRAM:
         if (!r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "pair-Gram kernel: batch-major path not active");
         launch_residual_bm(h, ws, batch, st, 2);
@@ -3914,7 +3968,7 @@ int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, i
         ja.joint_block_weighted = 0;
         ja.vertex_sa_closed_form = d.general ? 0 : 1;
         // (what a default fit runs: the rotations + k_prologue_bm where that applies)
-        launch_joint_stage_fit(h, ja, ws, batch, st, r.prologue_bm, r.rot_kind_next, 1);
+        launch_joint_stage_fit(h, ja, ws, batch, st, r.prologue_bm, r.rot_kind_next, 1, r.gemm_planes);
         return 0;
       }
       case SMPLFIT_KERNEL_REFINE: {  // (outputs into the workspace: ws.tvs is unused between fits)
@@ -3970,7 +4024,7 @@ int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, i
   // before K5), so caches are in the state the kernel sees in situ; only the target kernel is
   // bracketed by the two events.
   auto pre = [&]() {
-    if (kernel_id == SMPLFIT_KERNEL_SHAPE_ACCUM) launch_gemm(d, ws, batch, st, r.bm);
+    if (kernel_id == SMPLFIT_KERNEL_SHAPE_ACCUM) launch_gemm(d, ws, batch, st, r.bm, r.gemm_planes);
     if ((kernel_id == SMPLFIT_KERNEL_LBS_PARTSUM || kernel_id == SMPLFIT_KERNEL_LBS_LAST) && r.bm) {
       if (r.solve_bm) launch_solve_bm(h, r.solve_plan, ws, batch, st, 1.0f, 0.0f, 1.0f, 0, r.prologue_bm);
       else launch_shape_solve(d, ws, batch, st, 1.0f, 0.0f, 1.0f, r.pair_in, 0);
