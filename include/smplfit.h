@@ -778,6 +778,29 @@ int smplfit_reload_options(void);
  * this count is the one way to tell which ran: tests and A/B tools read it before and after a call. */
 uint64_t smplfit_gemm_plane_launches(void);
 
+/* Launches of the stage kernels of a fit by this process, one count per kernel: which of the lane = instance kernels
+ * (k_rotations_bm, k_prologue_bm, k_solve_bm, k_refine_bm) or of their wave-per-instance counterparts served a call is
+ * decided per call (route_of) and does not show in the results, which agree to rounding or to the bit.  The counts are
+ * process-wide, incremented on the host with relaxed atomics where the kernel is enqueued, and meant for tests and A/B
+ * tools: take the difference around a synchronised call, with no other thread inside the library.  A kernel launched in
+ * two parts for one batch (two instances a wave + the odd last instance) counts once.  An unknown id gives 0. */
+enum smplfit_stage_id {
+  SMPLFIT_STAGE_ROTATIONS_BM = 0,        /* k_rotations_bm: part rotations, lane = instance, one round (<= 32 joints) */
+  SMPLFIT_STAGE_ROTATIONS_BM_ROUNDS = 1, /* k_rotations_bm_rounds: the same in rounds of 32 joints                   */
+  SMPLFIT_STAGE_PROLOGUE_BM_S10 = 2,     /* k_prologue_bm<10>: the shape prologue, 10 shape unknowns                  */
+  SMPLFIT_STAGE_PROLOGUE_BM_S11 = 3,     /* k_prologue_bm<11>: 10 betas + the kid unknown                             */
+  SMPLFIT_STAGE_SOLVE_BM = 4,            /* k_solve_bm: normal-equation combine + solve, lane = instance              */
+  SMPLFIT_STAGE_REFINE_BM = 5,           /* k_refine_bm: refinement + epilogue, lane = instance                       */
+  SMPLFIT_STAGE_GT_TO_G = 6,             /* k_gt_to_g: rotations back to instance-major in front of k_refine_epilogue */
+  SMPLFIT_STAGE_JOINT_STAGE = 7,         /* k_joint_stage (wave per instance): rotations and / or the prologue        */
+  SMPLFIT_STAGE_GRAM_COMBINE = 8,        /* k_gram_combine_bm (fine tables: k_gram_combine_split)                     */
+  SMPLFIT_STAGE_SHAPE_SOLVE = 9,         /* k_shape_solve (wave per instance)                                         */
+  SMPLFIT_STAGE_REFINE_EPILOGUE = 10,    /* k_refine_epilogue (wave per instance)                                     */
+  SMPLFIT_STAGE_PSUM_COMBINE = 11,       /* k_psum_combine (fine tables: k_psum_combine_split)                        */
+  SMPLFIT_STAGE_COUNT = 12,
+};
+uint64_t smplfit_stage_launches(int stage_id);
+
 /* Measurement hook (bench.py's roofline leg): launches ONE kernel of the fit `reps` times on
  * `hip_stream` between two HIP events recorded on that same stream and returns the average
  * duration in milliseconds.  The workspace must hold the state a preceding smplfit_fit_f32 call on

@@ -464,9 +464,14 @@ class OracleFitter:
 
     # -- dependent refinement, level-batched branch (pt/bodyfitter.py:1418-1544) -------------------
     def fit_global_rotations_dependent(self, tv, tj, rv, rj_true, vw, jw, G, beta, trans,
-                                       rest_joints=None, scale_corr=None):
+                                       rest_joints=None, scale_corr=None, return_cov=False):
         """beta: all shape unknowns (betas + kid when enabled); ``rest_joints`` overrides the rest-pose
-        joints computed from it (known-shape entry point); ``scale_corr`` (B,1,1) scales them (:1449-1450)."""
+        joints computed from it (known-shape entry point); ``scale_corr`` (B,1,1) scales them (:1449-1450).
+
+        ``return_cov``: also a dict in the form of ``fit_global_rotations(return_cov=True)`` with what each adjustable
+        part's DELTA rotation was computed from — ``cov`` (B, J, 3, 3) the matrix handed to ``proj_so3``, ``kind`` (J,)
+        PART_LEAF for every adjustable part (each is a projection; -1: not adjusted), ``prev`` (B, J, 3, 3) the rotation
+        the part had before (the result is ``proj_so3(cov) @ prev``) — and zeros for the bone entries."""
         m, dt, J, par = self.m, self.m.dtype, self.m.J, self.m.parents
         B = tv.shape[0]
         if tj is None:
@@ -484,6 +489,7 @@ class OracleFitter:
         bones = j - jpar
         raw, st, sa, sw = self.part_sums(tv, rv, vw)
         rots = G.copy()
+        cov = np.zeros((B, J, 3, 3), dt)
         pos = np.zeros((B, J, 3), dt)
         pos[:, 0] = j[:, 0] + trans
         for k in range(self.adj_last + 1):
@@ -499,12 +505,19 @@ class OracleFitter:
                 if jw is not None:
                     dfl = dfl * jw[:, js, None]
                 A = A + np.swapaxes(est, 1, 2) @ dfl
+                cov[:, i] = A
                 new[i] = proj_so3(A.astype(dt)) @ G[:, i]
             for i, Rn in new.items():
                 rots[:, i] = Rn
         if self.smpl_family:
             rots[:, 10] = rots[:, 7]
             rots[:, 11] = rots[:, 8]
+        if return_cov:
+            kind = np.full(J, -1)
+            kind[[i for lv in self.adj_levels for i in lv]] = self.PART_LEAF
+            zero = lambda *sh: np.zeros((B, J) + sh, dt)  # noqa: E731
+            return rots, dict(cov=cov, kind=kind, prev=np.array(G, dt), twist_sc=zero(2), bone_ref=zero(3),
+                              bone_tgt=zero(3), bone_ref_len=zero(), bone_tgt_len=zero())
         return rots
 
     # -- driver (pt/bodyfitter.py:283-549) ----------------------------------------------------------

@@ -27,6 +27,12 @@ SMPLFIT_CREATE_HOST_ONLY = 1
 SMPLFIT_TRANSFER_NEGATE_X = 2  # smplfit_transfer_create: x -> -x after the product (the mirror)
 SMPLFIT_ABI_VERSION = 7  # include/smplfit.h; checked against smplfit_abi_version() when the library is loaded
 
+# smplfit_stage_id: the stage kernels smplfit_stage_launches counts
+STAGE_IDS = dict(
+    rotations_bm=0, rotations_bm_rounds=1, prologue_bm_s10=2, prologue_bm_s11=3, solve_bm=4, refine_bm=5, gt_to_g=6,
+    joint_stage=7, gram_combine=8, shape_solve=9, refine_epilogue=10, psum_combine=11,
+)
+
 TABLE_IDS = dict(
     part_assignment=0, sort_perm=1, part_type=2, fk_order=3, fk_level_start=4, adj_flag=5,
     used_part=6, segments=7, vertex_pieces=8, cell_counts=9, joint_pairs=10,
@@ -54,7 +60,7 @@ EXPORTED_SYMBOLS = [
     'smplfit_fit_known_shape_backward_workspace_bytes', 'smplfit_fit_known_shape_backward_f32',
     'smplfit_share_segments_create', 'smplfit_share_segments_destroy', 'smplfit_share_segments_batch',
     'smplfit_share_segments_get_table', 'smplfit_share_segments_workspace_bytes', 'smplfit_fit_segments_f32',
-    'smplfit_shape_solve_segments_f32', 'smplfit_gemm_plane_launches',
+    'smplfit_shape_solve_segments_f32', 'smplfit_gemm_plane_launches', 'smplfit_stage_launches',
 ]  # fmt: skip
 
 _fp = C.POINTER(C.c_float)
@@ -397,6 +403,9 @@ def load():
     if hasattr(lib, 'smplfit_gemm_plane_launches'):  # (as above)
         lib.smplfit_gemm_plane_launches.argtypes = []
         lib.smplfit_gemm_plane_launches.restype = C.c_uint64
+    if hasattr(lib, 'smplfit_stage_launches'):  # (as above)
+        lib.smplfit_stage_launches.argtypes = [i32]
+        lib.smplfit_stage_launches.restype = C.c_uint64
     if os.environ.get('SMPLFIT_LIB') and not hasattr(lib, 'smplfit_abi_version'):
         _lib = lib  # an older build loaded by the A/B tools (tools/ab_fit.py): no version / share-table exports
         return lib
@@ -543,6 +552,13 @@ def gemm_plane_launches() -> int:
     """Posedirs GEMM launches of this process that read the prologue kernel's split-bf16 feature planes
     (``SMPLFIT_GEMM_PLANES=0``: none); the results do not show which front end ran, this count does."""
     return int(load().smplfit_gemm_plane_launches())
+
+
+def stage_launches() -> dict:
+    """Launches of each stage kernel by this process (``STAGE_IDS``): process-wide host counters meant for tests and
+    A/B tools, which take the difference around a synchronised call to see the route it took."""
+    lib = load()
+    return {k: int(lib.smplfit_stage_launches(v)) for k, v in STAGE_IDS.items()}
 
 
 class Transfer:

@@ -1855,10 +1855,18 @@ __global__ __launch_bounds__(64 * kRefWaves) void k_rotations_bm_rounds(DevModel
       for (int k = 0; k < 9; ++k) G[k] = a.Gim[((size_t)b * J + j) * 9 + k];
     }
   };
-  auto store_G = [&](int j, const float (&R)[9], const float (&Gp)[9]) {  // compose with the previous rotation (:422-433)
+  // compose with the previous rotation (:422-433).  Two call sites (a round; the toes behind the last barrier): the
+  // product is written as explicit fused steps, so that the compiler cannot contract it one way here and another way
+  // there — a toe whose previous rotation has its foot's bits gets its foot's bits (as in k_rotations_bm, where both go
+  // through one site, and in k_joint_stage)
+  auto store_G = [&](int j, const float (&R)[9], const float (&Gp)[9]) {
     float G[9];
     if (a.gprev_mode != 0) {
-      sf::m3_mul(R, Gp, G);
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          G[r * 3 + c] = __builtin_fmaf(R[r * 3 + 2], Gp[6 + c], __builtin_fmaf(R[r * 3], Gp[c], R[r * 3 + 1] * Gp[3 + c]));
     } else {
 #pragma unroll
       for (int k = 0; k < 9; ++k) G[k] = R[k];

@@ -569,6 +569,12 @@ const Tuning& tune() {
   return *t;
 }
 
+// Launches of the stage kernels since the process started, by smplfit_stage_id (smplfit_stage_launches): which stage
+// kernels served a call is the route's decision and does not show in the results.  Each count is bumped at the one
+// place its kernel is enqueued; host side only.
+std::atomic<uint64_t> g_stage_launches[SMPLFIT_STAGE_COUNT] = {};
+inline void count_stage(int id) { g_stage_launches[id].fetch_add(1, std::memory_order_relaxed); }
+
 // joint rows of the current rotations, instance-innermost, for k_pair_gram_bm
 void launch_jd_transpose(const DevModel& d, const Workspace& ws, int B, hipStream_t st) {
   const int Mp = (int)align_up((size_t)B, 128), Ns = d.J * sf::jd_stride(d.S), Np = (int)align_up((size_t)Ns, 64);
@@ -587,6 +593,7 @@ ShareView share_view(const smplfit_handle* h, int kind, int B) {
 }
 dim3 share_grid(const ShareView& sv, int Mp) { return dim3(Mp / 64, sv.ncells / sv.mult / kBW); }
 void launch_psum_combine(const DevModel& d, const ShareView& sv, const Workspace& ws, int B, int Mp, hipStream_t st) {
+  count_stage(SMPLFIT_STAGE_PSUM_COMBINE);
   if (sv.fine) hipLaunchKernelGGL(k_psum_combine_split<8>, dim3(Mp / 64, d.J), dim3(64 * 8), 0, st, d, sv, ws, B, Mp);
   else hipLaunchKernelGGL(k_psum_combine, dim3((B + 255) / 256, d.J), dim3(256), 0, st, d, sv, ws, B, Mp);
 }
@@ -634,6 +641,7 @@ void launch_residual_bm_s(const smplfit_handle* h, const Workspace& ws, int B, h
   if (which & 2) {
     hipLaunchKernelGGL((k_pair_gram_bm<S>), dim3(pair_gram_workgroups(d.J, d.jt.np), Mp / 64), dim3(64 * kPgWaves), 0, st, d, ws, B, Mp);
   }
+  if (which & 4) count_stage(SMPLFIT_STAGE_GRAM_COMBINE);
   if ((which & 4) && sv.fine)
     hipLaunchKernelGGL((k_gram_combine_split<S, 16>), dim3(Mp / 64, S + 3 + 3 * d.J + sf::ne_ng(S)), dim3(64 * 16), 0,
                        st, d, sv, ws, B, Mp);
@@ -1123,6 +1131,7 @@ void launch_forward_joint(const DevModel& d, const ForwardArgs& fa, const Worksp
 void launch_joint_stage(const DevModel& d, JointStageArgs ja, const Workspace& ws, int B, hipStream_t st) {
   ja.B = B;
   ja.b0 = 0;
+  count_stage(SMPLFIT_STAGE_JOINT_STAGE);
   if (stage_half(d, 1, B)) {
     if (B / 2 > 0) hipLaunchKernelGGL(k_joint_stage<32>, dim3(B / 2), dim3(64), 2 * joint_lds(d), st, d, ja, ws);
     if (B & 1) {  // the odd last instance: a launch of its own (no wave works on one instance twice)
@@ -1137,6 +1146,7 @@ void launch_joint_stage(const DevModel& d, JointStageArgs ja, const Workspace& w
 void launch_refine(const DevModel& d, RefineArgs ra, const Workspace& ws, int B, hipStream_t st) {
   ra.B = B;
   ra.b0 = 0;
+  count_stage(SMPLFIT_STAGE_REFINE_EPILOGUE);
   if (stage_half(d, 4, B)) {
     if (B / 2 > 0) hipLaunchKernelGGL(k_refine_epilogue<32>, dim3(B / 2), dim3(64), 2 * joint_lds(d, 1), st, d, ra, ws);
     if (B & 1) {
@@ -1153,6 +1163,7 @@ void launch_shape_solve(const DevModel& d, const Workspace& ws, int B, hipStream
                         float kid_reg, int pair_form, int use_ref, int mode = 0, int first = 0, int count = -1,
                         int cen_b0 = 0, const int32_t* row_seg = nullptr) {
   if (count < 0) count = B;
+  count_stage(SMPLFIT_STAGE_SHAPE_SOLVE);
   if (d.general) {
     ensure_max_lds(reinterpret_cast<const void*>(&k_shape_solve<64, true>));
     hipLaunchKernelGGL((k_shape_solve<64, true>), dim3(count), dim3(d.S > 128 ? 1024 : d.S > 64 ? 256 : 64), solve_lds(d), st, d,
@@ -1219,6 +1230,7 @@ void launch_solve_bm_s(const smplfit_handle* h, const Workspace& ws, int B, hipS
   const DevModel& d = h->d;
   const int Mp = (int)align_up((size_t)B, 128);
   const int groups = (int)align_up((size_t)Mp / kSolveIB, 32);
+  count_stage(SMPLFIT_STAGE_SOLVE_BM);
   if (p.lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(&k_solve_bm<S, kSolveIB>));
   hipLaunchKernelGGL((k_solve_bm<S, kSolveIB>), dim3(groups), dim3(64 * kSolveWaves), p.lds, st, d, p.sv, ws, B, Mp, p.a);
 }
@@ -1246,6 +1258,7 @@ void launch_prologue_bm(const smplfit_handle* h, const JointStageArgs& ja, const
   PrologueArgs pa{ja.tj, ja.jw, ja.joint_block, ja.joint_block_weighted, ja.vertex_sa_closed_form, B, planes ? 1 : 0};
   const size_t lds = (size_t)(kProWaves / 2) * (sf::ne_size(d.S) + 1) * 64 * 4;
   const dim3 grid(Mp / 64, prologue_splits(d.J));
+  count_stage(d.S == 11 ? SMPLFIT_STAGE_PROLOGUE_BM_S11 : SMPLFIT_STAGE_PROLOGUE_BM_S10);
   if (d.S == 11) {
     if (lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(&k_prologue_bm<11>));
     hipLaunchKernelGGL(k_prologue_bm<11>, grid, dim3(64 * kProWaves), lds, st, d, pa, ws, Mp);
@@ -1267,6 +1280,7 @@ void launch_rotations_bm(const smplfit_handle* h, const JointStageArgs& ja, int 
   static_assert(sizeof(ra.slot) == sizeof(h->t.rot_slots), "RotArgs::slot holds HostTables::rot_slots");
   std::memcpy(ra.slot, h->t.rot_slots, sizeof(ra.slot));
   const size_t lds = (size_t)rot_bm_lds_floats(d.J) * 4;
+  count_stage(d.J <= kRotJoints * kRefWaves ? SMPLFIT_STAGE_ROTATIONS_BM : SMPLFIT_STAGE_ROTATIONS_BM_ROUNDS);
   if (d.J <= kRotJoints * kRefWaves) {
     if (lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(&k_rotations_bm));
     hipLaunchKernelGGL(k_rotations_bm, dim3((B + 63) / 64), dim3(64 * kRefWaves), lds, st, d, ra, share_view(h, rot_kind, B), ws, Mp);
@@ -1305,6 +1319,7 @@ void launch_refine_bm(const smplfit_handle* h, RefineArgs ra, const ShareView& s
   RefGroups rg;
   std::memcpy(rg.wave, h->t.refine_waves, sizeof(rg.wave));
   const size_t lds = (size_t)refine_bm_lds_floats(d.J) * 4;
+  count_stage(SMPLFIT_STAGE_REFINE_BM);
   if (d.S == 11) {
     if (lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(&k_refine_bm<11>));
     hipLaunchKernelGGL(k_refine_bm<11>, dim3((B + 63) / 64), dim3(64 * kRefWaves), lds, st, d, ra, sv, ws, ws.rjoints, Mp, rg);
@@ -1895,8 +1910,10 @@ int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_o
   if (r.refine_bm) {
     launch_refine_bm(h, ra, share_view(h, r.refine_kind, B), ws, B, st);
   } else {
-    if (r.gt_to_g)  // (k_rotations_bm left the rotations instance-innermost only)
+    if (r.gt_to_g) {  // (k_rotations_bm left the rotations instance-innermost only)
+      count_stage(SMPLFIT_STAGE_GT_TO_G);
       hipLaunchKernelGGL(k_gt_to_g, dim3((B + 63) / 64, (d.J + 15) / 16), dim3(256), 0, st, ws, d.J, B, (int)align_up((size_t)B, 128));
+    }
     launch_refine(d, ra, ws, B, st);
   }
   return post_launch_check();
@@ -3894,6 +3911,10 @@ int smplfit_reload_options(void) {
 }
 
 uint64_t smplfit_gemm_plane_launches(void) { return g_gemm_plane_launches.load(std::memory_order_relaxed); }
+uint64_t smplfit_stage_launches(int stage_id) {
+  if (stage_id < 0 || stage_id >= SMPLFIT_STAGE_COUNT) return 0;
+  return g_stage_launches[stage_id].load(std::memory_order_relaxed);
+}
 
 int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, int reps,
                             void* workspace, size_t workspace_bytes, void* hip_stream,

@@ -27,6 +27,18 @@ def test_header_symbols_exported(lib):
         assert getattr(lib, s) is not None
 
 
+def test_stage_launch_counters(lib):
+    """smplfit_stage_launches: one count per id of enum smplfit_stage_id (the header's values are the binding's), 0 for an
+    id the library does not know, and nothing has been launched in a process without a GPU."""
+    hdr = open(osp.join(ROOT, 'include', 'smplfit.h')).read()
+    enum = {k.lower(): int(v) for k, v in re.findall(r'SMPLFIT_STAGE_([A-Z0-9_]+) = (\d+)', hdr)}
+    count = enum.pop('count')
+    assert enum == _lib.STAGE_IDS and sorted(enum.values()) == list(range(count))
+    for bad in (-1, count, count + 1, 1 << 20):
+        assert lib.smplfit_stage_launches(bad) == 0
+    assert all(v == 0 for v in _lib.stage_launches().values())
+
+
 def test_build_id_covers_csrc():
     """Every file under csrc/ (and the public header) enters needs_build() and the build id smplfit_version() reports:
     an edit to any kernel file must change the id the profiles are tied to (round 5: kernels_gen.inc was missing)."""

@@ -8,15 +8,16 @@ weight; and a non-finite instance beside good ones.
 Routes.  The rotation-pass entry point always runs the wave-per-instance kernels (route_of: rotations_only is never
 batch-major), on the fine or the coarse cell tables; the shape-solve entry point runs k_gram_combine + k_shape_solve on
 the fine tables and the lane = instance k_solve_bm on the coarse ones (forced at a small batch with SMPLFIT_FINE_B=0),
-the accumulate kernel with weights.  k_rotations_bm / k_prologue_bm / k_refine_bm only run inside a whole fit and stay
-with their A/B tests in tests/test_gpu_parity.py."""
+the accumulate kernel with weights.  k_rotations_bm / k_prologue_bm / k_refine_bm only run inside a whole fit: they are
+held to the same oracles, stage by stage and on the same families, by tests/test_gpu_stage_chain.py.  Which solve
+kernels ran is read from the library's launch counters (smplfit_stage_launches)."""
 
 import numpy as np
 import pytest
 import torch
 
 import stage_util as S
-import util
+from smplfitter_amd import _lib
 from test_gpu_parity import get_model, t, to_np
 
 pytestmark = pytest.mark.gpu
@@ -33,14 +34,8 @@ def dev():
 def setup(name, model_root, golden, dev):
     """Model, oracles, families and the oracles' rotation passes of one model kind: computed once, shared, read only."""
     if name not in _cache:
-        g = golden(name)
-        kind, md = util.load_md(model_root, name, g)
-        m, f = get_model(model_root, name, g, dev)
-        om64, of64 = util.make_oracle(md, kind, np.float64)
-        _, of32 = util.make_oracle(md, kind, np.float32)
-        fams = S.families(om64, of64)
-        rot = {k: (S.oracle_rotations(of64, fam), S.oracle_rotations(of32, fam)[0]) for k, fam in fams.items()}
-        _cache[name] = dict(m=m, f=f, of64=of64, of32=of32, fams=fams, rot=rot)
+        m, f = get_model(model_root, name, golden(name), dev)
+        _cache[name] = dict(S.host_setup(name, model_root, golden), m=m, f=f)
     return _cache[name]
 
 
@@ -117,10 +112,8 @@ def test_solve_bm_rows_vs_oracle(Bn, model_root, golden, dev, smplfit_env, capsy
     same source must agree bit for bit whatever their lane or workgroup.  That the coarse route was taken is shown by the
     bits: the fine tables sum in another order, so the same call without SMPLFIT_FINE_B=0 must differ somewhere; with
     SMPLFIT_SOLVE_BM=0 (k_gram_combine_bm + k_shape_solve on the same tables, sums in k_solve_bm's order by design,
-    test_solve_bm_matches_two_kernels) it must not.  The library reports no per-call route (see route_of), so a gap
-    remains: the 'differs from fine' assertion proves the coarse tables were used, not that k_solve_bm ran instead of
-    k_gram_combine_bm + k_shape_solve.  If solve_bm_plan() silently returned !ok, all three variants would still pass.
-    Only a route query in the library would close that, which is outside what a test can add."""
+    test_solve_bm_matches_two_kernels) it must not.  Which kernels solved is read from the launch counters: k_solve_bm
+    and neither k_gram_combine_bm nor k_shape_solve in the 'coarse' variant, the reverse in 'coarse_two_kernels'."""
     c = setup('smpl', model_root, golden, dev)
     rows = np.arange(Bn) % S.B
     with capsys.disabled():
@@ -134,7 +127,15 @@ def test_solve_bm_rows_vs_oracle(Bn, model_root, golden, dev, smplfit_env, capsy
                              ('coarse_two_kernels', dict(SMPLFIT_FINE_B='0', SMPLFIT_SOLVE_BM='0'))):
                 for k in ('SMPLFIT_FINE_B', 'SMPLFIT_SOLVE_BM'):
                     smplfit_env(k, env.get(k))
+                torch.cuda.synchronize()
+                before = _lib.stage_launches()
                 out[tag] = to_np(c['f']._shape_solve(*args, beta_regularizer=1.0))
+                torch.cuda.synchronize()
+                ran = {k: v - before[k] for k, v in _lib.stage_launches().items()}
+                if tag == 'coarse':
+                    assert ran['solve_bm'] == 1 and ran['gram_combine'] == 0 and ran['shape_solve'] == 0, (tag, ran)
+                elif tag == 'coarse_two_kernels':
+                    assert ran['solve_bm'] == 0 and ran['gram_combine'] == 1 and ran['shape_solve'] == 1, (tag, ran)
             r64, r32, mean64 = solve_refs(c, 'smpl', family, 'reg1', G, 1.0, None, None)
             for tag in out:
                 S.check_solve('smpl', family, 'reg1', out[tag], r32, r64, mean64, False, f'device B={Bn} {tag}', rows=rows)
