@@ -801,6 +801,13 @@ enum smplfit_stage_id {
 };
 uint64_t smplfit_stage_launches(int stage_id);
 
+/* Part-rotation launches of this process that ran as k_rotations_spread: a joint per wave, the joints of a block of 64
+ * instances spread over ceil(J / 8) workgroups.  Fit calls of up to 4096 instances (SMPLFIT_ROT_SPREAD_B) run it
+ * wherever SMPLFIT_STAGE_ROTATIONS_BM / _ROUNDS count; larger calls, and every call with SMPLFIT_ROT_SPREAD=0, run
+ * k_rotations_bm / k_rotations_bm_rounds.  Both forms give the same bits and count under the same stage id, so this
+ * count is the one way to tell which ran. */
+uint64_t smplfit_rotation_spread_launches(void);
+
 /* Measurement hook (bench.py's roofline leg): launches ONE kernel of the fit `reps` times on
  * `hip_stream` between two HIP events recorded on that same stream and returns the average
  * duration in milliseconds.  The workspace must hold the state a preceding smplfit_fit_f32 call on

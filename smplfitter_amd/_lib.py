@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     'smplfit_share_segments_create', 'smplfit_share_segments_destroy', 'smplfit_share_segments_batch',
     'smplfit_share_segments_get_table', 'smplfit_share_segments_workspace_bytes', 'smplfit_fit_segments_f32',
     'smplfit_shape_solve_segments_f32', 'smplfit_gemm_plane_launches', 'smplfit_stage_launches',
+    'smplfit_rotation_spread_launches',
 ]  # fmt: skip
 
 _fp = C.POINTER(C.c_float)
@@ -406,6 +407,9 @@ def load():
     if hasattr(lib, 'smplfit_stage_launches'):  # (as above)
         lib.smplfit_stage_launches.argtypes = [i32]
         lib.smplfit_stage_launches.restype = C.c_uint64
+    if hasattr(lib, 'smplfit_rotation_spread_launches'):  # (as above)
+        lib.smplfit_rotation_spread_launches.argtypes = []
+        lib.smplfit_rotation_spread_launches.restype = C.c_uint64
     if os.environ.get('SMPLFIT_LIB') and not hasattr(lib, 'smplfit_abi_version'):
         _lib = lib  # an older build loaded by the A/B tools (tools/ab_fit.py): no version / share-table exports
         return lib
@@ -552,6 +556,12 @@ def gemm_plane_launches() -> int:
     """Posedirs GEMM launches of this process that read the prologue kernel's split-bf16 feature planes
     (``SMPLFIT_GEMM_PLANES=0``: none); the results do not show which front end ran, this count does."""
     return int(load().smplfit_gemm_plane_launches())
+
+
+def rotation_spread_launches() -> int:
+    """Part-rotation launches of this process that ran as ``k_rotations_spread``, a joint per wave
+    (calls of up to 4096 instances; ``SMPLFIT_ROT_SPREAD=0``: none); both forms give the same bits and the same stage counts, this count tells them apart."""
+    return int(load().smplfit_rotation_spread_launches())
 
 
 def stage_launches() -> dict:

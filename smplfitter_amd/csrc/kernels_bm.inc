@@ -1987,6 +1987,222 @@ __global__ __launch_bounds__(64 * kRefWaves) void k_rotations_bm_rounds(DevModel
   }
 }
 
+// K1r spread over the chip (calls of up to kRotSpreadMaxBatch instances; the two kernels above serve larger ones and
+// SMPLFIT_ROT_SPREAD=0): ONE joint per wave.
+// Workgroup (blk, y) owns the 64 instances of block blk and the joints y * kRefWaves .. + kRefWaves - 1; wave w fits the
+// part of joint j = y * kRefWaves + w for its 64 lanes.  A toe (toe_src[j] >= 0) fits its FOOT's part itself — the same
+// inputs through the same code, so the foot's bits — and composes with its own previous rotation: no rotation crosses
+// waves, LDS holds only the block's transposed target / reference joints, and the one barrier is the one behind them.
+// Every row of the part's sums is requested before the first add (kRotAhead rows a batch: the coarse cell tables give a
+// part at most 7 rows, so one batch), added in table order: the sums, and with them every rotation, keep the bits of the
+// kernels above.  The chain of a wave is one memory round trip, one projection and one row store.
+// grid (Mp / 64, ceil(J / kRefWaves)), block 64 * kRefWaves.
+//
+// Same bits as the kernels above, for the same sf:: code, needs FOUR expressions stated as the fused steps the compiler
+// gives every site of those kernels (it contracts a * b + c * d by how it happens to pack the products of an inlined site
+// in pairs, and packs this kernel's single site differently; each was a last bit of a rotation): the centred covariance
+// (centered_cov below); inside the swing + twist the middle element of H = R_swing A^T, which those sites leave over
+// from four pairs and form as (third product, rounded) + fma(second, (first product, rounded)) — swing_twist_k1r is
+// sf::swing_twist with that one statement added —; the weighted sums of the multi-joint Kabsch; the first element of the
+// composition on models of up to 32 joints.  The kernels above still leave these to the compiler: a compiler that
+// packs them otherwise moves THEIR bits, and tests/test_gpu_rot_spread.py fails until the steps here follow.
+__device__ inline void swing_twist_k1r(const float* b_ref, const float* b_tgt, const float* A, float* R) {  // sf::swing_twist
+  const float nr = sqrtf(b_ref[0] * b_ref[0] + b_ref[1] * b_ref[1] + b_ref[2] * b_ref[2]);
+  const float nt = sqrtf(b_tgt[0] * b_tgt[0] + b_tgt[1] * b_tgt[1] + b_tgt[2] * b_tgt[2]);
+  const float br[3] = {sf::divide_no_nan(b_ref[0], nr), sf::divide_no_nan(b_ref[1], nr), sf::divide_no_nan(b_ref[2], nr)};
+  const float bt[3] = {sf::divide_no_nan(b_tgt[0], nt), sf::divide_no_nan(b_tgt[1], nt), sf::divide_no_nan(b_tgt[2], nt)};
+  float Rsw[9], H[9];
+  sf::align_unit_vectors(br, bt, Rsw);
+  sf::m3_mult(Rsw, A, H);  // H = R_swing A^T
+  {
+#pragma clang fp contract(off)
+    const float p3 = Rsw[3] * A[3], p5 = Rsw[5] * A[5];
+    H[4] = p5 + __builtin_fmaf(Rsw[4], A[4], p3);
+  }
+  const float trH = H[0] + H[4] + H[8];
+  float Hb[3];
+  sf::m3_vec(H, bt, Hb);
+  const float bHb = bt[0] * Hb[0] + bt[1] * Hb[1] + bt[2] * Hb[2];
+  const float vee[3] = {H[5] - H[7], H[6] - H[2], H[1] - H[3]};
+  const float ang = atan2f(bt[0] * vee[0] + bt[1] * vee[1] + bt[2] * vee[2], trH - bHb);
+  const float rv[3] = {bt[0] * ang, bt[1] * ang, bt[2] * ang};
+  float Rtw[9];
+  sf::rotvec2mat(rv, Rtw);
+  sf::m3_mul(Rtw, Rsw, R);
+}
+constexpr int kRotAhead = 8;  // part-sum rows in flight per wave (16 registers each)
+constexpr int kRotSpreadMaxBatch = 4096;  // most instances of a call that take this form (route_of; SMPLFIT_ROT_SPREAD_B)
+__host__ __device__ inline int rot_spread_lds_floats(int J) { return 2 * 3 * J * kRefPitch; }
+__global__ __launch_bounds__(64 * kRefWaves) void k_rotations_spread(DevModel m, RotArgs a, ShareView sv, Workspace ws, int Mp) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const sf::JointTabs& tb = m.jt;
+  const int J = tb.J, J3 = 3 * J, B = a.B;
+  float* tjs = smem;                   // [3 J][65] centred target joints
+  float* rjs = tjs + J3 * kRefPitch;   // [3 J][65] reference joints
+  const int tid = threadIdx.x, lane = tid & 63, blk = blockIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = blockIdx.y * kRefWaves + wave;  // the joint whose row of ws.GT the wave writes
+  const bool live = j < J;
+  const int f = live && tb.toe_src[j] >= 0 ? tb.toe_src[j] : live ? j : 0;  // the part it fits (a toe: its foot's)
+  const int bcol = blk * 64 + lane, b = bcol < B ? bcol : B - 1;
+  const size_t pitch = (size_t)Mp;
+  const int i0 = blk * 64, ni = min(64, B - i0);
+  float* GT = ws.GT + bcol;
+  // ---- every global read: the part sums (rows in table order), the previous rotation, the block's joints
+  float ps[sf::kPsum], Gp[9];
+#pragma unroll
+  for (int k = 0; k < sf::kPsum; ++k) ps[k] = 0.f;
+  if (live) {
+    if (tb.part_type[f] >= 2) {  // bone and leaf parts: the part sums of the vertices (k_psum_combine: rows in table order)
+      const int q0 = sv.aux_start[f], q1 = sv.aux_start[f + 1];
+      for (int q = q0; q < q1; q += kRotAhead) {
+        float v[kRotAhead][sf::kPsum];
+#pragma unroll
+        for (int r = 0; r < kRotAhead; ++r)
+          if (q + r < q1) {
+            const float* src = ws.psumP + (size_t)sv.aux_rows[q + r] * sf::kPsum * pitch + bcol;
+#pragma unroll
+            for (int k = 0; k < sf::kPsum; ++k) v[r][k] = src[(size_t)k * pitch];
+          }
+#pragma unroll
+        for (int r = 0; r < kRotAhead; ++r)
+          if (q + r < q1) {
+#pragma unroll
+            for (int k = 0; k < sf::kPsum; ++k) ps[k] += v[r][k];
+          }
+      }
+    }
+    if (a.gprev_mode == 1) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) Gp[k] = GT[(size_t)(j * 9 + k) * pitch];
+    } else if (a.gprev_mode == 2) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) Gp[k] = a.Gim[((size_t)b * J + j) * 9 + k];
+    }
+  }
+  {
+    constexpr int NH = (3 * kRotMaxJ + 63) / 64;
+    float tv[64 / kRefWaves][NH], rv[64 / kRefWaves][NH];
+#pragma unroll
+    for (int u = 0; u < 64 / kRefWaves; ++u) {
+      const int inst = wave + u * kRefWaves, ii = inst < ni ? inst : ni - 1;
+      const float* tg = a.tj + (size_t)(i0 + ii) * J3;
+      const float* rg = a.rj_shared ? a.rj : a.rj + (size_t)(i0 + ii) * J3;
+#pragma unroll
+      for (int h = 0; h < NH; ++h)
+        if (64 * h < J3) {
+          const int k = lane + 64 * h, kk = k < J3 ? k : J3 - 1;
+          tv[u][h] = tg[kk];
+          rv[u][h] = rg[kk];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 64 / kRefWaves; ++u) {
+      const int inst = wave + u * kRefWaves;
+#pragma unroll
+      for (int h = 0; h < NH; ++h) {
+        const int k = lane + 64 * h;
+        if (k < J3) {
+          tjs[k * kRefPitch + inst] = tv[u][h];
+          rjs[k * kRefPitch + inst] = rv[u][h];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (!live) return;  // (a wave behind the last joint only took part in the transpose)
+  auto TJ = [&](int mj, int c) { return tjs[(mj * 3 + c) * kRefPitch + lane]; };
+  auto RJ = [&](int mj, int c) { return rjs[(mj * 3 + c) * kRefPitch + lane]; };
+  // sf::centered_cov as the fused steps of the kernels above (left to the compiler, one element stays unfused here: a
+  // last bit that the hard targets of tests/test_gpu_stage_chain.py turn into 6e-4 of a rotation)
+  auto centered_cov = [](const float* raw, const float* st, const float* sa, float sw, const float* ct, const float* ca, float* A) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        A[r * 3 + c] = __builtin_fmaf(sw, ct[r] * ca[c], __builtin_fmaf(-ct[r], sa[c], __builtin_fmaf(-st[r], ca[c], raw[r * 3 + c])));
+  };
+  // ---- the part's rotation (sf::joint_stage, per lane)
+  const int type = tb.part_type[f];
+  float R[9];
+  sf::m3_identity(R);
+  if (type != 0) {
+    const int c0 = tb.cas_start[f], n = tb.cas_start[f + 1] - c0;
+    const float inv = 1.0f / (float)n;
+    float ct[3] = {0, 0, 0}, ca[3] = {0, 0, 0};
+    for (int q = 0; q < n; ++q) {
+      const int mj = tb.cas_flat[c0 + q];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        ct[c] += inv * TJ(mj, c);
+        ca[c] += inv * RJ(mj, c);
+      }
+    }
+    float A[9];
+    if (type == 1) {  // multi-joint part: Kabsch on its joints only (:1361-1383)
+      float raw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, st[3] = {0, 0, 0}, sa[3] = {0, 0, 0}, sw = 0;
+      for (int q = 0; q < n; ++q) {
+        const int mj = tb.cas_flat[c0 + q];
+        const float w = a.jw ? a.jw[(size_t)b * J + mj] : 1.0f;
+        const float t[3] = {TJ(mj, 0), TJ(mj, 1), TJ(mj, 2)}, rj[3] = {RJ(mj, 0), RJ(mj, 1), RJ(mj, 2)};
+        // (the steps of k_rotations_bm's sites, which matter once w is not 1: every sum fused but sa[0], whose product the
+        // compiler packs with w there)
+        float aa[3];
+        {
+#pragma clang fp contract(off)
+          aa[0] = rj[0] * w, aa[1] = rj[1] * w, aa[2] = rj[2] * w;
+          sa[0] = sa[0] + aa[0];
+        }
+        sa[1] = __builtin_fmaf(rj[1], w, sa[1]);
+        sa[2] = __builtin_fmaf(rj[2], w, sa[2]);
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) raw[r * 3 + c] = __builtin_fmaf(t[r], aa[c], raw[r * 3 + c]);
+          st[r] = __builtin_fmaf(t[r], w, st[r]);
+        }
+        sw += w;
+      }
+      centered_cov(raw, st, sa, sw, ct, ca, A);
+    } else {
+      centered_cov(ps, ps + 9, ps + 12, ps[15], ct, ca, A);
+    }
+    if (type == 2) {  // bone part: swing + twist (:1389-1412)
+      const int k0 = tb.cas_flat[c0], k1 = tb.cas_flat[c0 + 1];
+      float br[3], bt[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        br[c] = RJ(k1, c) - RJ(k0, c);
+        bt[c] = TJ(k1, c) - TJ(k0, c);
+      }
+      swing_twist_k1r(br, bt, A, R);
+    } else {
+      sf::proj_so3(A, R);
+    }
+  }
+  // ---- compose with the joint's own previous rotation (:422-433; explicit fused steps, as k_rotations_bm_rounds); row
+  // j of ws.GT
+  float G[9];
+  if (a.gprev_mode != 0) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        G[r * 3 + c] = __builtin_fmaf(R[r * 3 + 2], Gp[6 + c], __builtin_fmaf(R[r * 3], Gp[c], R[r * 3 + 1] * Gp[3 + c]));
+    if (J <= kRotJoints * kRefWaves) {  // (k_rotations_bm leaves sf::m3_mul to the compiler, which pairs eight elements
+                                        // into the steps above and forms the first one like this at all four sites)
+#pragma clang fp contract(off)
+      const float p0 = R[0] * Gp[0], p2 = R[2] * Gp[6];
+      G[0] = __builtin_fmaf(R[1], Gp[3], p0) + p2;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) G[k] = R[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) GT[(size_t)(j * 9 + k) * pitch] = G[k];
+}
+
 // the rotations instance-innermost (ws.GT) -> instance-major (ws.G): the wave-per-instance refinement of a model whose
 // joints do not fit k_refine_bm reads them there.  grid (Mp / 64, chunks of 16 joints), block 256.
 __global__ __launch_bounds__(256) void k_gt_to_g(Workspace ws, int J, int B, int Mp) {

@@ -519,6 +519,8 @@ struct Tuning {
   int share_slots = 4096;  // SMPLFIT_BM_SLOTS: resident waves a batch-major vertex pass is dealt for (share-count choice)
   bool gen_mfma = true;    // SMPLFIT_GEN_MFMA=0: the general path's vertex block on the vector ALUs (k_gen_accum) instead of the matrix cores (A/B)
   bool rot_bm = true;      // SMPLFIT_ROT_BM=0: the part rotations as the wave-per-instance k_joint_stage behind a part-sum combine instead of k_rotations_bm (A/B)
+  bool rot_spread = true;  // SMPLFIT_ROT_SPREAD=0: the part rotations always as k_rotations_bm / k_rotations_bm_rounds (a workgroup per 64 instances, its waves fit several joints each), never as k_rotations_spread (a joint per wave, the joints over the grid's second dimension) (A/B, bit-identical)
+  int rot_spread_b = kRotSpreadMaxBatch;  // SMPLFIT_ROT_SPREAD_B: the most instances of a call (all its chunks together) that take k_rotations_spread
   bool refine_bm = true;   // SMPLFIT_REFINE_BM=0: the refinement + epilogue as the wave-per-instance k_refine_epilogue behind a part-sum combine instead of k_refine_bm (A/B)
   bool prologue_bm = true; // SMPLFIT_PROLOGUE_BM=0: the shape prologue inside k_joint_stage + the joint-row transpose instead of k_prologue_bm (A/B)
   bool solve_bm = true;    // SMPLFIT_SOLVE_BM=0: normal-equation combine + wave-per-instance solve as two launches instead of k_solve_bm (A/B)
@@ -550,6 +552,8 @@ Tuning read_tuning() {
   if (const char* e = env("SMPLFIT_PROLOGUE_BM")) t.prologue_bm = e[0] != '0';
   if (const char* e = env("SMPLFIT_REFINE_BM")) t.refine_bm = e[0] != '0';
   if (const char* e = env("SMPLFIT_ROT_BM")) t.rot_bm = e[0] != '0';
+  if (const char* e = env("SMPLFIT_ROT_SPREAD")) t.rot_spread = e[0] != '0';
+  if (const char* e = env("SMPLFIT_ROT_SPREAD_B")) t.rot_spread_b = std::max(atoi(e), 0);
   return t;
 }
 void load_tuning() {
@@ -1272,11 +1276,23 @@ void launch_prologue_bm(const smplfit_handle* h, const JointStageArgs& ja, const
 // K1r (k_rotations_bm): the part rotations with lane = instance, adding the part-sum rows of the pass in front of it
 // itself.  rot_kind: the cell table of that pass (its rows), or -1: k_joint_stage fits the rotations.  gprev_mode: where
 // the previous rotations come from (0 none, 1 ws.GT, 2 the instance-major ja.Gprev).
+// spread: Route::rot_spread, the form with a joint per wave (k_rotations_spread; it has no use for RotArgs::slot); it
+// counts under the stage id of the kernel it replaces, and in g_rot_spread_launches.
+std::atomic<uint64_t> g_rot_spread_launches{0};
 void launch_rotations_bm(const smplfit_handle* h, const JointStageArgs& ja, int rot_kind, int gprev_mode, const Workspace& ws, int B,
-                         hipStream_t st) {
+                         hipStream_t st, bool spread) {
   const DevModel& d = h->d;
   const int Mp = (int)align_up((size_t)B, 128);
   RotArgs ra{ja.tj, ja.rj, ja.jw, ja.Gprev, ja.rj_shared, gprev_mode, B, {}};
+  if (spread) {
+    const size_t lds = (size_t)rot_spread_lds_floats(d.J) * 4;
+    count_stage(d.J <= kRotJoints * kRefWaves ? SMPLFIT_STAGE_ROTATIONS_BM : SMPLFIT_STAGE_ROTATIONS_BM_ROUNDS);
+    g_rot_spread_launches.fetch_add(1, std::memory_order_relaxed);
+    if (lds > 64 * 1024) ensure_max_lds(reinterpret_cast<const void*>(&k_rotations_spread));
+    hipLaunchKernelGGL(k_rotations_spread, dim3((B + 63) / 64, (d.J + kRefWaves - 1) / kRefWaves), dim3(64 * kRefWaves), lds, st, d, ra,
+                       share_view(h, rot_kind, B), ws, Mp);
+    return;
+  }
   static_assert(sizeof(ra.slot) == sizeof(h->t.rot_slots), "RotArgs::slot holds HostTables::rot_slots");
   std::memcpy(ra.slot, h->t.rot_slots, sizeof(ra.slot));
   const size_t lds = (size_t)rot_bm_lds_floats(d.J) * 4;
@@ -1291,10 +1307,10 @@ void launch_rotations_bm(const smplfit_handle* h, const JointStageArgs& ja, int 
 }
 // planes: Route::gemm_planes (with pro)
 void launch_joint_stage_fit(const smplfit_handle* h, JointStageArgs ja, const Workspace& ws, int B, hipStream_t st, bool pro,
-                            int rot_kind = -1, int gprev_mode = 0, bool planes = false) {
+                            int rot_kind = -1, int gprev_mode = 0, bool planes = false, bool rot_spread = false) {
   if (pro && ja.do_prologue) {
     if (rot_kind >= 0) {
-      launch_rotations_bm(h, ja, rot_kind, gprev_mode, ws, B, st);
+      launch_rotations_bm(h, ja, rot_kind, gprev_mode, ws, B, st, rot_spread);
     } else {
       ja.do_prologue = 0;
       ja.gt_pitch = (int)align_up((size_t)B, 128);
@@ -1331,9 +1347,11 @@ void launch_refine_bm(const smplfit_handle* h, RefineArgs ra, const ShareView& s
 
 // ------------------------------------------------------------------------------------------------
 // Kernel route of one call: which kernel family serves its vertex passes and which stage kernels run inside the
-// batch-major one, decided once per call by route_of() from the handle, the batch and the call's shape.  Nothing else
-// reads the routing switches (SMPLFIT_BM, SMPLFIT_BM_*, _ROT_BM, _REFINE_BM, _PROLOGUE_BM, _SOLVE_BM, _GEMM_PLANES,
-// _SHAPE_FORM).
+// batch-major one, decided once per call by route_of() from the handle, the batch and the call's shape (a fit call cut
+// into concurrent chunks: once per chunk, from the chunk's batch; the one rule about what runs side by side on the
+// chip, the batch limit of k_rotations_spread, counts the instances of the whole call, CallShape::call_batch).  Nothing
+// else reads the routing switches (SMPLFIT_BM, SMPLFIT_BM_*, _ROT_BM, _ROT_SPREAD, _ROT_SPREAD_B, _REFINE_BM, _PROLOGUE_BM,
+// _SOLVE_BM, _GEMM_PLANES, _SHAPE_FORM).
 //
 //   condition                                                      -> kernels
 //   <= 8 skinning weights summing to one, 10 / 16 betas +- kid,      -> bm: the batch-major vertex passes; otherwise
@@ -1346,8 +1364,11 @@ void launch_refine_bm(const smplfit_handle* h, RefineArgs ra, const ShareView& s
 //   k_prologue_bm, Kp == 208, split-bf16 GEMM on an exclusive CU,     -> gemm_planes: k_prologue_bm writes the features as bf16
 //     three products; GEMM_PLANES                                      planes, not as fp32 rows; the GEMM of a shape solve
 //                                                                      reads those
-//   k_prologue_bm, <= 64 joints, toe sources fit; ROT_BM             -> k_rotations_bm: no k_psum_combine behind the passes
-//                                                                      in front of a rotation pass
+//   k_prologue_bm, <= 64 joints; ROT_BM                              -> calls of up to 4096 instances (ROT_SPREAD_B; not with
+//                                                                      ROT_SPREAD=0): k_rotations_spread, a joint per
+//                                                                      wave; else, where the toe sources fit,
+//                                                                      k_rotations_bm / _rounds: no k_psum_combine behind
+//                                                                      the passes in front of a rotation pass
 //   k_prologue_bm, <= 32 joints, <= 4 adjustable parts a wave; REFINE_BM -> k_refine_bm: no k_psum_combine behind the last
 //                                                                      pass; else k_refine_epilogue (+ k_gt_to_g first
 //                                                                      when k_rotations_bm ran)
@@ -1370,6 +1391,7 @@ struct CallShape {
   int scale_mode = 0;
   bool share_beta = false, rotations_only = false;
   bool warm = false;                 // warm start: the first rotation pass reads the rows of the warm start's LBS pass
+  int call_batch = 0;                // a chunk of a fit call: the instances of all its chunks, which run side by side (0: B)
 };
 struct Route {
   bool bm = false;                   // batch-major vertex kernels
@@ -1380,6 +1402,7 @@ struct Route {
                                      // and the GEMMs behind it (launch_normal_equations) read those
   bool jd_transpose = false;         // k_jd_transpose in front of a fit iteration's vertex passes
   bool rot_bm = false;               // k_rotations_bm, on the rows of the tables rot_kind_first / _next (else -1)
+  bool rot_spread = false;           // ... as k_rotations_spread (a joint per wave) instead of k_rotations_bm / _rounds
   int rot_kind_first = -1, rot_kind_next = -1;
   bool refine_bm = false;            // k_refine_bm on the rows of the table refine_kind (else -1); else k_refine_epilogue
   int refine_kind = -1;
@@ -1413,8 +1436,20 @@ Route route_of(const smplfit_handle* h, int B, const CallShape& c) {
   r.jd_transpose = r.bm && !r.prologue_bm;
   // (once k_rotations_bm runs nothing writes the instance-major ws.G any more: a model whose refinement stays on
   // k_refine_epilogue — more than 32 joints — gets it from k_gt_to_g in front of that kernel)
-  r.rot_bm = r.prologue_bm && tn.rot_bm && d.J <= kRotMaxJ && h->t.rot_nslots <= kRotSlots && h->t.rot_toes_per_wave <= 2 &&
-             (size_t)rot_bm_lds_floats(d.J) * 4 <= 160 * 1024;
+  // (k_rotations_spread needs the joints of 64 instances in LDS and nothing of the toes; the two kernels it replaces
+  // also the toe sources in their LDS slots and at most two toes a wave)
+  // The spread form for calls of up to kRotSpreadMaxBatch = 4096 instances, all chunks of the call counted since they
+  // run side by side (64 blocks of 64: the block form's grid leaves three quarters of the 256 CUs idle).  Its workgroups
+  // hold one per CU by their registers; with more blocks they queue behind each other while the block form's grid
+  // fills the chip by itself.  Measured (profiles/rot_spread_mi355x.json): a gain at 4096 on both models, none at 8192
+  // (the ranges overlap), none at 16384 (0.3 - 0.4 % below the parent, which is also what c4 moves between runs of one
+  // build): where no gain was seen the parent's kernels stay.
+  const bool spread = tn.rot_spread && std::max(B, c.call_batch) <= tn.rot_spread_b;
+  const bool rot_fits = spread ? (size_t)rot_spread_lds_floats(d.J) * 4 <= 160 * 1024
+                               : h->t.rot_nslots <= kRotSlots && h->t.rot_toes_per_wave <= 2 &&
+                                     (size_t)rot_bm_lds_floats(d.J) * 4 <= 160 * 1024;
+  r.rot_bm = r.prologue_bm && tn.rot_bm && d.J <= kRotMaxJ && rot_fits;
+  r.rot_spread = r.rot_bm && spread;
   r.refine_bm = r.prologue_bm && tn.refine_bm && d.J <= 32 && h->t.refine_group_max <= kRefParts &&
                 (size_t)refine_bm_lds_floats(d.J) * 4 <= 160 * 1024;
   r.gt_to_g = r.rot_bm && !r.refine_bm;
@@ -1806,7 +1841,7 @@ int enqueue_solve(const smplfit_handle* h, const Route& r, const Workspace& ws, 
 // of being read from target_vertices).
 int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_only, const ConvertSource* source,
             const Workspace& ws, hipStream_t st, int ph_lo = 0, int ph_hi = 1 << 30, bool vw_shared = false,
-            const smplfit_share_segments* segments = nullptr) {
+            const smplfit_share_segments* segments = nullptr, int call_batch = 0) {  // call_batch: CallShape::call_batch
   // PHASES.  The launches of a fit are numbered in phases — 0: the prologue up to the first rotation pass; 1 + 2 it:
   // the vertex block of iteration `it` up to the normal equations; 2 + 2 it: solve, vertices at the solution, next
   // rotation pass; 1 + 2 num_iter: refinement and epilogue — and a call enqueues the phases [ph_lo, ph_hi) only (the
@@ -1830,7 +1865,7 @@ int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_o
   // shape solve — the weighted accumulate.  scale_target / scale_fit: the LAST iteration's solve has one more unknown
   // and needs extra vertex sums — that iteration runs the accumulate kernel (with or without weights) in its EXTRAS form
   const Route r = route_of(h, B, {source ? Entry::kConvert : Entry::kFit, joints, vweighted, w.v, o.scale_mode,
-                                  o.share_beta != 0, o.rotations_only != 0, warm});
+                                  o.share_beta != 0, o.rotations_only != 0, warm, call_batch});
   if (source && !r.bm) return fail(SMPLFIT_ERR_UNSUPPORTED, "fused conversion: the batch-major path does not apply");
   if (on(0)) {
     TargetsIn t{a.target_vertices, tj, vw, vw, source, !warm, true, vw_shared};
@@ -1873,7 +1908,7 @@ int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_o
   // (first rotations: the rows of the template pass — or of the warm start's LBS pass —; previous rotations: the
   // instance-major ws.G of the warm start's forward stage, if any)
   if (on(0))
-    launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_first, ja.Gprev ? 2 : 0, r.gemm_planes);
+    launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_first, ja.Gprev ? 2 : 0, r.gemm_planes, r.rot_spread);
   if (o.rotations_only) {
     if (on(0)) hipLaunchKernelGGL(k_copy, dim3(256), dim3(256), 0, st, ws.G, a.orientations, (size_t)B * d.J * 9);
     return post_launch_check();
@@ -1894,7 +1929,7 @@ int run_fit(const smplfit_handle* h, const smplfit_fit_args& a, bool rotations_o
     ja.rj = joints ? ws.rjoints : ws.rjreg;
     ja.rj_shared = 0;
     ja.Gprev = ws.G;
-    if (pb) launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_next, 1, r.gemm_planes);
+    if (pb) launch_joint_stage_fit(h, ja, ws, B, st, r.prologue_bm, r.rot_kind_next, 1, r.gemm_planes, r.rot_spread);
   }
   if (!on(1 + 2 * o.num_iter)) return post_launch_check();
   RefineArgs ra = refine_args(tj_rot, joints, jw, o.final_adjust, ws, a.pose_rotvecs, a.shape_betas, a.trans, a.kid_factor,
@@ -2175,7 +2210,7 @@ int fit_impl(const smplfit_handle* h, const smplfit_fit_args* args, const Conver
     if (vw_shared) v.vertex_weights = a.vertex_weights;  // (every chunk reads the one row)
     // (a plan of segments: share_beta, so the one chunk)
     const Workspace ws = segments ? point_segments(lay[c].ws, h, *segments, a.workspace) : lay[c].ws;
-    return run_fit(h, v, false, job ? &src : nullptr, ws, cs, ph_lo, ph_hi, vw_shared, segments);
+    return run_fit(h, v, false, job ? &src : nullptr, ws, cs, ph_lo, ph_hi, vw_shared, segments, batch);
   };
   if (nchunk <= 1) return run_chunk(0, st, 0, 1 << 30);
   // fork: every chunk is an independent fit with its own workspace slice; chunk 0 stays on the
@@ -3911,6 +3946,7 @@ int smplfit_reload_options(void) {
 }
 
 uint64_t smplfit_gemm_plane_launches(void) { return g_gemm_plane_launches.load(std::memory_order_relaxed); }
+uint64_t smplfit_rotation_spread_launches(void) { return g_rot_spread_launches.load(std::memory_order_relaxed); }
 uint64_t smplfit_stage_launches(int stage_id) {
   if (stage_id < 0 || stage_id >= SMPLFIT_STAGE_COUNT) return 0;
   return g_stage_launches[stage_id].load(std::memory_order_relaxed);
@@ -3989,7 +4025,7 @@ int smplfit_time_kernel_f32(const smplfit_handle* h, int kernel_id, int batch, i
         ja.joint_block_weighted = 0;
         ja.vertex_sa_closed_form = d.general ? 0 : 1;
         // (what a default fit runs: the rotations + k_prologue_bm where that applies)
-        launch_joint_stage_fit(h, ja, ws, batch, st, r.prologue_bm, r.rot_kind_next, 1, r.gemm_planes);
+        launch_joint_stage_fit(h, ja, ws, batch, st, r.prologue_bm, r.rot_kind_next, 1, r.gemm_planes, r.rot_spread);
         return 0;
       }
       case SMPLFIT_KERNEL_REFINE: {  // (outputs into the workspace: ws.tvs is unused between fits)
