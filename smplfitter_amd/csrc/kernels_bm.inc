@@ -1361,6 +1361,68 @@ __global__ __launch_bounds__(64 * kProWaves) void k_prologue_bm(DevModel m, Prol
 constexpr int kRefPitch = 65;  // LDS pitch of the transposed joint arrays (the fill walks k at a fixed instance)
 constexpr int kRefParts = 4;   // adjustable parts of one group at most (a wave keeps their part sums in registers)
 __host__ __device__ inline int refine_bm_lds_floats(int J) { return 2 * 3 * J * kRefPitch + 2 * 3 * J * 64 + 9 * J * kRefPitch; }
+// The two pieces of data movement that k_refine_bm and the K1r kernels below share (lane = instance, column bcol).
+// The part sums of one part, added onto ps (the caller zeroes it): its rows of the last LBS pass (psumP,
+// instance-innermost) in table order — k_psum_combine's order —, AHEAD rows requested together, then added in turn.  The
+// adds, and so the bits, do not depend on AHEAD or CLAMP.  Requests behind the part's last row are skipped (k_rotations_spread,
+// AHEAD 8: a part has two to seven rows) or, CLAMP, repeat the last row (the three callers with AHEAD 4: one straight run
+// of requests; skipping them costs k_refine_bm<10> two registers, 169 against 167, which is an occupancy step).
+template <int AHEAD, bool CLAMP = false>
+__device__ __forceinline__ void gather_part_sums(const ShareView& sv, const float* __restrict__ psumP, int part, size_t pitch,
+                                                 int bcol, float (&ps)[sf::kPsum]) {
+  const int q0 = sv.aux_start[part], q1 = sv.aux_start[part + 1];
+  for (int q = q0; q < q1; q += AHEAD) {
+    float v[AHEAD][sf::kPsum];
+#pragma unroll
+    for (int r = 0; r < AHEAD; ++r)
+      if (CLAMP || q + r < q1) {
+        const float* src = psumP + (size_t)sv.aux_rows[q + r < q1 ? q + r : q1 - 1] * sf::kPsum * pitch + bcol;
+#pragma unroll
+        for (int k = 0; k < sf::kPsum; ++k) v[r][k] = src[(size_t)k * pitch];
+      }
+#pragma unroll
+    for (int r = 0; r < AHEAD; ++r)
+      if (q + r < q1) {
+#pragma unroll
+        for (int k = 0; k < sf::kPsum; ++k) ps[k] += v[r][k];
+      }
+  }
+}
+// The target / reference joints of the block's ni instances from i0 on (rows of J3 consecutive floats; rj_stride 0: one
+// reference row for all), transposed into LDS with pitch kRefPitch: wave w takes the instances w, w + kRefWaves, ...,
+// NH requests of 64 lanes cover a row (J3 <= 64 NH), every request before the first LDS store; with NH = 3 a request that
+// lies wholly behind the row is skipped (wave-uniform), with two both are made (a model of 22 .. 32 joints needs both, and
+// the straight run of requests is what k_refine_bm and k_rotations_bm were measured with).  No barrier in here.
+template <int NH>
+__device__ __forceinline__ void stage_block_joints(const float* __restrict__ tj, const float* __restrict__ rj, size_t rj_stride,
+                                                   int i0, int ni, int J3, int wave, int lane, float* tjs, float* rjs) {
+  float tv[64 / kRefWaves][NH], rv[64 / kRefWaves][NH];
+#pragma unroll
+  for (int u = 0; u < 64 / kRefWaves; ++u) {
+    const int inst = wave + u * kRefWaves, ii = inst < ni ? inst : ni - 1;
+    const float* tg = tj + (size_t)(i0 + ii) * J3;
+    const float* rg = rj + (size_t)(i0 + ii) * rj_stride;
+#pragma unroll
+    for (int h = 0; h < NH; ++h)
+      if (NH <= 2 || 64 * h < J3) {
+        const int k = lane + 64 * h, kk = k < J3 ? k : J3 - 1;
+        tv[u][h] = tg[kk];
+        rv[u][h] = rg[kk];
+      }
+  }
+#pragma unroll
+  for (int u = 0; u < 64 / kRefWaves; ++u) {
+    const int inst = wave + u * kRefWaves;
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int k = lane + 64 * h;
+      if (k < J3) {
+        tjs[k * kRefPitch + inst] = tv[u][h];
+        rjs[k * kRefPitch + inst] = rv[u][h];
+      }
+    }
+  }
+}
 template <int S>
 __global__ __launch_bounds__(64 * kRefWaves) void k_refine_bm(DevModel m, RefineArgs a, ShareView sv, Workspace ws, const float* rj_true,
                                                                 int Mp, RefGroups rg) {
@@ -1407,55 +1469,13 @@ __global__ __launch_bounds__(64 * kRefWaves) void k_refine_bm(DevModel m, Refine
       for (int k = 0; k < sf::kPsum; ++k) ps[u][k] = 0.f;
       if (ai >= 0) {
         const int prt = tb.adj_parts[ai];
-        const int q0 = sv.aux_start[prt], q1 = sv.aux_start[prt + 1];
-        for (int q = q0; q < q1; q += 4) {
-          float v[4][sf::kPsum];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float* src = ws.psumP + (size_t)sv.aux_rows[q + r < q1 ? q + r : q1 - 1] * sf::kPsum * pitch + bcol;
-#pragma unroll
-            for (int k = 0; k < sf::kPsum; ++k) v[r][k] = src[(size_t)k * pitch];
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (q + r < q1) {
-#pragma unroll
-              for (int k = 0; k < sf::kPsum; ++k) ps[u][k] += v[r][k];
-            }
-        }
+        gather_part_sums<4, true>(sv, ws.psumP, prt, pitch, bcol, ps[u]);
 #pragma unroll
         for (int c = 0; c < 3; ++c) ca[u][c] = rj_true[((size_t)b * J + prt) * 3 + c];
       }
     }
-    // target / reference joints of the block, transposed: wave w takes the instances w, w + 8, ... (a row of 3 J
-    // consecutive floats each; J <= 32: at most two requests of 64 lanes per row)
-    {
-      float tv[64 / kRefWaves][2], rv[64 / kRefWaves][2];
-#pragma unroll
-      for (int u = 0; u < 64 / kRefWaves; ++u) {
-        const int inst = wave + u * kRefWaves, ii = inst < ni ? inst : ni - 1;
-        const float* tg = a.tj + (size_t)(i0 + ii) * J3;
-        const float* rg = a.rj_term + (size_t)(i0 + ii) * J3;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int k = lane + 64 * h, kk = k < J3 ? k : J3 - 1;
-          tv[u][h] = tg[kk];
-          rv[u][h] = rg[kk];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 64 / kRefWaves; ++u) {
-        const int inst = wave + u * kRefWaves;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int k = lane + 64 * h;
-          if (k < J3) {
-            tjs[k * kRefPitch + inst] = tv[u][h];
-            rjs[k * kRefPitch + inst] = rv[u][h];
-          }
-        }
-      }
-    }
+    // target / reference joints of the block, transposed (J <= 32: at most two requests of 64 lanes per row)
+    stage_block_joints<2>(a.tj, a.rj_term, (size_t)J3, i0, ni, J3, wave, lane, tjs, rjs);
   }
   {  // the rotations as fitted: rows of 64 instances, nine requests in flight per step
     const float* GT = ws.GT + bcol;
@@ -1644,368 +1664,25 @@ struct RotArgs {
   int8_t slot[kRotMaxJ];  // the joint's slot among the joints a toe copies, or -1 (host: rot_bm_slots)
 };
 __host__ __device__ inline int rot_bm_lds_floats(int J) { return J <= kRotJoints * kRefWaves ? 2 * 3 * J * kRefPitch + 9 * J * 64 : 2 * 3 * J * kRefPitch + kRotSlots * 9 * 64; }
-// Models of at most kRotJoints * kRefWaves = 32 joints: ONE round — the wave's joints all at once, every rotation through
-// LDS ([J][9][64]), the toes composed with the others behind one barrier.  (The form with rounds below, which carries the
-// SMPL-X-shaped model, runs this case 6 us slower — 52 against 46 us with the prologue at 4096 instances —: kept apart.)
-__global__ __launch_bounds__(64 * kRefWaves) void k_rotations_bm(DevModel m, RotArgs a, ShareView sv, Workspace ws, int Mp) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const sf::JointTabs& tb = m.jt;
-  const int J = tb.J, J3 = 3 * J, B = a.B;
-  float* tjs = smem;                   // [3 J][65] centred target joints
-  float* rjs = tjs + J3 * kRefPitch;   // [3 J][65] reference joints
-  float* Rs = rjs + J3 * kRefPitch;    // [J][9][64] the parts' fitted rotations (a toe reads its foot's)
-  const int tid = threadIdx.x, lane = tid & 63, blk = blockIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int bcol = blk * 64 + lane, b = bcol < B ? bcol : B - 1;
-  const size_t pitch = (size_t)Mp;
-  const int i0 = blk * 64, ni = min(64, B - i0);
-  float* GT = ws.GT + bcol;
-  // ---- phase 0: every global read
-  float ps[kRotJoints][sf::kPsum], Gp[kRotJoints][9];
+// ---- The arithmetic of K1r, stated ONCE for the three kernels below: the fit of one part on one lane (part_rotation)
+// and the composition with the previous rotation (compose_prev).  The kernels must return the same bits (a call takes
+// one or another by its size; tests/test_gpu_rot_spread.py), and the compiler contracts a * b + c * d by how it happens
+// to pack the products of an inlined site in pairs, so the expressions on which that showed — each was a last bit of a
+// rotation — have every rounding spelled out here, and these are the only statements of them:
+//   the centred covariance (centered_cov_k1r: three fused steps per element, the product ct ca rounded first);
+//   the middle element of H = R_swing A^T inside the swing + twist (swing_twist_k1r: sf::swing_twist with that one
+//     statement added — (third product, rounded) + fma(second, (first product, rounded)));
+//   the weighted sums of the multi-joint Kabsch (part_rotation: every sum fused but sa[0]);
+//   the composition (compose_prev: fma(r2 g2, fma(r0 g0, r1 g1)), and its first element on models of up to 32 joints).
+// Everything else is sf:: code whose results did not depend on the site.
+__device__ __forceinline__ void centered_cov_k1r(const float* raw, const float* st, const float* sa, float sw, const float* ct,
+                                                 const float* ca, float* A) {  // sf::centered_cov
 #pragma unroll
-  for (int u = 0; u < kRotJoints; ++u) {
-    const int j = wave + u * kRefWaves;
+  for (int r = 0; r < 3; ++r)
 #pragma unroll
-    for (int k = 0; k < sf::kPsum; ++k) ps[u][k] = 0.f;
-    if (j >= J) continue;
-    if (tb.part_type[j] >= 2) {  // bone and leaf parts: the part sums of the vertices (k_psum_combine: rows in table order)
-      const int q0 = sv.aux_start[j], q1 = sv.aux_start[j + 1];
-      for (int q = q0; q < q1; q += 4) {
-        float v[4][sf::kPsum];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float* src = ws.psumP + (size_t)sv.aux_rows[q + r < q1 ? q + r : q1 - 1] * sf::kPsum * pitch + bcol;
-#pragma unroll
-          for (int k = 0; k < sf::kPsum; ++k) v[r][k] = src[(size_t)k * pitch];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (q + r < q1) {
-#pragma unroll
-            for (int k = 0; k < sf::kPsum; ++k) ps[u][k] += v[r][k];
-          }
-      }
-    }
-    if (a.gprev_mode == 1) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Gp[u][k] = GT[(size_t)(j * 9 + k) * pitch];
-    } else if (a.gprev_mode == 2) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Gp[u][k] = a.Gim[((size_t)b * J + j) * 9 + k];
-    }
-  }
-  {
-    float tv[64 / kRefWaves][2], rv[64 / kRefWaves][2];
-#pragma unroll
-    for (int u = 0; u < 64 / kRefWaves; ++u) {
-      const int inst = wave + u * kRefWaves, ii = inst < ni ? inst : ni - 1;
-      const float* tg = a.tj + (size_t)(i0 + ii) * J3;
-      const float* rg = a.rj_shared ? a.rj : a.rj + (size_t)(i0 + ii) * J3;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int k = lane + 64 * h, kk = k < J3 ? k : J3 - 1;
-        tv[u][h] = tg[kk];
-        rv[u][h] = rg[kk];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 64 / kRefWaves; ++u) {
-      const int inst = wave + u * kRefWaves;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int k = lane + 64 * h;
-        if (k < J3) {
-          tjs[k * kRefPitch + inst] = tv[u][h];
-          rjs[k * kRefPitch + inst] = rv[u][h];
-        }
-      }
-    }
-  }
-  __syncthreads();
-  auto TJ = [&](int mj, int c) { return tjs[(mj * 3 + c) * kRefPitch + lane]; };
-  auto RJ = [&](int mj, int c) { return rjs[(mj * 3 + c) * kRefPitch + lane]; };
-  // ---- phase 1: the parts' rotations (sf::joint_stage, per lane)
-#pragma unroll
-  for (int u = 0; u < kRotJoints; ++u) {
-    const int j = wave + u * kRefWaves;
-    if (j >= J) continue;
-    const int type = tb.part_type[j];
-    float R[9];
-    sf::m3_identity(R);
-    if (type != 0) {
-      const int c0 = tb.cas_start[j], n = tb.cas_start[j + 1] - c0;
-      const float inv = 1.0f / (float)n;
-      float ct[3] = {0, 0, 0}, ca[3] = {0, 0, 0};
-      for (int q = 0; q < n; ++q) {
-        const int mj = tb.cas_flat[c0 + q];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          ct[c] += inv * TJ(mj, c);
-          ca[c] += inv * RJ(mj, c);
-        }
-      }
-      float A[9];
-      if (type == 1) {  // multi-joint part: Kabsch on its joints only (:1361-1383)
-        float raw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, st[3] = {0, 0, 0}, sa[3] = {0, 0, 0}, sw = 0;
-        for (int q = 0; q < n; ++q) {
-          const int mj = tb.cas_flat[c0 + q];
-          const float w = a.jw ? a.jw[(size_t)b * J + mj] : 1.0f;
-          const float t[3] = {TJ(mj, 0), TJ(mj, 1), TJ(mj, 2)};
-          const float aa[3] = {RJ(mj, 0) * w, RJ(mj, 1) * w, RJ(mj, 2) * w};
-#pragma unroll
-          for (int r = 0; r < 3; ++r) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) raw[r * 3 + c] += t[r] * aa[c];
-            st[r] += t[r] * w;
-            sa[r] += aa[r];
-          }
-          sw += w;
-        }
-        sf::centered_cov(raw, st, sa, sw, ct, ca, A);
-      } else {
-        sf::centered_cov(ps[u], ps[u] + 9, ps[u] + 12, ps[u][15], ct, ca, A);
-      }
-      if (type == 2) {  // bone part: swing + twist (:1389-1412)
-        const int k0 = tb.cas_flat[c0], k1 = tb.cas_flat[c0 + 1];
-        float br[3], bt[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          br[c] = RJ(k1, c) - RJ(k0, c);
-          bt[c] = TJ(k1, c) - TJ(k0, c);
-        }
-        sf::swing_twist(br, bt, A, R);
-      } else {
-        sf::proj_so3(A, R);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Rs[(j * 9 + k) * 64 + lane] = R[k];
-  }
-  __syncthreads();
-  // ---- phase 2: toes take the feet; compose with the previous rotations (:422-433); rows of ws.GT
-#pragma unroll
-  for (int u = 0; u < kRotJoints; ++u) {
-    const int j = wave + u * kRefWaves;
-    if (j >= J) continue;
-    const int src = tb.toe_src[j] >= 0 ? tb.toe_src[j] : j;
-    float R[9], G[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = Rs[(src * 9 + k) * 64 + lane];
-    if (a.gprev_mode != 0) {
-      sf::m3_mul(R, Gp[u], G);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) G[k] = R[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) GT[(size_t)(j * 9 + k) * pitch] = G[k];
-  }
+    for (int c = 0; c < 3; ++c)
+      A[r * 3 + c] = __builtin_fmaf(sw, ct[r] * ca[c], __builtin_fmaf(-ct[r], sa[c], __builtin_fmaf(-st[r], ca[c], raw[r * 3 + c])));
 }
-
-// More joints (33 .. 64): rounds of kRotJoints joints per wave; only the rotations a toe copies go through LDS.
-__global__ __launch_bounds__(64 * kRefWaves) void k_rotations_bm_rounds(DevModel m, RotArgs a, ShareView sv, Workspace ws, int Mp) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const sf::JointTabs& tb = m.jt;
-  const int J = tb.J, J3 = 3 * J, B = a.B;
-  float* tjs = smem;                   // [3 J][65] centred target joints
-  float* rjs = tjs + J3 * kRefPitch;   // [3 J][65] reference joints
-  float* Rs = rjs + J3 * kRefPitch;    // [kRotSlots][9][64] fitted rotations of the joints a toe copies
-  const int tid = threadIdx.x, lane = tid & 63, blk = blockIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int bcol = blk * 64 + lane, b = bcol < B ? bcol : B - 1;
-  const size_t pitch = (size_t)Mp;
-  const int i0 = blk * 64, ni = min(64, B - i0);
-  float* GT = ws.GT + bcol;
-  // ---- the block's target / reference joints, transposed (wave w: the instances w, w + 8, ...)
-  {
-    float tv[64 / kRefWaves][3], rv[64 / kRefWaves][3];
-#pragma unroll
-    for (int u = 0; u < 64 / kRefWaves; ++u) {
-      const int inst = wave + u * kRefWaves, ii = inst < ni ? inst : ni - 1;
-      const float* tg = a.tj + (size_t)(i0 + ii) * J3;
-      const float* rg = a.rj_shared ? a.rj : a.rj + (size_t)(i0 + ii) * J3;
-#pragma unroll
-      for (int h = 0; h < 3; ++h) {
-        const int k = lane + 64 * h, kk = k < J3 ? k : J3 - 1;
-        tv[u][h] = tg[kk];
-        rv[u][h] = rg[kk];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 64 / kRefWaves; ++u) {
-      const int inst = wave + u * kRefWaves;
-#pragma unroll
-      for (int h = 0; h < 3; ++h) {
-        const int k = lane + 64 * h;
-        if (k < J3) {
-          tjs[k * kRefPitch + inst] = tv[u][h];
-          rjs[k * kRefPitch + inst] = rv[u][h];
-        }
-      }
-    }
-  }
-  auto TJ = [&](int mj, int c) { return tjs[(mj * 3 + c) * kRefPitch + lane]; };
-  auto RJ = [&](int mj, int c) { return rjs[(mj * 3 + c) * kRefPitch + lane]; };
-  auto load_prev = [&](int j, float (&G)[9]) {
-    if (a.gprev_mode == 1) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) G[k] = GT[(size_t)(j * 9 + k) * pitch];
-    } else if (a.gprev_mode == 2) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) G[k] = a.Gim[((size_t)b * J + j) * 9 + k];
-    }
-  };
-  // compose with the previous rotation (:422-433).  Two call sites (a round; the toes behind the last barrier): the
-  // product is written as explicit fused steps, so that the compiler cannot contract it one way here and another way
-  // there — a toe whose previous rotation has its foot's bits gets its foot's bits (as in k_rotations_bm, where both go
-  // through one site, and in k_joint_stage)
-  auto store_G = [&](int j, const float (&R)[9], const float (&Gp)[9]) {
-    float G[9];
-    if (a.gprev_mode != 0) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          G[r * 3 + c] = __builtin_fmaf(R[r * 3 + 2], Gp[6 + c], __builtin_fmaf(R[r * 3], Gp[c], R[r * 3 + 1] * Gp[3 + c]));
-    } else {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) G[k] = R[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) GT[(size_t)(j * 9 + k) * pitch] = G[k];
-  };
-  // the wave's toes (at most two: route_of): their previous rotations are requested now, used behind the last barrier
-  int toej[2] = {-1, -1};
-  float Gtoe[2][9];
-  for (int j = wave, n = 0; j < J; j += kRefWaves)
-    if (tb.toe_src[j] >= 0 && n < 2) toej[n++] = j;
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-    if (toej[u] >= 0) load_prev(toej[u], Gtoe[u]);
-  // ---- rounds of kRotJoints joints per wave: request (part sums from the rows of the pass in front — k_psum_combine's
-  // order —, previous rotations), fit (sf::joint_stage, per lane), compose and write; a toe waits for its foot
-  for (int r0 = 0; r0 < J; r0 += kRotJoints * kRefWaves) {
-    float ps[kRotJoints][sf::kPsum], Gp[kRotJoints][9];
-#pragma unroll
-    for (int u = 0; u < kRotJoints; ++u) {
-      const int j = r0 + wave + u * kRefWaves;
-#pragma unroll
-      for (int k = 0; k < sf::kPsum; ++k) ps[u][k] = 0.f;
-      if (j >= J) continue;
-      if (tb.part_type[j] >= 2) {  // bone and leaf parts: the part sums of the vertices
-        const int q0 = sv.aux_start[j], q1 = sv.aux_start[j + 1];
-        for (int q = q0; q < q1; q += 4) {
-          float v[4][sf::kPsum];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float* src = ws.psumP + (size_t)sv.aux_rows[q + r < q1 ? q + r : q1 - 1] * sf::kPsum * pitch + bcol;
-#pragma unroll
-            for (int k = 0; k < sf::kPsum; ++k) v[r][k] = src[(size_t)k * pitch];
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (q + r < q1) {
-#pragma unroll
-              for (int k = 0; k < sf::kPsum; ++k) ps[u][k] += v[r][k];
-            }
-        }
-      }
-      if (tb.toe_src[j] < 0) load_prev(j, Gp[u]);
-    }
-    if (r0 == 0) __syncthreads();  // (the joints in LDS)
-#pragma unroll
-    for (int u = 0; u < kRotJoints; ++u) {
-      const int j = r0 + wave + u * kRefWaves;
-      if (j >= J) continue;
-      const int type = tb.part_type[j];
-      float R[9];
-      sf::m3_identity(R);
-      if (type != 0) {
-        const int c0 = tb.cas_start[j], n = tb.cas_start[j + 1] - c0;
-        const float inv = 1.0f / (float)n;
-        float ct[3] = {0, 0, 0}, ca[3] = {0, 0, 0};
-        for (int q = 0; q < n; ++q) {
-          const int mj = tb.cas_flat[c0 + q];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            ct[c] += inv * TJ(mj, c);
-            ca[c] += inv * RJ(mj, c);
-          }
-        }
-        float A[9];
-        if (type == 1) {  // multi-joint part: Kabsch on its joints only (:1361-1383)
-          float raw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, st[3] = {0, 0, 0}, sa[3] = {0, 0, 0}, sw = 0;
-          for (int q = 0; q < n; ++q) {
-            const int mj = tb.cas_flat[c0 + q];
-            const float w = a.jw ? a.jw[(size_t)b * J + mj] : 1.0f;
-            const float t[3] = {TJ(mj, 0), TJ(mj, 1), TJ(mj, 2)};
-            const float aa[3] = {RJ(mj, 0) * w, RJ(mj, 1) * w, RJ(mj, 2) * w};
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-#pragma unroll
-              for (int c = 0; c < 3; ++c) raw[r * 3 + c] += t[r] * aa[c];
-              st[r] += t[r] * w;
-              sa[r] += aa[r];
-            }
-            sw += w;
-          }
-          sf::centered_cov(raw, st, sa, sw, ct, ca, A);
-        } else {
-          sf::centered_cov(ps[u], ps[u] + 9, ps[u] + 12, ps[u][15], ct, ca, A);
-        }
-        if (type == 2) {  // bone part: swing + twist (:1389-1412)
-          const int k0 = tb.cas_flat[c0], k1 = tb.cas_flat[c0 + 1];
-          float br[3], bt[3];
-#pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            br[c] = RJ(k1, c) - RJ(k0, c);
-            bt[c] = TJ(k1, c) - TJ(k0, c);
-          }
-          sf::swing_twist(br, bt, A, R);
-        } else {
-          sf::proj_so3(A, R);
-        }
-      }
-      const int sl = a.slot[j];
-      if (sl >= 0) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Rs[(sl * 9 + k) * 64 + lane] = R[k];
-      }
-      if (tb.toe_src[j] < 0) store_G(j, R, Gp[u]);
-    }
-  }
-  __syncthreads();
-  // ---- toes take the feet (:147-156)
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    if (toej[u] < 0) continue;
-    const int sl = a.slot[tb.toe_src[toej[u]]];
-    float R[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = Rs[(sl * 9 + k) * 64 + lane];
-    store_G(toej[u], R, Gtoe[u]);
-  }
-}
-
-// K1r spread over the chip (calls of up to kRotSpreadMaxBatch instances; the two kernels above serve larger ones and
-// SMPLFIT_ROT_SPREAD=0): ONE joint per wave.
-// Workgroup (blk, y) owns the 64 instances of block blk and the joints y * kRefWaves .. + kRefWaves - 1; wave w fits the
-// part of joint j = y * kRefWaves + w for its 64 lanes.  A toe (toe_src[j] >= 0) fits its FOOT's part itself — the same
-// inputs through the same code, so the foot's bits — and composes with its own previous rotation: no rotation crosses
-// waves, LDS holds only the block's transposed target / reference joints, and the one barrier is the one behind them.
-// Every row of the part's sums is requested before the first add (kRotAhead rows a batch: the coarse cell tables give a
-// part at most 7 rows, so one batch), added in table order: the sums, and with them every rotation, keep the bits of the
-// kernels above.  The chain of a wave is one memory round trip, one projection and one row store.
-// grid (Mp / 64, ceil(J / kRefWaves)), block 64 * kRefWaves.
-//
-// Same bits as the kernels above, for the same sf:: code, needs FOUR expressions stated as the fused steps the compiler
-// gives every site of those kernels (it contracts a * b + c * d by how it happens to pack the products of an inlined site
-// in pairs, and packs this kernel's single site differently; each was a last bit of a rotation): the centred covariance
-// (centered_cov below); inside the swing + twist the middle element of H = R_swing A^T, which those sites leave over
-// from four pairs and form as (third product, rounded) + fma(second, (first product, rounded)) — swing_twist_k1r is
-// sf::swing_twist with that one statement added —; the weighted sums of the multi-joint Kabsch; the first element of the
-// composition on models of up to 32 joints.  The kernels above still leave these to the compiler: a compiler that
-// packs them otherwise moves THEIR bits, and tests/test_gpu_rot_spread.py fails until the steps here follow.
 __device__ inline void swing_twist_k1r(const float* b_ref, const float* b_tgt, const float* A, float* R) {  // sf::swing_twist
   const float nr = sqrtf(b_ref[0] * b_ref[0] + b_ref[1] * b_ref[1] + b_ref[2] * b_ref[2]);
   const float nt = sqrtf(b_tgt[0] * b_tgt[0] + b_tgt[1] * b_tgt[1] + b_tgt[2] * b_tgt[2]);
@@ -2030,6 +1707,236 @@ __device__ inline void swing_twist_k1r(const float* b_ref, const float* b_tgt, c
   sf::rotvec2mat(rv, Rtw);
   sf::m3_mul(Rtw, Rsw, R);
 }
+// The rotation R of part f for the lane's instance b (sf::joint_stage up to its prologue, per lane): from the part's
+// sums ps (gather_part_sums; read for bone and leaf parts only) and the block's joints in LDS (stage_block_joints).
+__device__ __forceinline__ void part_rotation(const sf::JointTabs& tb, int f, const float (&ps)[sf::kPsum], const float* tjs,
+                                              const float* rjs, int lane, const float* __restrict__ jw, int b, float (&R)[9]) {
+  auto TJ = [&](int mj, int c) { return tjs[(mj * 3 + c) * kRefPitch + lane]; };
+  auto RJ = [&](int mj, int c) { return rjs[(mj * 3 + c) * kRefPitch + lane]; };
+  const int type = tb.part_type[f];
+  sf::m3_identity(R);
+  if (type == 0) return;
+  const int c0 = tb.cas_start[f], n = tb.cas_start[f + 1] - c0;
+  const float inv = 1.0f / (float)n;
+  float ct[3] = {0, 0, 0}, ca[3] = {0, 0, 0};
+  for (int q = 0; q < n; ++q) {
+    const int mj = tb.cas_flat[c0 + q];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      ct[c] += inv * TJ(mj, c);
+      ca[c] += inv * RJ(mj, c);
+    }
+  }
+  float A[9];
+  if (type == 1) {  // multi-joint part: Kabsch on its joints only (:1361-1383)
+    float raw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, st[3] = {0, 0, 0}, sa[3] = {0, 0, 0}, sw = 0;
+    for (int q = 0; q < n; ++q) {
+      const int mj = tb.cas_flat[c0 + q];
+      const float w = jw ? jw[(size_t)b * tb.J + mj] : 1.0f;
+      const float t[3] = {TJ(mj, 0), TJ(mj, 1), TJ(mj, 2)}, rj[3] = {RJ(mj, 0), RJ(mj, 1), RJ(mj, 2)};
+      // (the steps matter once w is not 1: every sum fused but sa[0], which adds the rounded product)
+      float aa[3];
+      {
+#pragma clang fp contract(off)
+        aa[0] = rj[0] * w, aa[1] = rj[1] * w, aa[2] = rj[2] * w;
+        sa[0] = sa[0] + aa[0];
+      }
+      sa[1] = __builtin_fmaf(rj[1], w, sa[1]);
+      sa[2] = __builtin_fmaf(rj[2], w, sa[2]);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) raw[r * 3 + c] = __builtin_fmaf(t[r], aa[c], raw[r * 3 + c]);
+        st[r] = __builtin_fmaf(t[r], w, st[r]);
+      }
+      sw += w;
+    }
+    centered_cov_k1r(raw, st, sa, sw, ct, ca, A);
+  } else {
+    centered_cov_k1r(ps, ps + 9, ps + 12, ps[15], ct, ca, A);
+  }
+  if (type == 2) {  // bone part: swing + twist (:1389-1412)
+    const int k0 = tb.cas_flat[c0], k1 = tb.cas_flat[c0 + 1];
+    float br[3], bt[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      br[c] = RJ(k1, c) - RJ(k0, c);
+      bt[c] = TJ(k1, c) - TJ(k0, c);
+    }
+    swing_twist_k1r(br, bt, A, R);
+  } else {
+    sf::proj_so3(A, R);
+  }
+}
+// The previous rotation of joint j (gprev_mode 1: its row of ws.GT, GT at the lane's column; 2: the instance-major Gim).
+__device__ __forceinline__ void load_prev(const RotArgs& a, const float* GT, size_t pitch, int J, int b, int j, float (&G)[9]) {
+  if (a.gprev_mode == 1) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) G[k] = GT[(size_t)(j * 9 + k) * pitch];
+  } else if (a.gprev_mode == 2) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) G[k] = a.Gim[((size_t)b * J + j) * 9 + k];
+  }
+}
+// G = R Gp, the composition with the previous rotation (:422-433; gprev_mode 0: G = R).  A toe whose previous rotation
+// has its foot's bits gets its foot's bits.
+// one_round: models of up to kRotJoints * kRefWaves = 32 joints round the FIRST element in another order, (r0 g0 rounded,
+// then fma(r1, g3, .)) + (r2 g6 rounded) — what the one-round kernel gave when it left the product to the compiler, and
+// what every fit of those models has returned since.  Kept as behaviour; the other eight elements do not differ.
+__device__ __forceinline__ void compose_prev(const float (&R)[9], const float (&Gp)[9], int gprev_mode, bool one_round, float (&G)[9]) {
+  if (gprev_mode != 0) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        G[r * 3 + c] = __builtin_fmaf(R[r * 3 + 2], Gp[6 + c], __builtin_fmaf(R[r * 3], Gp[c], R[r * 3 + 1] * Gp[3 + c]));
+    if (one_round) {
+#pragma clang fp contract(off)
+      const float p0 = R[0] * Gp[0], p2 = R[2] * Gp[6];
+      G[0] = __builtin_fmaf(R[1], Gp[3], p0) + p2;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) G[k] = R[k];
+  }
+}
+__device__ __forceinline__ void store_rotation_row(float* GT, size_t pitch, int j, const float (&G)[9]) {  // row j of ws.GT
+#pragma unroll
+  for (int k = 0; k < 9; ++k) GT[(size_t)(j * 9 + k) * pitch] = G[k];
+}
+
+// Models of at most kRotJoints * kRefWaves = 32 joints: ONE round — the wave's joints all at once, every rotation through
+// LDS ([J][9][64]), the toes composed with the others behind one barrier.  (The form with rounds below, which carries the
+// SMPL-X-shaped model, runs this case 6 us slower — 52 against 46 us with the prologue at 4096 instances —: kept apart.)
+__global__ __launch_bounds__(64 * kRefWaves) void k_rotations_bm(DevModel m, RotArgs a, ShareView sv, Workspace ws, int Mp) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const sf::JointTabs& tb = m.jt;
+  const int J = tb.J, J3 = 3 * J, B = a.B;
+  float* tjs = smem;                   // [3 J][65] centred target joints
+  float* rjs = tjs + J3 * kRefPitch;   // [3 J][65] reference joints
+  float* Rs = rjs + J3 * kRefPitch;    // [J][9][64] the parts' fitted rotations (a toe reads its foot's)
+  const int tid = threadIdx.x, lane = tid & 63, blk = blockIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int bcol = blk * 64 + lane, b = bcol < B ? bcol : B - 1;
+  const size_t pitch = (size_t)Mp;
+  const int i0 = blk * 64, ni = min(64, B - i0);
+  float* GT = ws.GT + bcol;
+  // ---- phase 0: every global read
+  float ps[kRotJoints][sf::kPsum], Gp[kRotJoints][9];
+#pragma unroll
+  for (int u = 0; u < kRotJoints; ++u) {
+    const int j = wave + u * kRefWaves;
+#pragma unroll
+    for (int k = 0; k < sf::kPsum; ++k) ps[u][k] = 0.f;
+    if (j >= J) continue;
+    if (tb.part_type[j] >= 2) gather_part_sums<4, true>(sv, ws.psumP, j, pitch, bcol, ps[u]);  // bone and leaf parts
+    load_prev(a, GT, pitch, J, b, j, Gp[u]);
+  }
+  stage_block_joints<2>(a.tj, a.rj, a.rj_shared ? (size_t)0 : (size_t)J3, i0, ni, J3, wave, lane, tjs, rjs);
+  __syncthreads();
+  // ---- phase 1: the parts' rotations
+#pragma unroll
+  for (int u = 0; u < kRotJoints; ++u) {
+    const int j = wave + u * kRefWaves;
+    if (j >= J) continue;
+    float R[9];
+    part_rotation(tb, j, ps[u], tjs, rjs, lane, a.jw, b, R);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rs[(j * 9 + k) * 64 + lane] = R[k];
+  }
+  __syncthreads();
+  // ---- phase 2: toes take the feet (:147-156); compose with the previous rotations; rows of ws.GT
+#pragma unroll
+  for (int u = 0; u < kRotJoints; ++u) {
+    const int j = wave + u * kRefWaves;
+    if (j >= J) continue;
+    const int src = tb.toe_src[j] >= 0 ? tb.toe_src[j] : j;
+    float R[9], G[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = Rs[(src * 9 + k) * 64 + lane];
+    compose_prev(R, Gp[u], a.gprev_mode, true, G);
+    store_rotation_row(GT, pitch, j, G);
+  }
+}
+
+// More joints (33 .. 64): rounds of kRotJoints joints per wave; only the rotations a toe copies go through LDS.
+__global__ __launch_bounds__(64 * kRefWaves) void k_rotations_bm_rounds(DevModel m, RotArgs a, ShareView sv, Workspace ws, int Mp) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const sf::JointTabs& tb = m.jt;
+  const int J = tb.J, J3 = 3 * J, B = a.B;
+  float* tjs = smem;                   // [3 J][65] centred target joints
+  float* rjs = tjs + J3 * kRefPitch;   // [3 J][65] reference joints
+  float* Rs = rjs + J3 * kRefPitch;    // [kRotSlots][9][64] fitted rotations of the joints a toe copies
+  const int tid = threadIdx.x, lane = tid & 63, blk = blockIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int bcol = blk * 64 + lane, b = bcol < B ? bcol : B - 1;
+  const size_t pitch = (size_t)Mp;
+  const int i0 = blk * 64, ni = min(64, B - i0);
+  float* GT = ws.GT + bcol;
+  stage_block_joints<(3 * kRotMaxJ + 63) / 64>(a.tj, a.rj, a.rj_shared ? (size_t)0 : (size_t)J3, i0, ni, J3, wave, lane, tjs, rjs);
+  // the wave's toes (at most two: route_of): their previous rotations are requested now, used behind the last barrier
+  int toej[2] = {-1, -1};
+  float Gtoe[2][9];
+  for (int j = wave, n = 0; j < J; j += kRefWaves)
+    if (tb.toe_src[j] >= 0 && n < 2) toej[n++] = j;
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    if (toej[u] >= 0) load_prev(a, GT, pitch, J, b, toej[u], Gtoe[u]);
+  // ---- rounds of kRotJoints joints per wave: request (part sums, previous rotations), fit, compose and write; a toe
+  // waits for its foot
+  for (int r0 = 0; r0 < J; r0 += kRotJoints * kRefWaves) {
+    float ps[kRotJoints][sf::kPsum], Gp[kRotJoints][9];
+#pragma unroll
+    for (int u = 0; u < kRotJoints; ++u) {
+      const int j = r0 + wave + u * kRefWaves;
+#pragma unroll
+      for (int k = 0; k < sf::kPsum; ++k) ps[u][k] = 0.f;
+      if (j >= J) continue;
+      if (tb.part_type[j] >= 2) gather_part_sums<4, true>(sv, ws.psumP, j, pitch, bcol, ps[u]);  // bone and leaf parts
+      if (tb.toe_src[j] < 0) load_prev(a, GT, pitch, J, b, j, Gp[u]);
+    }
+    if (r0 == 0) __syncthreads();  // (the joints in LDS)
+#pragma unroll
+    for (int u = 0; u < kRotJoints; ++u) {
+      const int j = r0 + wave + u * kRefWaves;
+      if (j >= J) continue;
+      float R[9], G[9];
+      part_rotation(tb, j, ps[u], tjs, rjs, lane, a.jw, b, R);
+      const int sl = a.slot[j];
+      if (sl >= 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rs[(sl * 9 + k) * 64 + lane] = R[k];
+      }
+      if (tb.toe_src[j] < 0) {
+        compose_prev(R, Gp[u], a.gprev_mode, false, G);
+        store_rotation_row(GT, pitch, j, G);
+      }
+    }
+  }
+  __syncthreads();
+  // ---- toes take the feet (:147-156)
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    if (toej[u] < 0) continue;
+    const int sl = a.slot[tb.toe_src[toej[u]]];
+    float R[9], G[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = Rs[(sl * 9 + k) * 64 + lane];
+    compose_prev(R, Gtoe[u], a.gprev_mode, false, G);
+    store_rotation_row(GT, pitch, toej[u], G);
+  }
+}
+
+// K1r spread over the chip (calls of up to kRotSpreadMaxBatch instances; the two kernels above serve larger ones and
+// SMPLFIT_ROT_SPREAD=0): ONE joint per wave.
+// Workgroup (blk, y) owns the 64 instances of block blk and the joints y * kRefWaves .. + kRefWaves - 1; wave w fits the
+// part of joint j = y * kRefWaves + w for its 64 lanes.  A toe (toe_src[j] >= 0) fits its FOOT's part itself — the same
+// inputs through the same code, so the foot's bits — and composes with its own previous rotation: no rotation crosses
+// waves, LDS holds only the block's transposed target / reference joints, and the one barrier is the one behind them.
+// Every row of the part's sums is requested before the first add (kRotAhead rows a batch: the coarse cell tables give a
+// part at most 7 rows, so one batch), added in table order: the sums, and with them every rotation, keep the bits of the
+// kernels above.  The chain of a wave is one memory round trip, one projection and one row store.
+// grid (Mp / 64, ceil(J / kRefWaves)), block 64 * kRefWaves.
 constexpr int kRotAhead = 8;  // part-sum rows in flight per wave (16 registers each)
 constexpr int kRotSpreadMaxBatch = 4096;  // most instances of a call that take this form (route_of; SMPLFIT_ROT_SPREAD_B)
 __host__ __device__ inline int rot_spread_lds_floats(int J) { return 2 * 3 * J * kRefPitch; }
@@ -2048,159 +1955,22 @@ __global__ __launch_bounds__(64 * kRefWaves) void k_rotations_spread(DevModel m,
   const size_t pitch = (size_t)Mp;
   const int i0 = blk * 64, ni = min(64, B - i0);
   float* GT = ws.GT + bcol;
-  // ---- every global read: the part sums (rows in table order), the previous rotation, the block's joints
+  // ---- every global read: the part sums, the previous rotation, the block's joints
   float ps[sf::kPsum], Gp[9];
 #pragma unroll
   for (int k = 0; k < sf::kPsum; ++k) ps[k] = 0.f;
   if (live) {
-    if (tb.part_type[f] >= 2) {  // bone and leaf parts: the part sums of the vertices (k_psum_combine: rows in table order)
-      const int q0 = sv.aux_start[f], q1 = sv.aux_start[f + 1];
-      for (int q = q0; q < q1; q += kRotAhead) {
-        float v[kRotAhead][sf::kPsum];
-#pragma unroll
-        for (int r = 0; r < kRotAhead; ++r)
-          if (q + r < q1) {
-            const float* src = ws.psumP + (size_t)sv.aux_rows[q + r] * sf::kPsum * pitch + bcol;
-#pragma unroll
-            for (int k = 0; k < sf::kPsum; ++k) v[r][k] = src[(size_t)k * pitch];
-          }
-#pragma unroll
-        for (int r = 0; r < kRotAhead; ++r)
-          if (q + r < q1) {
-#pragma unroll
-            for (int k = 0; k < sf::kPsum; ++k) ps[k] += v[r][k];
-          }
-      }
-    }
-    if (a.gprev_mode == 1) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Gp[k] = GT[(size_t)(j * 9 + k) * pitch];
-    } else if (a.gprev_mode == 2) {
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Gp[k] = a.Gim[((size_t)b * J + j) * 9 + k];
-    }
+    if (tb.part_type[f] >= 2) gather_part_sums<kRotAhead>(sv, ws.psumP, f, pitch, bcol, ps);  // bone and leaf parts
+    load_prev(a, GT, pitch, J, b, j, Gp);
   }
-  {
-    constexpr int NH = (3 * kRotMaxJ + 63) / 64;
-    float tv[64 / kRefWaves][NH], rv[64 / kRefWaves][NH];
-#pragma unroll
-    for (int u = 0; u < 64 / kRefWaves; ++u) {
-      const int inst = wave + u * kRefWaves, ii = inst < ni ? inst : ni - 1;
-      const float* tg = a.tj + (size_t)(i0 + ii) * J3;
-      const float* rg = a.rj_shared ? a.rj : a.rj + (size_t)(i0 + ii) * J3;
-#pragma unroll
-      for (int h = 0; h < NH; ++h)
-        if (64 * h < J3) {
-          const int k = lane + 64 * h, kk = k < J3 ? k : J3 - 1;
-          tv[u][h] = tg[kk];
-          rv[u][h] = rg[kk];
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < 64 / kRefWaves; ++u) {
-      const int inst = wave + u * kRefWaves;
-#pragma unroll
-      for (int h = 0; h < NH; ++h) {
-        const int k = lane + 64 * h;
-        if (k < J3) {
-          tjs[k * kRefPitch + inst] = tv[u][h];
-          rjs[k * kRefPitch + inst] = rv[u][h];
-        }
-      }
-    }
-  }
+  stage_block_joints<(3 * kRotMaxJ + 63) / 64>(a.tj, a.rj, a.rj_shared ? (size_t)0 : (size_t)J3, i0, ni, J3, wave, lane, tjs, rjs);
   __syncthreads();
   if (!live) return;  // (a wave behind the last joint only took part in the transpose)
-  auto TJ = [&](int mj, int c) { return tjs[(mj * 3 + c) * kRefPitch + lane]; };
-  auto RJ = [&](int mj, int c) { return rjs[(mj * 3 + c) * kRefPitch + lane]; };
-  // sf::centered_cov as the fused steps of the kernels above (left to the compiler, one element stays unfused here: a
-  // last bit that the hard targets of tests/test_gpu_stage_chain.py turn into 6e-4 of a rotation)
-  auto centered_cov = [](const float* raw, const float* st, const float* sa, float sw, const float* ct, const float* ca, float* A) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        A[r * 3 + c] = __builtin_fmaf(sw, ct[r] * ca[c], __builtin_fmaf(-ct[r], sa[c], __builtin_fmaf(-st[r], ca[c], raw[r * 3 + c])));
-  };
-  // ---- the part's rotation (sf::joint_stage, per lane)
-  const int type = tb.part_type[f];
-  float R[9];
-  sf::m3_identity(R);
-  if (type != 0) {
-    const int c0 = tb.cas_start[f], n = tb.cas_start[f + 1] - c0;
-    const float inv = 1.0f / (float)n;
-    float ct[3] = {0, 0, 0}, ca[3] = {0, 0, 0};
-    for (int q = 0; q < n; ++q) {
-      const int mj = tb.cas_flat[c0 + q];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        ct[c] += inv * TJ(mj, c);
-        ca[c] += inv * RJ(mj, c);
-      }
-    }
-    float A[9];
-    if (type == 1) {  // multi-joint part: Kabsch on its joints only (:1361-1383)
-      float raw[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, st[3] = {0, 0, 0}, sa[3] = {0, 0, 0}, sw = 0;
-      for (int q = 0; q < n; ++q) {
-        const int mj = tb.cas_flat[c0 + q];
-        const float w = a.jw ? a.jw[(size_t)b * J + mj] : 1.0f;
-        const float t[3] = {TJ(mj, 0), TJ(mj, 1), TJ(mj, 2)}, rj[3] = {RJ(mj, 0), RJ(mj, 1), RJ(mj, 2)};
-        // (the steps of k_rotations_bm's sites, which matter once w is not 1: every sum fused but sa[0], whose product the
-        // compiler packs with w there)
-        float aa[3];
-        {
-#pragma clang fp contract(off)
-          aa[0] = rj[0] * w, aa[1] = rj[1] * w, aa[2] = rj[2] * w;
-          sa[0] = sa[0] + aa[0];
-        }
-        sa[1] = __builtin_fmaf(rj[1], w, sa[1]);
-        sa[2] = __builtin_fmaf(rj[2], w, sa[2]);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-#pragma unroll
-          for (int c = 0; c < 3; ++c) raw[r * 3 + c] = __builtin_fmaf(t[r], aa[c], raw[r * 3 + c]);
-          st[r] = __builtin_fmaf(t[r], w, st[r]);
-        }
-        sw += w;
-      }
-      centered_cov(raw, st, sa, sw, ct, ca, A);
-    } else {
-      centered_cov(ps, ps + 9, ps + 12, ps[15], ct, ca, A);
-    }
-    if (type == 2) {  // bone part: swing + twist (:1389-1412)
-      const int k0 = tb.cas_flat[c0], k1 = tb.cas_flat[c0 + 1];
-      float br[3], bt[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        br[c] = RJ(k1, c) - RJ(k0, c);
-        bt[c] = TJ(k1, c) - TJ(k0, c);
-      }
-      swing_twist_k1r(br, bt, A, R);
-    } else {
-      sf::proj_so3(A, R);
-    }
-  }
-  // ---- compose with the joint's own previous rotation (:422-433; explicit fused steps, as k_rotations_bm_rounds); row
-  // j of ws.GT
-  float G[9];
-  if (a.gprev_mode != 0) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        G[r * 3 + c] = __builtin_fmaf(R[r * 3 + 2], Gp[6 + c], __builtin_fmaf(R[r * 3], Gp[c], R[r * 3 + 1] * Gp[3 + c]));
-    if (J <= kRotJoints * kRefWaves) {  // (k_rotations_bm leaves sf::m3_mul to the compiler, which pairs eight elements
-                                        // into the steps above and forms the first one like this at all four sites)
-#pragma clang fp contract(off)
-      const float p0 = R[0] * Gp[0], p2 = R[2] * Gp[6];
-      G[0] = __builtin_fmaf(R[1], Gp[3], p0) + p2;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) G[k] = R[k];
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) GT[(size_t)(j * 9 + k) * pitch] = G[k];
+  // ---- the part's rotation, composed with the joint's own previous rotation; row j of ws.GT
+  float R[9], G[9];
+  part_rotation(tb, f, ps, tjs, rjs, lane, a.jw, b, R);
+  compose_prev(R, Gp, a.gprev_mode, J <= kRotJoints * kRefWaves, G);
+  store_rotation_row(GT, pitch, j, G);
 }
 
 // the rotations instance-innermost (ws.GT) -> instance-major (ws.G): the wave-per-instance refinement of a model whose
