@@ -240,6 +240,65 @@ typedef struct smplfit_forward_backward_args {
 } smplfit_forward_backward_args;
 int smplfit_forward_backward_f32(const smplfit_handle* h, const smplfit_forward_backward_args* args);
 
+/* BodyModel.rototranslate (pt/bodymodel.py:383-453) for a batch: the body parameters after the rigid transform (R, t),
+ *   new_pose_rotvecs = [mat2rotvec(R rotvec2mat(pose[0:3])), pose[3:]]   (pose[3:] copied bit for bit)
+ *   pelvis    = J_template[0] + J_shapedirs[0, :, :num_betas_given] shape_betas (+ kid_J_shapedir[0] kid_factor)
+ *   new_trans = R trans + t + (R - I) pelvis          (post_translate != 0)
+ *   new_trans = R (trans - t) + (R - I) pelvis        (post_translate == 0)
+ * so that forward(new_pose_rotvecs, shape_betas, new_trans) = R forward(pose_rotvecs, shape_betas, trans) + t (or
+ * R (forward(...) - t)).  R is (B,3,3) with R_per_instance != 0, else one (3,3) for the batch; t likewise (B,3) / (3),
+ * or NULL (= 0).  new_pose_rotvecs may be pose_rotvecs itself (in place: only the three root values are written) and
+ * new_trans may be trans; the buffers must not overlap in any other way.  One kernel launch on hip_stream, no
+ * workspace, no synchronisation; batch == 0 enqueues nothing.  Zero-initialise. */
+typedef struct smplfit_rototranslate_args {
+  const float* R;              /* (B,3,3) or (3,3) */
+  int32_t R_per_instance;
+  const float* t;              /* (B,3), (3) or NULL */
+  int32_t t_per_instance;
+  const float* pose_rotvecs;   /* (B,3J) */
+  const float* shape_betas;    /* (B,num_betas_given) or NULL */
+  int32_t num_betas_given;
+  const float* trans;          /* (B,3) */
+  const float* kid_factor;     /* (B) or NULL (kid handles only) */
+  int32_t post_translate;
+  int32_t batch;
+  float* new_pose_rotvecs;     /* out (B,3J) */
+  float* new_trans;            /* out (B,3) */
+  void* hip_stream;
+} smplfit_rototranslate_args;
+int smplfit_rototranslate_f32(const smplfit_handle* h, const smplfit_rototranslate_args* args);
+
+/* Vector-Jacobian product of smplfit_rototranslate_f32.  Inputs as in the forward struct.  Upstream gradients, each
+ * may be NULL (= zero): grad_new_pose_rotvecs (B,3J), grad_new_trans (B,3).  Outputs, each may be NULL (= not wanted),
+ * always one row per instance — the caller sums the rows of what it shared across the batch, so there are no float
+ * atomics and the result is deterministic: grad_R (B,3,3), grad_t (B,3), grad_pose_rotvecs (B,3J; may be
+ * grad_new_pose_rotvecs itself), grad_shape_betas (B,num_betas_given), grad_trans (B,3), grad_kid_factor (B).
+ * At a root rotation vector of exactly 0 the derivative of the exponential map is [e_i]x (the reference's autograd
+ * returns 0 there); where the log map's |xyz| is 0 its gradient is 0.  One launch, no workspace.  Zero-initialise. */
+typedef struct smplfit_rototranslate_backward_args {
+  const float* R;
+  int32_t R_per_instance;
+  const float* t;
+  int32_t t_per_instance;
+  const float* pose_rotvecs;
+  const float* shape_betas;
+  int32_t num_betas_given;
+  const float* trans;
+  const float* kid_factor;
+  int32_t post_translate;
+  int32_t batch;
+  const float* grad_new_pose_rotvecs;  /* (B,3J) or NULL */
+  const float* grad_new_trans;         /* (B,3) or NULL */
+  float* grad_R;                       /* out (B,3,3) or NULL */
+  float* grad_t;                       /* out (B,3) or NULL */
+  float* grad_pose_rotvecs;            /* out (B,3J) or NULL */
+  float* grad_shape_betas;             /* out (B,num_betas_given) or NULL */
+  float* grad_trans;                   /* out (B,3) or NULL */
+  float* grad_kid_factor;              /* out (B) or NULL */
+  void* hip_stream;
+} smplfit_rototranslate_backward_args;
+int smplfit_rototranslate_backward_f32(const smplfit_handle* h, const smplfit_rototranslate_backward_args* args);
+
 /* Value and gradient of the mesh-distance objective in one call (a refinement step of BodyFlipperOpt):
  *   loss[b] = scale * sum_v w_bv |v_bv - t_bv|,   L = sum_b loss[b],
  * v = the vertices of smplfit_forward_ex_f32 at the inputs (trans included), t = target_vertices, w = vertex_weights

@@ -61,7 +61,7 @@ EXPORTED_SYMBOLS = [
     'smplfit_share_segments_create', 'smplfit_share_segments_destroy', 'smplfit_share_segments_batch',
     'smplfit_share_segments_get_table', 'smplfit_share_segments_workspace_bytes', 'smplfit_fit_segments_f32',
     'smplfit_shape_solve_segments_f32', 'smplfit_gemm_plane_launches', 'smplfit_stage_launches',
-    'smplfit_rotation_spread_launches',
+    'smplfit_rotation_spread_launches', 'smplfit_rototranslate_f32', 'smplfit_rototranslate_backward_f32',
 ]  # fmt: skip
 
 _fp = C.POINTER(C.c_float)
@@ -127,6 +127,29 @@ class ForwardBackwardArgs(C.Structure):
         ('grad_rel_rotmats', C.c_void_p), ('grad_shape_betas', C.c_void_p), ('grad_trans', C.c_void_p),
         ('grad_kid_factor', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
         ('hip_stream', C.c_void_p),
+    ]
+
+
+_RIGID_INPUTS = [
+    ('R', C.c_void_p), ('R_per_instance', C.c_int32), ('t', C.c_void_p), ('t_per_instance', C.c_int32),
+    ('pose_rotvecs', C.c_void_p), ('shape_betas', C.c_void_p), ('num_betas_given', C.c_int32),
+    ('trans', C.c_void_p), ('kid_factor', C.c_void_p), ('post_translate', C.c_int32), ('batch', C.c_int32),
+]
+
+
+class RototranslateArgs(C.Structure):
+    """smplfit_rototranslate_args (include/smplfit.h)."""
+    _fields_ = _RIGID_INPUTS + [
+        ('new_pose_rotvecs', C.c_void_p), ('new_trans', C.c_void_p), ('hip_stream', C.c_void_p),
+    ]
+
+
+class RototranslateBackwardArgs(C.Structure):
+    """smplfit_rototranslate_backward_args (include/smplfit.h)."""
+    _fields_ = _RIGID_INPUTS + [
+        ('grad_new_pose_rotvecs', C.c_void_p), ('grad_new_trans', C.c_void_p), ('grad_R', C.c_void_p),
+        ('grad_t', C.c_void_p), ('grad_pose_rotvecs', C.c_void_p), ('grad_shape_betas', C.c_void_p),
+        ('grad_trans', C.c_void_p), ('grad_kid_factor', C.c_void_p), ('hip_stream', C.c_void_p),
     ]
 
 
@@ -331,6 +354,10 @@ def load():
     lib.smplfit_forward_backward_workspace_bytes.restype = sz
     lib.smplfit_forward_backward_f32.argtypes = [vp, C.POINTER(ForwardBackwardArgs)]
     lib.smplfit_forward_backward_f32.restype = i32
+    lib.smplfit_rototranslate_f32.argtypes = [vp, C.POINTER(RototranslateArgs)]
+    lib.smplfit_rototranslate_f32.restype = i32
+    lib.smplfit_rototranslate_backward_f32.argtypes = [vp, C.POINTER(RototranslateBackwardArgs)]
+    lib.smplfit_rototranslate_backward_f32.restype = i32
     lib.smplfit_mesh_objective_workspace_bytes.argtypes = [vp, i32]
     lib.smplfit_mesh_objective_workspace_bytes.restype = sz
     lib.smplfit_mesh_objective_f32.argtypes = [vp, C.POINTER(MeshObjectiveArgs)]

@@ -17,6 +17,8 @@
 //   k_obj_vertex                                           value + gradient of the mesh-distance objective (same file)
 //   k_adj_gram, k_adj_apply, k_adj_combine                 adjoint of the shape solve: gradients of fit_with_known_pose
 //                                                          (kernels_adj.inc)
+//   k_rototranslate, k_rototranslate_backward              BodyModel.rototranslate and its backward: lane = instance,
+//                                                          pose rows copied coalesced (kernels_rigid.inc)
 // Batch-major kernels (LANE = INSTANCE; the default vertex block where they apply, see route_of): k_layout_targets,
 //   k_mean_finish, k_template_partsum_bm, k_residual_bm, k_pair_gram_bm, k_gram_combine_bm, k_lbs_partsum_bm,
 //   k_psum_combine, k_regress_joints_bm, k_transpose_targets (joint rows) — grid = (vertex group | unit chunk) x
@@ -37,6 +39,7 @@
 #include <type_traits>
 
 #include "../../include/smplfit.h"
+#include "sf_rigid.h"
 #include "sf_stages.h"
 #include "sf_tables.h"
 
@@ -495,6 +498,7 @@ __device__ __forceinline__ void st_stream(float* p, float v) {
 #include "kernels_gen.inc"
 #include "kernels_bwd.inc"
 #include "kernels_adj.inc"
+#include "kernels_rigid.inc"
 
 // ------------------------------------------------------------------------------------------------
 // launch helpers
@@ -953,11 +957,17 @@ int launch_lbs_any(const DevModel& d, const Workspace& ws, int B, bool weighted,
 
 // Handle, batch and workspace of every entry point `who`.  needed: what the entry's workspace query `query` answers
 // for this handle and batch (the queries answer 0 for a null handle or a batch <= 0, so they may be asked first).
+// check_handle: the handle alone, for the entries without workspace whose empty batch is a call that enqueues nothing
+// (smplfit_rototranslate_f32 and its backward).
+int check_handle(const char* who, const smplfit_handle* h) {
+  if (!h) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null handle");
+  if (!h->has_device) return fail(SMPLFIT_ERR_HIP, std::string(who) + ": handle was created host-only (no device)");
+  return 0;
+}
 int check_call(const char* who, const smplfit_handle* h, int batch, const void* workspace, size_t given, size_t needed,
                const char* query) {
   const auto bad = [who](int code, const std::string& what) { return fail(code, std::string(who) + ": " + what); };
-  if (!h) return bad(SMPLFIT_ERR_BAD_ARG, "null handle");
-  if (!h->has_device) return bad(SMPLFIT_ERR_HIP, "handle was created host-only (no device)");
+  if (int rc = check_handle(who, h)) return rc;
   if (batch <= 0) return bad(SMPLFIT_ERR_BAD_ARG, "batch must be positive");
   if (!workspace || ((uintptr_t)workspace & 255))
     return bad(SMPLFIT_ERR_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
@@ -1013,6 +1023,36 @@ ForwardArgs forward_args(const ForwardInputs& in, int nb, const float* trans, fl
   fa.joints = joints;
   fa.orient = orient;
   return fa;
+}
+
+// BodyModel.rototranslate (smplfit_rototranslate_f32 and its backward): the inputs both entries share, checked before
+// anything is enqueued (the betas / kid rules are check_forward_inputs'), as the kernels' argument struct.
+template <class A>
+int rigid_inputs(const char* who, const smplfit_handle* h, const A& a, RigidInputs* out) {
+  if (int rc = check_handle(who, h)) return rc;
+  if (a.batch < 0) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": batch must not be negative");
+  if (!a.R || !a.pose_rotvecs || !a.trans)
+    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": R, pose_rotvecs and trans are required");
+  const DevModel& d = h->d;
+  const ForwardInputs in{a.pose_rotvecs, nullptr, nullptr, a.shape_betas, a.kid_factor, a.num_betas_given};
+  if (int rc = check_forward_inputs(who, d, in)) return rc;
+  RigidInputs r{};
+  r.j_ext = d.jt.j_ext;
+  r.S = d.S;
+  r.J3 = 3 * d.J;
+  r.R = a.R;
+  r.R_stride = a.R_per_instance ? 9 : 0;
+  r.t = a.t;
+  r.t_stride = a.t_per_instance ? 3 : 0;
+  r.pose = a.pose_rotvecs;
+  r.betas = in.betas;
+  r.nb = backward_nb(in);
+  if (!r.nb) r.betas = nullptr;
+  r.kid = in.kid;
+  r.trans = a.trans;
+  r.post = a.post_translate != 0;
+  *out = r;
+  return 0;
 }
 
 // Arithmetic of the posedirs contraction: "bf16x3" (default) runs it on the bf16 matrix cores with every fp32
@@ -3356,6 +3396,43 @@ int smplfit_forward_backward_f32(const smplfit_handle* h, const smplfit_forward_
   ct.joints = a->grad_joints;
   ct.orient = a->grad_orientations;
   if (int rc = launch_forward_backward(h, in, backward_nb(in), ct, grad_outputs(*a), l, B, (hipStream_t)a->hip_stream)) return rc;
+  return post_launch_check();
+}
+
+// ---- BodyModel.rototranslate: one launch, no workspace (rigid_inputs) ----------------------------------
+int smplfit_rototranslate_f32(const smplfit_handle* h, const smplfit_rototranslate_args* a) {
+  const char* who = "smplfit_rototranslate_f32";
+  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
+  RigidInputs in;
+  if (int rc = rigid_inputs(who, h, *a, &in)) return rc;
+  if (!a->new_pose_rotvecs || !a->new_trans) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null output pointer");
+  const int B = a->batch;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(k_rototranslate, dim3((B + kRigidBlock - 1) / kRigidBlock), dim3(kRigidBlock), 0,
+                     (hipStream_t)a->hip_stream, in, a->new_pose_rotvecs, a->new_trans, B);
+  return post_launch_check();
+}
+
+int smplfit_rototranslate_backward_f32(const smplfit_handle* h, const smplfit_rototranslate_backward_args* a) {
+  const char* who = "smplfit_rototranslate_backward_f32";
+  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
+  RigidInputs in;
+  if (int rc = rigid_inputs(who, h, *a, &in)) return rc;
+  if (a->grad_kid_factor && !h->d.jt.n_kid)
+    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": grad_kid_factor asked of a handle without kid");
+  const int B = a->batch;
+  if (B == 0) return 0;
+  RigidGrads g{};
+  g.g_pose = a->grad_new_pose_rotvecs;
+  g.g_trans = a->grad_new_trans;
+  g.gR = a->grad_R;
+  g.gt = a->grad_t;
+  g.gpose = a->grad_pose_rotvecs;
+  g.gbetas = in.betas ? a->grad_shape_betas : nullptr;
+  g.gtrans = a->grad_trans;
+  g.gkid = a->grad_kid_factor;
+  hipLaunchKernelGGL(k_rototranslate_backward, dim3((B + kRigidBlock - 1) / kRigidBlock), dim3(kRigidBlock), 0,
+                     (hipStream_t)a->hip_stream, in, g, B);
   return post_launch_check();
 }
 

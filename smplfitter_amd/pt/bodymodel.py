@@ -1,6 +1,8 @@
 """``BodyModel`` — same surface as ``smplfitter.pt.BodyModel`` (reference
 src/smplfitter/pt/bodymodel.py:12-453), with ``forward`` dispatched to the HIP LBS kernels through the
-C-ABI (``smplfit_forward_f32``).  PyTorch tensors are containers only: device memory + stream.
+C-ABI (``smplfit_forward_f32``) and ``rototranslate`` to its own kernel (``smplfit_rototranslate_f32``).  One
+extension of that surface: ``rototranslate`` also takes a batch.  PyTorch tensors are containers only: device memory +
+stream.
 """
 
 from __future__ import annotations
@@ -14,6 +16,12 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from .. import _lib, modelio
+
+
+_NO_CPU_PATH = (
+    'smplfitter_amd runs on MI355X through its HIP kernels only: move the model and the '
+    "inputs to a 'cuda' (ROCm) device. There is no CPU path."
+)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -78,10 +86,7 @@ class BodyModel(nn.Module):
         """The C-ABI handle holding this model's constants on ``device`` (created on first use).
         ``kid=True``: the variant whose last shape unknown is the kid blend shape."""
         if device.type != 'cuda':
-            raise RuntimeError(
-                'smplfitter_amd runs on MI355X through its HIP kernels only: move the model and the '
-                "inputs to a 'cuda' (ROCm) device. There is no CPU path."
-            )
+            raise RuntimeError(_NO_CPU_PATH)
         idx = device.index if device.index is not None else torch.cuda.current_device()
         h = self._handles.get((idx, kid))
         if h is None:
@@ -402,6 +407,196 @@ class BodyModel(nn.Module):
         res = self.forward(u(pose_rotvecs), u(shape_betas), u(trans), kid_factor, u(rel_rotmats),
                            u(glob_rotmats), return_vertices)
         return {k: v.squeeze(0) for k, v in res.items()}
+
+    # -- rototranslate ---------------------------------------------------------------------------
+    def rototranslate(
+        self,
+        R: torch.Tensor,
+        t: Optional[torch.Tensor] = None,
+        pose_rotvecs: Optional[torch.Tensor] = None,
+        shape_betas: Optional[torch.Tensor] = None,
+        trans: Optional[torch.Tensor] = None,
+        kid_factor: Optional[torch.Tensor] = None,
+        post_translate: bool = True,
+    ) -> tuple[torch.Tensor, torch.Tensor]:
+        """Rotates and translates the body in parametric form (pt/bodymodel.py:383-453): the parameters
+        ``(new_pose_rotvecs, new_trans)`` with ``forward(new_pose_rotvecs, shape_betas, new_trans) = R @ forward(
+        pose_rotvecs, shape_betas, trans) + t`` (``post_translate``) or ``R @ (forward(...) - t)`` (otherwise).  The root
+        rotation acts about the pelvis of the shaped T-pose, so the translation carries ``(R - I) @ pelvis``.  One HIP
+        launch (``smplfit_rototranslate_f32``).
+
+        Unbatched, as the reference: ``R`` (3, 3), ``t`` (3,) or None, ``pose_rotvecs`` (3J,), ``shape_betas`` (n,) with
+        ``n <= num_betas``, ``trans`` (3,), ``kid_factor`` (1,) or None; returns (3J,) and (3,).
+
+        Batched (no counterpart in the reference): ``pose_rotvecs`` (B, 3J) and ``trans`` (B, 3) with ``R`` (3, 3) or
+        (B, 3, 3), ``t`` None, (3,) or (B, 3), ``shape_betas`` (n,) or (B, n), ``kid_factor`` None, a scalar, (1,) or
+        (B,); returns (B, 3J) and (B, 3).  ``B = 0`` returns empty tensors.
+
+        Differentiable like ``forward``: with gradients enabled and a tensor input that requires grad, the backward is
+        the HIP vector-Jacobian product (``smplfit_rototranslate_backward_f32``) with respect to all six inputs, once
+        differentiable; an input shared across the batch gets the sum over the rows.  At a root rotation vector of
+        exactly zero the gradient is the true derivative of the exponential map, not 0."""
+        if pose_rotvecs is None or shape_betas is None or trans is None:
+            raise ValueError('pose_rotvecs, shape_betas, and trans are required.')
+        if torch.compiler.is_compiling():  # one opaque operator for torch.compile / export
+            kid = kid_factor
+            if kid is not None and not isinstance(kid, torch.Tensor):
+                kid = torch.as_tensor(kid, dtype=torch.float32, device=self.v_template.device)
+            p, tr = torch.ops.smplfitter_amd.rototranslate(
+                self._model_id, R, t, pose_rotvecs, shape_betas, trans, kid, post_translate)
+            return p, tr
+        ins = (R, t, pose_rotvecs, shape_betas, trans, kid_factor)
+        if torch.is_grad_enabled() and any(isinstance(a, torch.Tensor) and a.requires_grad for a in ins):
+            return _RototranslateFn.apply(self, post_translate, *ins)
+        return self._rototranslate_direct(*ins, post_translate)
+
+    def _rigid_inputs(self, R, t, pose_rotvecs, shape_betas, trans, kid_factor):
+        """The inputs of ``rototranslate`` checked and as detached contiguous fp32 tensors in the C-ABI's shapes:
+        ``pose`` (B, 3J), ``trans`` (B, 3), ``R`` (B, 3, 3) or (3, 3), ``t`` (B, 3), (3,) or None, ``betas`` (B, n) and
+        ``kid`` (B) or None (both expanded here when shared; ``R`` and ``t`` are shared inside the kernel)."""
+        device = self.v_template.device
+        J3 = 3 * self.num_joints
+        named = dict(R=R, t=t, pose_rotvecs=pose_rotvecs, shape_betas=shape_betas, trans=trans, kid_factor=kid_factor)
+        for name, a in named.items():
+            if isinstance(a, np.ndarray):
+                raise TypeError(f"Expected torch.Tensor for '{name}', got numpy.ndarray. "
+                                f'Convert with torch.from_numpy() or torch.as_tensor().')
+            if isinstance(a, torch.Tensor) and a.device.type != 'cuda':
+                raise RuntimeError(_NO_CPU_PATH)
+        if device.type != 'cuda':
+            raise RuntimeError(_NO_CPU_PATH)
+        prep = lambda a: a.detach().to(device=device, dtype=torch.float32)  # noqa: E731
+        single = pose_rotvecs.ndim == 1
+        bad = lambda name, a, want: ValueError(  # noqa: E731
+            f"rototranslate: '{name}' must have shape {want}, got {tuple(a.shape)}")
+        pose = prep(pose_rotvecs)
+        if single:
+            pose = pose[None]
+        if pose.ndim != 2 or pose.shape[1] != J3:
+            raise bad('pose_rotvecs', pose_rotvecs, f'({J3},) or (batch, {J3})')
+        B = pose.shape[0]
+        tr = prep(trans)
+        if tuple(tr.shape) != ((3,) if single else (B, 3)):
+            raise bad('trans', trans, '(3,)' if single else f'({B}, 3)')
+        tr = tr.reshape(B, 3)
+        Rm = prep(R)
+        if tuple(Rm.shape) != (3, 3) and (single or tuple(Rm.shape) != (B, 3, 3)):
+            raise bad('R', R, '(3, 3)' if single else f'(3, 3) or ({B}, 3, 3)')
+        tt = None
+        if t is not None:
+            tt = prep(t)
+            if tuple(tt.shape) != (3,) and (single or tuple(tt.shape) != (B, 3)):
+                raise bad('t', t, '(3,)' if single else f'(3,) or ({B}, 3)')
+        betas = prep(shape_betas)
+        if betas.ndim == 2 and not single and betas.shape[0] == B:
+            betas_shared = False
+        elif betas.ndim == 1:
+            betas_shared = True
+            betas = betas[None].expand(B, betas.shape[0])
+        else:
+            raise bad('shape_betas', shape_betas, '(n,)' if single else f'(n,) or ({B}, n)')
+        nb = betas.shape[1]
+        if nb > self.num_betas:
+            raise ValueError(f'rototranslate: {nb} shape_betas given to a model of {self.num_betas}')
+        kid, kid_shared = None, False
+        if kid_factor is not None:
+            kid = torch.as_tensor(kid_factor, dtype=torch.float32, device=device).detach().reshape(-1)
+            kid_shared = kid.numel() == 1
+            if not kid_shared and (single or kid.numel() != B or kid_factor.ndim != 1):
+                raise bad('kid_factor', kid_factor, '(1,)' if single else f'a scalar, (1,) or ({B},)')
+            kid = kid.expand(B).contiguous()
+        c = lambda a: None if a is None else a.contiguous()  # noqa: E731
+        return dict(single=single, B=B, R=c(Rm), R_per=Rm.ndim == 3, t=c(tt), t_per=tt is not None and tt.ndim == 2,
+                    pose=c(pose), betas=c(betas) if nb else None, nb=nb, betas_shared=betas_shared, trans=c(tr),
+                    kid=kid, kid_shared=kid_shared)
+
+    @staticmethod
+    def _rigid_fields(x, stream):
+        p = lambda a: None if a is None else a.data_ptr()  # noqa: E731
+        return dict(R=p(x['R']), R_per_instance=int(x['R_per']), t=p(x['t']), t_per_instance=int(x['t_per']),
+                    pose_rotvecs=p(x['pose']), shape_betas=p(x['betas']), num_betas_given=x['nb'], trans=p(x['trans']),
+                    kid_factor=p(x['kid']), batch=x['B'], hip_stream=stream)
+
+    def _rototranslate_direct(self, R, t, pose_rotvecs, shape_betas, trans, kid_factor, post_translate=True):
+        """The C-ABI call behind ``rototranslate`` (and behind the ``smplfitter_amd::rototranslate`` operator)."""
+        x = self._rigid_inputs(R, t, pose_rotvecs, shape_betas, trans, kid_factor)
+        device = self.v_template.device
+        B = x['B']
+        new_pose = torch.empty((B, 3 * self.num_joints), dtype=torch.float32, device=device)
+        new_trans = torch.empty((B, 3), dtype=torch.float32, device=device)
+        if B:
+            h = self._native(device, kid=x['kid'] is not None)
+            with torch.cuda.device(device):
+                stream = torch.cuda.current_stream(device).cuda_stream
+                args = _lib.RototranslateArgs(
+                    post_translate=int(bool(post_translate)), new_pose_rotvecs=new_pose.data_ptr(),
+                    new_trans=new_trans.data_ptr(), **self._rigid_fields(x, stream))
+                _lib.check(_lib.load().smplfit_rototranslate_f32(h.ptr, C.byref(args)))
+        return (new_pose[0], new_trans[0]) if x['single'] else (new_pose, new_trans)
+
+    def _rototranslate_backward_direct(self, R, t, pose_rotvecs, shape_betas, trans, kid_factor, post_translate,
+                                       grad_pose=None, grad_trans=None):
+        """The C-ABI call behind ``rototranslate``'s backward (``smplfit_rototranslate_backward_f32``): the gradients of
+        the six inputs (None for one that is no tensor), each in the caller's shape and dtype; what was shared across
+        the batch gets the sum of the per-row gradients (one ``sum(0)``: deterministic)."""
+        ins = (R, t, pose_rotvecs, shape_betas, trans, kid_factor)
+        x = self._rigid_inputs(*ins)
+        device = self.v_template.device
+        B, nb = x['B'], x['nb']
+        out = [torch.zeros_like(a) if isinstance(a, torch.Tensor) else None for a in ins]
+        if B == 0:
+            return out
+        g = lambda a, w: None if a is None else a.detach().to(device=device, dtype=torch.float32).reshape(B, w).contiguous()  # noqa: E731
+        gp, gt_in = g(grad_pose, 3 * self.num_joints), g(grad_trans, 3)
+        new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=device)  # noqa: E731
+        g_R, g_pose, g_tr = new(B, 3, 3), new(B, 3 * self.num_joints), new(B, 3)
+        g_t = new(B, 3) if isinstance(t, torch.Tensor) else None
+        g_betas = new(B, nb) if nb else None
+        g_kid = new(B) if isinstance(kid_factor, torch.Tensor) else None
+        h = self._native(device, kid=x['kid'] is not None)
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            p = lambda a: None if a is None else a.data_ptr()  # noqa: E731
+            args = _lib.RototranslateBackwardArgs(
+                post_translate=int(bool(post_translate)), grad_new_pose_rotvecs=p(gp), grad_new_trans=p(gt_in),
+                grad_R=p(g_R), grad_t=p(g_t), grad_pose_rotvecs=p(g_pose), grad_shape_betas=p(g_betas),
+                grad_trans=p(g_tr), grad_kid_factor=p(g_kid), **self._rigid_fields(x, stream))
+            _lib.check(_lib.load().smplfit_rototranslate_backward_f32(h.ptr, C.byref(args)))
+        give = lambda gr, a, shared: (gr.sum(0) if shared else gr).reshape(a.shape).to(a.dtype)  # noqa: E731
+        out[0] = give(g_R, R, not x['R_per'])
+        if g_t is not None:
+            out[1] = give(g_t, t, not x['t_per'])
+        out[2] = give(g_pose, pose_rotvecs, False)
+        if g_betas is not None:
+            out[3] = give(g_betas, shape_betas, x['betas_shared'])
+        out[4] = give(g_tr, trans, False)
+        if g_kid is not None:
+            out[5] = give(g_kid, kid_factor, x['kid_shared'])
+        return out
+
+
+class _RototranslateFn(torch.autograd.Function):
+    """``BodyModel.rototranslate`` under autograd: the forward is ``_rototranslate_direct`` (bit for bit the no-grad
+    result), the backward ``_rototranslate_backward_direct`` on the current stream.  Only the inputs are saved."""
+
+    @staticmethod
+    def forward(ctx, model, post_translate, R, t, pose_rotvecs, shape_betas, trans, kid_factor):
+        ins = (R, t, pose_rotvecs, shape_betas, trans, kid_factor)
+        ctx.model, ctx.post_translate = model, post_translate
+        ctx.set_materialize_grads(False)
+        ctx.tensor_mask = [isinstance(a, torch.Tensor) for a in ins]
+        ctx.others = [None if m else a for m, a in zip(ctx.tensor_mask, ins)]
+        ctx.save_for_backward(*[a for a in ins if isinstance(a, torch.Tensor)])
+        return model._rototranslate_direct(*ins, post_translate)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_pose, g_trans):
+        saved = iter(ctx.saved_tensors)
+        ins = [next(saved) if m else o for m, o in zip(ctx.tensor_mask, ctx.others)]
+        grads = ctx.model._rototranslate_backward_direct(*ins, ctx.post_translate, g_pose, g_trans)
+        grads = [gr if isinstance(a, torch.Tensor) and a.requires_grad else None for gr, a in zip(grads, ins)]
+        return (None, None, *grads)
 
 
 class _ForwardFn(torch.autograd.Function):

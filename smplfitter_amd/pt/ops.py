@@ -155,3 +155,60 @@ def _forward_backward_formula(ctx, grads):
 
 
 forward.register_autograd(_forward_backward_formula, setup_context=_forward_setup_context)
+
+
+@custom_op('smplfitter_amd::rototranslate', mutates_args=())
+def rototranslate(
+    model_id: int, R: torch.Tensor, t: Optional[torch.Tensor], pose_rotvecs: torch.Tensor, shape_betas: torch.Tensor,
+    trans: torch.Tensor, kid_factor: Optional[torch.Tensor], post_translate: bool,
+) -> List[torch.Tensor]:
+    """[new_pose_rotvecs, new_trans] of ``BodyModel.rototranslate``, in the shapes of pose_rotvecs and trans."""
+    return list(_model(model_id)._rototranslate_direct(R, t, pose_rotvecs, shape_betas, trans, kid_factor,
+                                                       post_translate))
+
+
+@rototranslate.register_fake
+def _(model_id, R, t, pose_rotvecs, shape_betas, trans, kid_factor, post_translate):
+    dev = _model_device(model_id)
+    return [pose_rotvecs.new_empty(pose_rotvecs.shape, dtype=torch.float32, device=dev),
+            trans.new_empty(trans.shape, dtype=torch.float32, device=dev)]
+
+
+@custom_op('smplfitter_amd::rototranslate_backward', mutates_args=())
+def rototranslate_backward(
+    model_id: int, R: torch.Tensor, t: Optional[torch.Tensor], pose_rotvecs: torch.Tensor, shape_betas: torch.Tensor,
+    trans: torch.Tensor, kid_factor: Optional[torch.Tensor], post_translate: bool,
+    grad_pose_rotvecs: Optional[torch.Tensor], grad_trans: Optional[torch.Tensor],
+) -> List[torch.Tensor]:
+    """Gradients of ``rototranslate`` w.r.t. [R, t, pose_rotvecs, shape_betas, trans, kid_factor], each in its input's
+    shape (an empty tensor for an input not given)."""
+    gs = _model(model_id)._rototranslate_backward_direct(R, t, pose_rotvecs, shape_betas, trans, kid_factor,
+                                                         post_translate, grad_pose_rotvecs, grad_trans)
+    dev = _model_device(model_id)
+    return [g if g is not None else torch.empty((0,), device=dev) for g in gs]
+
+
+@rototranslate_backward.register_fake
+def _(model_id, R, t, pose_rotvecs, shape_betas, trans, kid_factor, post_translate, grad_pose_rotvecs, grad_trans):
+    dev = _model_device(model_id)
+    return [torch.empty_like(a) if a is not None else torch.empty((0,), device=dev)
+            for a in (R, t, pose_rotvecs, shape_betas, trans, kid_factor)]
+
+
+def _rototranslate_setup_context(ctx, inputs, output):
+    model_id, R, t, pose_rotvecs, shape_betas, trans, kid_factor, post_translate = inputs
+    ctx.model_id, ctx.post_translate = model_id, post_translate
+    ins = (R, t, pose_rotvecs, shape_betas, trans, kid_factor)
+    ctx.present = [a is not None for a in ins]
+    ctx.save_for_backward(*[a for a in ins if a is not None])
+
+
+def _rototranslate_backward_formula(ctx, grads):
+    g_pose, g_trans = grads
+    saved = iter(ctx.saved_tensors)
+    ins = [next(saved) if p else None for p in ctx.present]
+    gs = torch.ops.smplfitter_amd.rototranslate_backward(ctx.model_id, *ins, ctx.post_translate, g_pose, g_trans)
+    return (None, *[g if p else None for g, p in zip(gs, ctx.present)], None)
+
+
+rototranslate.register_autograd(_rototranslate_backward_formula, setup_context=_rototranslate_setup_context)
