@@ -827,6 +827,54 @@ int smplfit_fit_segments_f32(const smplfit_handle* h, const smplfit_fit_args* ar
 int smplfit_shape_solve_segments_f32(const smplfit_handle* h, const smplfit_shape_solve_args* args,
                                      const smplfit_share_segments* plan);
 
+/* ---- mesh error: the model at given parameters, measured against the targets ----------
+ * What follows a fit: the parametric mesh and joints at its parameters, and how far each vertex and joint lies from
+ * its target.
+ *   vertices (B,V,3), joints (B,J,3)   the forward at the inputs (the bits of smplfit_forward_ex_f32)
+ *   vertex_error (B,V)                 |vertices[b,v] - target_vertices[b,v]|, Euclidean
+ *   joint_error (B,J)                  |joints[b,j] - target_joints[b,j]|
+ * The errors are unweighted.  A non-finite target or parameter row gives non-finite values in that row alone.  Each of
+ * the four outputs may be NULL, at least one must be given (SMPLFIT_ERR_BAD_ARG); joint_error without target_joints
+ * is SMPLFIT_ERR_BAD_ARG.  Where `vertices` is NULL on the batch-major kernels no (B,V,3) is written anywhere.  A
+ * refused call enqueues nothing and leaves the outputs as they were.  Zero-initialise the structs.
+ *   smplfit_mesh_error_f32: the step on its own.  The inputs of the forward's argument struct: one rotation form or none, betas,
+ *   kid, trans; target_vertices (required) and target_joints.  Workspace: smplfit_mesh_error_workspace_bytes(h, batch).
+ *   smplfit_fit_recon_f32: smplfit_fit_segments_f32 (plan may be NULL) followed, on the same stream, by the step at
+ *   the fit's own orientations, shape_betas, kid_factor and trans against the fit's targets.  Every result of the fit
+ *   keeps the bits of the call without reconstruction.  args->scale_mode != 0: SMPLFIT_ERR_UNSUPPORTED.  A NULL
+ *   `recon` makes it smplfit_fit_segments_f32.  Workspace (args->workspace): smplfit_fit_recon_workspace_bytes(h,
+ *   batch, plan); 0 for a batch that is not the plan's. */
+typedef struct smplfit_mesh_error_args {
+  const float* pose_rotvecs;   /* (B,3J) or NULL */
+  const float* glob_rotmats;   /* (B,J,3,3) or NULL */
+  const float* rel_rotmats;    /* (B,J,3,3) or NULL */
+  const float* shape_betas;    /* (B,num_betas_given) or NULL */
+  int32_t num_betas_given;
+  const float* trans;          /* (B,3) or NULL */
+  const float* kid_factor;     /* (B) or NULL */
+  int32_t batch;
+  const float* target_vertices; /* (B,V,3) */
+  const float* target_joints;   /* (B,J,3) or NULL */
+  float* vertices;             /* out (B,V,3) or NULL */
+  float* joints;               /* out (B,J,3) or NULL */
+  float* vertex_error;         /* out (B,V) or NULL */
+  float* joint_error;          /* out (B,J) or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  void* hip_stream;
+} smplfit_mesh_error_args;
+size_t smplfit_mesh_error_workspace_bytes(const smplfit_handle* h, int batch);
+int smplfit_mesh_error_f32(const smplfit_handle* h, const smplfit_mesh_error_args* args);
+typedef struct smplfit_fit_recon_args {
+  float* vertices;             /* out (B,V,3) or NULL */
+  float* joints;               /* out (B,J,3) or NULL */
+  float* vertex_error;         /* out (B,V) or NULL */
+  float* joint_error;          /* out (B,J) or NULL; needs args->target_joints */
+} smplfit_fit_recon_args;
+size_t smplfit_fit_recon_workspace_bytes(const smplfit_handle* h, int batch, const smplfit_share_segments* plan);
+int smplfit_fit_recon_f32(const smplfit_handle* h, const smplfit_fit_args* args, const smplfit_share_segments* plan,
+                          const smplfit_fit_recon_args* recon);
+
 /* Re-reads the SMPLFIT_* tuning variables (INTEGRATION.md lists them).  They are read once, at first use; tests and
  * the A/B tools that switch kernel paths inside one process call this after changing the environment.  Not to be
  * called while other threads are inside the library. */

@@ -62,7 +62,12 @@ EXPORTED_SYMBOLS = [
     'smplfit_share_segments_get_table', 'smplfit_share_segments_workspace_bytes', 'smplfit_fit_segments_f32',
     'smplfit_shape_solve_segments_f32', 'smplfit_gemm_plane_launches', 'smplfit_stage_launches',
     'smplfit_rotation_spread_launches', 'smplfit_rototranslate_f32', 'smplfit_rototranslate_backward_f32',
+    'smplfit_mesh_error_workspace_bytes', 'smplfit_mesh_error_f32', 'smplfit_fit_recon_workspace_bytes',
+    'smplfit_fit_recon_f32',
 ]  # fmt: skip
+
+# the result keys of the mesh-error step (BodyFitter.fit(requested_keys=...), BodyModel.mesh_error)
+RECON_KEYS = ('vertices', 'joints', 'vertex_error', 'joint_error')
 
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -115,6 +120,24 @@ class ForwardArgs(C.Structure):
         ('orientations', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
         ('hip_stream', C.c_void_p),
     ]
+
+
+class MeshErrorArgs(C.Structure):
+    """smplfit_mesh_error_args (include/smplfit.h)."""
+    _fields_ = [
+        ('pose_rotvecs', C.c_void_p), ('glob_rotmats', C.c_void_p), ('rel_rotmats', C.c_void_p),
+        ('shape_betas', C.c_void_p), ('num_betas_given', C.c_int32), ('trans', C.c_void_p),
+        ('kid_factor', C.c_void_p), ('batch', C.c_int32), ('target_vertices', C.c_void_p),
+        ('target_joints', C.c_void_p), ('vertices', C.c_void_p), ('joints', C.c_void_p),
+        ('vertex_error', C.c_void_p), ('joint_error', C.c_void_p), ('workspace', C.c_void_p),
+        ('workspace_bytes', C.c_size_t), ('hip_stream', C.c_void_p),
+    ]
+
+
+class FitReconArgs(C.Structure):
+    """smplfit_fit_recon_args (include/smplfit.h)."""
+    _fields_ = [('vertices', C.c_void_p), ('joints', C.c_void_p), ('vertex_error', C.c_void_p),
+                ('joint_error', C.c_void_p)]
 
 
 class ForwardBackwardArgs(C.Structure):
@@ -437,6 +460,15 @@ def load():
     if hasattr(lib, 'smplfit_rotation_spread_launches'):  # (as above)
         lib.smplfit_rotation_spread_launches.argtypes = []
         lib.smplfit_rotation_spread_launches.restype = C.c_uint64
+    if hasattr(lib, 'smplfit_mesh_error_f32'):  # (as above)
+        lib.smplfit_mesh_error_workspace_bytes.argtypes = [vp, i32]
+        lib.smplfit_mesh_error_workspace_bytes.restype = sz
+        lib.smplfit_mesh_error_f32.argtypes = [vp, C.POINTER(MeshErrorArgs)]
+        lib.smplfit_mesh_error_f32.restype = i32
+        lib.smplfit_fit_recon_workspace_bytes.argtypes = [vp, i32, vp]
+        lib.smplfit_fit_recon_workspace_bytes.restype = sz
+        lib.smplfit_fit_recon_f32.argtypes = [vp, C.POINTER(FitArgs), vp, C.POINTER(FitReconArgs)]
+        lib.smplfit_fit_recon_f32.restype = i32
     if os.environ.get('SMPLFIT_LIB') and not hasattr(lib, 'smplfit_abi_version'):
         _lib = lib  # an older build loaded by the A/B tools (tools/ab_fit.py): no version / share-table exports
         return lib
@@ -542,6 +574,12 @@ class Handle:
 
     def workspace_bytes(self, batch: int) -> int:
         return int(load().smplfit_workspace_bytes(self._h, int(batch)))
+
+    def mesh_error_workspace_bytes(self, batch: int) -> int:
+        return int(load().smplfit_mesh_error_workspace_bytes(self._h, int(batch)))
+
+    def fit_recon_workspace_bytes(self, batch: int, plan: 'ShareSegments | None' = None) -> int:
+        return int(load().smplfit_fit_recon_workspace_bytes(self._h, int(batch), plan.ptr if plan is not None else None))
 
     def forward_backward_workspace_bytes(self, batch: int) -> int:
         return int(load().smplfit_forward_backward_workspace_bytes(self._h, int(batch)))

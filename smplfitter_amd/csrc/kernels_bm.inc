@@ -183,6 +183,90 @@ __global__ __launch_bounds__(256) void k_unlayout_vertices(DevModel m, const flo
   }
 }
 
+// The measuring form of k_unlayout_vertices (the mesh-error step, launch_mesh_error): the same tile of the posed mesh,
+// turned in LDS the same way; the caller's target tile is then read in the pattern the BLEND form reads `in` (element
+// e = tid + 256 i: consecutive lanes, consecutive floats of an instance's run) and every element of the tile is replaced
+// by mesh - target by the one thread that owns it — which, WRITE_MESH, first stores the mesh value to `out`, the plain
+// form's store.  Behind a second barrier a thread takes a (instance, vertex) pair, reads its three differences — three
+// scalar LDS reads: kSlabRow is odd, so a vertex's words are 4-byte aligned only — and writes the distance to
+// err (B, V): 32 consecutive lanes write the 128 contiguous bytes of an instance's kSlabV vertices.  Without WRITE_MESH
+// no (B, V, 3) is written.  Rows >= B and vertices >= V are neither read from the target nor written; every output
+// element has one writer.  grid (ceil(V/kSlabV), Mp/64), block 256, as the plain form.
+__device__ __forceinline__ float point_distance(float dx, float dy, float dz) {
+  return __fsqrt_rn(__fmaf_rn(dz, dz, __fmaf_rn(dy, dy, __fmul_rn(dx, dx))));
+}
+template <bool WRITE_MESH>
+__global__ __launch_bounds__(256) void k_unlayout_error(DevModel m, const float* __restrict__ vT, float* __restrict__ out,
+                                                        const float* __restrict__ target, float* __restrict__ err, int B) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];  // [64][kSlabRow]
+  const int slab = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int V = m.V, Vp = m.Vp;
+  const int v0 = slab * kSlabV, nv = min(kSlabV, V - v0), nf = 3 * nv;
+  const size_t tile = ((size_t)blk * 64 * V + v0) * 3;  // the tile's first float in a (B, V, 3) tensor
+  const float* src = vT + (size_t)blk * 3 * Vp * 64 + lane;
+  constexpr int NR = kSlabF / 4, UB = NR % 12 == 0 ? 12 : 8;
+  static_assert(NR % UB == 0, "rows per wave");
+#pragma unroll
+  for (int k0 = 0; k0 < NR; k0 += UB) {
+    float x[UB];
+#pragma unroll
+    for (int k = 0; k < UB; ++k) {
+      const int j = wave + 4 * (k0 + k), jj = j < nf ? j : 0, vl = jj / 3, c = jj - vl * 3;
+      x[k] = ld_stream<1>(src + ((size_t)c * Vp + m.inv_slot[v0 + vl]) * 64);
+    }
+#pragma unroll
+    for (int k = 0; k < UB; ++k) {
+      const int j = wave + 4 * (k0 + k);
+      if (j < nf) smem[lane * kSlabRow + j] = x[k];
+    }
+  }
+  __syncthreads();
+  // ---- mesh out, mesh - target in place: all target requests of a batch first
+  constexpr int NL = 64 * kSlabF / 256, UL = 8;
+  static_assert(NL % UL == 0, "tile elements per thread");
+#pragma unroll
+  for (int i0 = 0; i0 < NL; i0 += UL) {
+    float t[UL];
+#pragma unroll
+    for (int i = 0; i < UL; ++i) {
+      const int e = tid + 256 * (i0 + i), inst = e / kSlabF, f = e - inst * kSlabF;
+      t[i] = (f < nf && blk * 64 + inst < B) ? ld_stream<4>(target + tile + (size_t)inst * V * 3 + f) : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < UL; ++i) {
+      const int e = tid + 256 * (i0 + i), inst = e / kSlabF, f = e - inst * kSlabF;
+      if (f < nf && blk * 64 + inst < B) {
+        const float v = smem[inst * kSlabRow + f];
+        if constexpr (WRITE_MESH) st_stream<8>(out + tile + (size_t)inst * V * 3 + f, v);
+        smem[inst * kSlabRow + f] = __fsub_rn(v, t[i]);
+      }
+    }
+  }
+  __syncthreads();
+  // ---- one distance per (instance, vertex)
+  constexpr int NE = 64 * kSlabV / 256;
+#pragma unroll
+  for (int i = 0; i < NE; ++i) {
+    const int e = tid + 256 * i, inst = e / kSlabV, vl = e - inst * kSlabV;
+    if (vl < nv && blk * 64 + inst < B) {
+      const float* d = smem + inst * kSlabRow + 3 * vl;
+      err[((size_t)blk * 64 + inst) * V + v0 + vl] = point_distance(d[0], d[1], d[2]);
+    }
+  }
+}
+
+// The distances of the mesh-error step where no tile is turned: err[i] = |a[i] - b[i]| over n points of two (n, 3)
+// arrays, one thread per point — the joints of every route, the vertices of the wave-per-instance and general routes
+// (behind their forward LBS pass).  The arithmetic of k_unlayout_error.
+__global__ __launch_bounds__(256) void k_point_error(const float* __restrict__ a, const float* __restrict__ b,
+                                                     float* __restrict__ err, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float *pa = a + i * 3, *pb = b + i * 3;
+  err[i] = point_distance(__fsub_rn(pa[0], pb[0]), __fsub_rn(pa[1], pb[1]), __fsub_rn(pa[2], pb[2]));
+}
+
 constexpr int kMeanWaves = 16;  // waves of a k_mean_finish workgroup (they share the slabs / joints / padding slots)
 __global__ __launch_bounds__(64 * kMeanWaves) void k_mean_finish(DevModel m, const float* __restrict__ tj,
                                                                  const float* __restrict__ part, Workspace ws, int B, int Mp,

@@ -1518,6 +1518,8 @@ int post_launch_check() {
 //   launch_targets_in         targets (+ weights) into the workspace, their mean, first part sums, regressed target joints
 //   launch_posed_pass         the model at the current parameters: forward joint stage, GEMM, joint-row transpose, then
 //   launch_lbs_pass           the LBS pass: part sums against the targets / the mesh alone (also to the caller: mesh out)
+//   launch_mesh_error         the model at forward inputs against the caller's targets: mesh, joints and the distance of
+//                             every vertex and joint to its target, any subset
 //   launch_normal_equations   GEMM, joint-row transpose, the vertex block of one shape solve
 //   launch_alignment          scale and translation of a known-shape fit
 //   launch_forward_backward   the forward's vector-Jacobian product (below, behind the layouts it runs in)
@@ -1696,6 +1698,46 @@ int launch_posed_pass(const smplfit_handle* h, const Route& r, const PosedPass& 
   if (int rc = launch_gemm(d, ws, B, st, r.bm)) return rc;
   if (r.bm && (p.fa || r.jd_transpose)) launch_jd_transpose(d, ws, B, st);
   return launch_lbs_pass(h, r, p.lbs, ws, B, st);
+}
+
+// STEP mesh error.  The model at forward inputs, measured against the caller's targets: any of the mesh (B, V, 3), the
+// joints (fa.joints: the caller's (B, J, 3), or ws.rjoints where they are not asked for), the distance of every vertex
+// to its target (B, V) and of every joint to its (B, J).  Unweighted; no sums, no atomics: every element has one writer.
+// r: the forward's route (Entry::kForward).  Batch-major: the forward pass leaves the mesh in ws.vpT and
+// k_unlayout_error turns it, measures it and writes it only where it is asked for — no (B, V, 3) otherwise.  The other
+// routes: the forward pass writes the mesh to the caller's or, where it is not asked for, to ws.tvs (B, 3, Vp; the
+// sorted targets of a fit, which no forward reads), and k_point_error measures it.
+struct MeshError {
+  ForwardArgs fa;                  // joints set
+  const float *tv = nullptr, *tj = nullptr;  // targets: (B,V,3), needed with verr; (B,J,3), needed with jerr
+  float *vertices = nullptr, *verr = nullptr, *jerr = nullptr;  // each may be null
+};
+int launch_mesh_error(const smplfit_handle* h, const Route& r, const MeshError& p, const Workspace& ws, int B, hipStream_t st) {
+  const DevModel& d = h->d;
+  launch_forward_joint(d, p.fa, ws, B, st);
+  if (p.jerr) {
+    const size_t n = (size_t)B * d.J;
+    hipLaunchKernelGGL(k_point_error, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p.fa.joints, p.tj, p.jerr, n);
+  }
+  if (!p.vertices && !p.verr) return 0;
+  if (r.bm && p.verr) {
+    if (int rc = launch_posed_pass(h, r, {nullptr, mesh_alone(&p.fa, nullptr)}, ws, B, st)) return rc;
+    const int Mp = (int)align_up((size_t)B, 128);
+    const dim3 grid((d.V + kSlabV - 1) / kSlabV, Mp / 64);
+    if (p.vertices)
+      hipLaunchKernelGGL(k_unlayout_error<true>, grid, dim3(256), (size_t)64 * kSlabRow * 4, st, d, ws.vpT, p.vertices, p.tv, p.verr, B);
+    else
+      hipLaunchKernelGGL(k_unlayout_error<false>, grid, dim3(256), (size_t)64 * kSlabRow * 4, st, d, ws.vpT, (float*)nullptr, p.tv,
+                         p.verr, B);
+    return 0;
+  }
+  float* mesh = p.vertices ? p.vertices : ws.tvs;
+  if (int rc = launch_posed_pass(h, r, {nullptr, mesh_alone(&p.fa, mesh)}, ws, B, st)) return rc;
+  if (p.verr) {
+    const size_t n = (size_t)B * d.V;
+    hipLaunchKernelGGL(k_point_error, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mesh, p.tv, p.verr, n);
+  }
+  return 0;
 }
 
 // STEP normal equations of one shape solve (its vertex block; the joint block comes from the joint stage, see
@@ -2543,6 +2585,32 @@ ReplaceLayout replace_layout(const sf::HostTables& t, int B, Arena& ar) {
   l.betas = ar.take<float>((size_t)B * t.num_betas());
   l.trans = ar.take<float>((size_t)B * 3);
   l.fit = ar.take<char>(chunked_workspace_bytes(t, B));
+  return l;
+}
+
+// LAYOUT fit with reconstruction: the fit's global rotations (B,J,9) and kid factors (B), which stand in for outputs
+// the caller left NULL (the mesh-error step reads them), then the fit's own workspace — its chunks, or with a plan of
+// segments that call's —, in which the step then runs as one fit workspace
+struct ReconLayout {
+  float *orient, *kid;
+  char* fit;
+  size_t fit_bytes;
+};
+// What the two entries with the mesh-error step check of its four optional outputs before anything is enqueued
+int check_recon_outputs(const char* who, const float* vertices, const float* joints, const float* verr, const float* jerr,
+                        const float* tv, const float* tj) {
+  if (!vertices && !joints && !verr && !jerr)
+    return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": at least one of vertices, joints, vertex_error, joint_error is required");
+  if (!tv) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": target_vertices is required");
+  if (jerr && !tj) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": joint_error needs target_joints");
+  return 0;
+}
+ReconLayout recon_layout(const smplfit_handle* h, int B, const smplfit_share_segments* segments, Arena& ar) {
+  ReconLayout l;
+  l.orient = ar.take<float>((size_t)B * h->t.J * 9);
+  l.kid = ar.take<float>((size_t)B);
+  l.fit_bytes = segments ? segments_workspace_bytes(h, *segments) : chunked_workspace_bytes(h->t, B);
+  l.fit = ar.take<char>(l.fit_bytes);
   return l;
 }
 
@@ -4013,6 +4081,85 @@ int smplfit_replace_hands_f32(const smplfit_replace_hands_plan* p, const smplfit
   const ForwardArgs fa = forward_args(in, d.S - d.jt.n_kid - d.jt.n_pad, trans, ws.rjoints, nullptr);
   launch_forward_joint(d, fa, ws, B, st);
   if (int rc = launch_posed_pass(h, rf, {nullptr, mesh_blended(&fa, a->out_vertices, a->vertices, p->d_mix)}, ws, B, st)) return rc;
+  return post_launch_check();
+}
+
+// ---- mesh error: the model at given parameters against the caller's targets ----------
+size_t smplfit_mesh_error_workspace_bytes(const smplfit_handle* h, int batch) { return smplfit_workspace_bytes(h, batch); }
+
+int smplfit_mesh_error_f32(const smplfit_handle* h, const smplfit_mesh_error_args* a) {
+  const char* who = "smplfit_mesh_error_f32";
+  if (!a) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
+  const int B = a->batch;
+  if (int rc = check_call(who, h, B, a->workspace, a->workspace_bytes, smplfit_mesh_error_workspace_bytes(h, B),
+                          "smplfit_mesh_error_workspace_bytes"))
+    return rc;
+  const DevModel& d = h->d;
+  const ForwardInputs in = forward_inputs(*a);
+  if (int rc = check_forward_inputs(who, d, in)) return rc;
+  if (int rc = check_recon_outputs(who, a->vertices, a->joints, a->vertex_error, a->joint_error, a->target_vertices, a->target_joints))
+    return rc;
+  hipStream_t st = (hipStream_t)a->hip_stream;
+  const Workspace ws = fit_workspace(h, B, a->workspace);
+  MeshError me;
+  me.fa = forward_args(in, forward_nb(d, in), a->trans, a->joints ? a->joints : ws.rjoints, nullptr);
+  me.tv = a->target_vertices;
+  me.tj = a->target_joints;
+  me.vertices = a->vertices;
+  me.verr = a->vertex_error;
+  me.jerr = a->joint_error;
+  if (int rc = launch_mesh_error(h, route_of(h, B, {Entry::kForward}), me, ws, B, st)) return rc;
+  return post_launch_check();
+}
+
+size_t smplfit_fit_recon_workspace_bytes(const smplfit_handle* h, int batch, const smplfit_share_segments* segments) {
+  if (!h || batch <= 0 || (segments && batch != segments->t.batch)) return 0;
+  Arena ar{nullptr};
+  recon_layout(h, batch, segments, ar);
+  return ar.off;
+}
+
+int smplfit_fit_recon_f32(const smplfit_handle* h, const smplfit_fit_args* args, const smplfit_share_segments* segments,
+                          const smplfit_fit_recon_args* recon) {
+  const char* who = "smplfit_fit_recon_f32";
+  if (!recon) return smplfit_fit_segments_f32(h, args, segments);
+  if (!args) return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": null arguments");
+  const int B = args->batch;
+  if (int rc = check_segments(who, segments, B, args->share_allreduce)) return rc;
+  if (int rc = check_call(who, h, B, args->workspace, args->workspace_bytes, smplfit_fit_recon_workspace_bytes(h, B, segments),
+                          "smplfit_fit_recon_workspace_bytes"))
+    return rc;
+  if (int rc = check_recon_outputs(who, recon->vertices, recon->joints, recon->vertex_error, recon->joint_error,
+                                   args->target_vertices, args->target_joints))
+    return rc;
+  // (which target the errors of a scaled fit refer to is undecided: refused before anything is enqueued)
+  if (args->scale_mode) return fail(SMPLFIT_ERR_UNSUPPORTED, std::string(who) + ": the scale options are not served with reconstruction");
+  Arena ar{(char*)args->workspace};
+  const ReconLayout l = recon_layout(h, B, segments, ar);
+  smplfit_fit_args f = *args;
+  if (!f.orientations) f.orientations = l.orient;
+  if (h->t.n_kid && !f.kid_factor) f.kid_factor = l.kid;
+  f.workspace = l.fit;
+  f.workspace_bytes = l.fit_bytes;
+  if (segments) f.share_beta = 1;  // segments imply shared shapes within them
+  if (int rc = fit_impl(h, &f, nullptr, false, segments)) return rc;
+  // the step at the fit's results (its chunks have been joined: one pass over the whole batch, as one fit workspace)
+  const DevModel& d = h->d;
+  hipStream_t st = (hipStream_t)args->hip_stream;
+  const Workspace ws = fit_workspace(h, B, l.fit);
+  ForwardInputs in{};
+  in.glob = f.orientations;
+  in.betas = f.shape_betas;
+  in.given = h->t.num_betas();
+  in.kid = h->t.n_kid ? f.kid_factor : nullptr;
+  MeshError me;
+  me.fa = forward_args(in, forward_nb(d, in), f.trans, recon->joints ? recon->joints : ws.rjoints, nullptr);
+  me.tv = args->target_vertices;
+  me.tj = args->target_joints;
+  me.vertices = recon->vertices;
+  me.verr = recon->vertex_error;
+  me.jerr = recon->joint_error;
+  if (int rc = launch_mesh_error(h, route_of(h, B, {Entry::kForward}), me, ws, B, st)) return rc;
   return post_launch_check();
 }
 

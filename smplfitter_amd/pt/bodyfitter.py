@@ -61,6 +61,20 @@ def _segment_sizes(segments, batch: int) -> tuple:
     return sizes
 
 
+def _recon_keys(requested_keys, target_joints, **scale_options) -> tuple:
+    """The keys of the mesh-error step among ``requested_keys`` (``vertices, joints, vertex_error, joint_error``:
+    DESIGN.md §22), checked on the host: ``joint_error`` needs target joints, and no key is served with a scale option
+    (which target the errors of a scaled fit refer to is undecided)."""
+    recon = tuple(k for k in _lib.RECON_KEYS if k in requested_keys)
+    if recon:
+        if 'joint_error' in recon and target_joints is None:
+            raise ValueError("requested_keys: 'joint_error' needs target_joints")
+        bad = [k for k, v in scale_options.items() if v]
+        if bad:
+            raise NotImplementedError(f'requested_keys {list(recon)} are not served together with {", ".join(bad)}')
+    return recon
+
+
 class BodyFitter(nn.Module):
     """Fits SMPL-family parameters (pose, shape, translation) to target vertices (and joints).
 
@@ -153,7 +167,16 @@ class BodyFitter(nn.Module):
         (and one kid factor), and its rows are bit for bit those of ``fit(rows of the run, share_beta=True)`` with the
         same options (to the bit while the batch and the run take the same cell tables — both up to 768
         rows or both above —, to rounding otherwise).  Implies ``share_beta``; not with ``share_beta_group``, gradients or
-        ``torch.compile``."""
+        ``torch.compile``.
+
+        ``requested_keys`` also understands ``'vertices'``, ``'joints'``, ``'vertex_error'`` and ``'joint_error'`` (not
+        in the reference): the model posed at the fitted parameters — the bits of ``BodyModel.forward(
+        glob_rotmats=orientations, shape_betas, trans, kid_factor)`` — and the unweighted Euclidean distance of every
+        vertex / joint to its target, from the same call (``smplfit_fit_recon_f32``): the fit's results keep their bits.
+        ``'joint_error'`` needs ``target_joints`` (``ValueError``); none of them is served with ``scale_target`` /
+        ``scale_fit`` (``NotImplementedError``).  A caller ``_workspace`` then has the size of
+        ``Handle.fit_recon_workspace_bytes``.  With gradients or under ``torch.compile`` the keys come from
+        ``BodyModel.forward`` and PyTorch arithmetic on the results."""
         if requested_keys is None:
             requested_keys = ['pose_rotvecs']
         segments = None
@@ -168,6 +191,7 @@ class BodyFitter(nn.Module):
         if scale_target and scale_fit:  # same check, same message as pt/bodyfitter.py:858-859
             raise ValueError('Only one of estim_scale_target and estim_scale_fit can be True')
         scale_mode = 1 if scale_target else 2 if scale_fit else 0
+        recon = _recon_keys(requested_keys, target_joints, scale_target=scale_target, scale_fit=scale_fit)
         if share_beta_group is not None:
             if not share_beta:
                 raise ValueError('share_beta_group needs share_beta=True')
@@ -201,6 +225,7 @@ class BodyFitter(nn.Module):
                 result = self._fit_differentiable(
                     target_vertices, target_joints, vertex_weights, joint_weights, num_iter, beta_regularizer,
                     beta_regularizer2, kid_regularizer, final_adjust_rots, unsupported=unsupported)
+            result.update(self._recon_after(recon, True, target_vertices, target_joints, result))
         elif torch.compiler.is_compiling():  # one opaque operator for torch.compile / export
             pose, betas, trans, kid, orient, rel, scale = torch.ops.smplfitter_amd.fit(
                 self.body_model._model_id, self.enable_kid, target_vertices, target_joints,
@@ -214,12 +239,13 @@ class BodyFitter(nn.Module):
                 result['kid_factor'] = kid
             if scale_mode:
                 result['scale_corr'] = scale
+            result.update(self._recon_after(recon, True, target_vertices, target_joints, result))
         else:
             result = self._fit_direct(target_vertices, target_joints, vertex_weights, joint_weights,
                                       num_iter, beta_regularizer, beta_regularizer2, kid_reg,
                                       final_adjust_rots, initial_pose_rotvecs, initial_shape_betas,
                                       initial_kid_factor, _workspace, share_beta, scale_mode,
-                                      scale_regularizer, share_beta_group, segments)
+                                      scale_regularizer, share_beta_group, segments, recon)
         # relative_orientations = parent^T @ global of the FINAL rotations (pt/bodyfitter.py:523-533);
         # returned always (the reference returns the pre-refinement ones when neither
         # 'relative_orientations' nor 'pose_rotvecs' is requested)
@@ -246,9 +272,10 @@ class BodyFitter(nn.Module):
     def _fit_direct(self, target_vertices, target_joints, vertex_weights, joint_weights, num_iter,
                     beta_regularizer, beta_regularizer2, kid_reg, final_adjust_rots,
                     initial_pose_rotvecs, initial_shape_betas, initial_kid_factor, _workspace,
-                    share_beta=False, scale_mode=0, scale_regularizer=0.0, share_beta_group=None, segments=None):
+                    share_beta=False, scale_mode=0, scale_regularizer=0.0, share_beta_group=None, segments=None, recon=()):
         """The C-ABI call behind ``fit`` (and behind the ``smplfitter_amd::fit`` operator): every result
-        tensor, ``pose_rotvecs`` included.  ``segments``: the checked sizes of ``share_beta_segments``."""
+        tensor, ``pose_rotvecs`` included.  ``segments``: the checked sizes of ``share_beta_segments``.  ``recon``: the
+        keys of the mesh-error step to return as well (``_recon_keys``): the call is then ``smplfit_fit_recon_f32``."""
         bm = self.body_model
         device = bm.v_template.device
         for t in (target_vertices, target_joints, vertex_weights, joint_weights):
@@ -279,12 +306,19 @@ class BodyFitter(nn.Module):
         rel = torch.empty((B, J, 3, 3), dtype=torch.float32, device=device)
         kid = torch.empty((B,), dtype=torch.float32, device=device) if self.enable_kid else None
         scale = torch.empty((B,), dtype=torch.float32, device=device) if scale_mode else None
+        shapes = dict(vertices=(B, V, 3), joints=(B, J, 3), vertex_error=(B, V), joint_error=(B, J))
+        extra = {k: torch.empty(shapes[k], dtype=torch.float32, device=device) for k in recon}
         if B == 0 and share_beta_group is not None:
             raise ValueError('every rank of a sharded share_beta fit needs at least one instance')
         if B > 0:
             h = bm._native(device, kid=self.enable_kid)
             plan = self._segment_plan(device, segments) if segments is not None else None
-            ws = _workspace if _workspace is not None else self._segments_workspace(h, B, device, plan)
+            if _workspace is not None:
+                ws = _workspace
+            elif recon:
+                ws = torch.empty(h.fit_recon_workspace_bytes(B, plan), dtype=torch.uint8, device=device)
+            else:
+                ws = self._segments_workspace(h, B, device, plan)
             callback, failure = _share_callback(ws, share_beta_group)
             with torch.cuda.device(device):
                 stream = torch.cuda.current_stream(device).cuda_stream
@@ -305,7 +339,12 @@ class BodyFitter(nn.Module):
                     relative_orientations=rel.data_ptr(),
                     scale_corr=scale.data_ptr() if scale is not None else None, workspace=ws.data_ptr(),
                     workspace_bytes=ws.numel(), hip_stream=stream, share_allreduce=callback)
-                rc = _lib.load().smplfit_fit_segments_f32(h.ptr, C.byref(args), plan.ptr if plan is not None else None)
+                if recon:
+                    rargs = _lib.FitReconArgs(**{k: t.data_ptr() for k, t in extra.items()})
+                    rc = _lib.load().smplfit_fit_recon_f32(h.ptr, C.byref(args), plan.ptr if plan is not None else None,
+                                                           C.byref(rargs))
+                else:
+                    rc = _lib.load().smplfit_fit_segments_f32(h.ptr, C.byref(args), plan.ptr if plan is not None else None)
                 if failure:
                     raise failure[0]
                 _lib.check(rc)
@@ -315,7 +354,21 @@ class BodyFitter(nn.Module):
             result['kid_factor'] = kid
         if scale_mode:
             result['scale_corr'] = scale
+        result.update(extra)
         return result
+
+    def _recon_after(self, recon, composed, target_vertices, target_joints, result, shape_betas=None, kid_factor=None):
+        """The keys ``recon`` of the mesh-error step at the parameters of ``result`` (``orientations, trans`` and, unless
+        given, ``shape_betas, kid_factor``), for the calls whose own native call does not return them: ``composed`` —
+        gradients, tracing — from ``BodyModel.forward`` and PyTorch arithmetic, else ``smplfit_mesh_error_f32``."""
+        if not recon:
+            return {}
+        bm = self.body_model
+        params = dict(glob_rotmats=result['orientations'], trans=result['trans'],
+                      shape_betas=result['shape_betas'] if shape_betas is None else shape_betas,
+                      kid_factor=result.get('kid_factor') if kid_factor is None else kid_factor)
+        call = bm._recon_composed if composed else bm._recon_direct
+        return call(recon, target_vertices, target_joints, **params)
 
     @staticmethod
     def _segments_workspace(h, batch, device, plan):
@@ -390,7 +443,9 @@ class BodyFitter(nn.Module):
         solve in HIP (``smplfit_shape_solve_backward_f32``); once differentiable; up to 17 shape
         unknowns; ``share_beta`` and the scale options with gradients raise ``NotImplementedError``.
         ``share_beta`` ignores the ridge references, as the reference's all-shared solve does
-        (pt/lstsq.py:45-47).  ``share_beta_group``, ``share_beta_segments``: as in :meth:`fit`."""
+        (pt/lstsq.py:45-47).  ``share_beta_group``, ``share_beta_segments``: as in :meth:`fit`; so are the
+        keys ``'vertices'``, ``'joints'``, ``'vertex_error'``, ``'joint_error'`` of ``requested_keys``, served by
+        ``smplfit_mesh_error_f32`` behind the solve (not with the scale options)."""
         if scale_target and scale_fit:  # same check, same message as pt/bodyfitter.py:858-859
             raise ValueError('Only one of estim_scale_target and estim_scale_fit can be True')
         segments = None
@@ -403,6 +458,7 @@ class BodyFitter(nn.Module):
             share_beta = True
         if share_beta_group is not None and not share_beta:
             raise ValueError('share_beta_group needs share_beta=True')
+        recon = _recon_keys(requested_keys or (), target_joints, scale_target=scale_target, scale_fit=scale_fit)
         if kid_regularizer_reference is not None and not self.enable_kid:
             kid_regularizer_reference = None  # the reference only reads it with enable_kid (:1235-1246)
         bm = self.body_model
@@ -428,7 +484,9 @@ class BodyFitter(nn.Module):
             r = dict(shape_betas=res[0], trans=res[1])
             if self.enable_kid:
                 r['kid_factor'] = res[2]
+            composed = True
         else:
+            composed = torch.compiler.is_compiling()
             G = bm(pose_rotvecs=pose, return_vertices=False)['orientations']
             r = self._shape_solve(G, target_vertices, target_joints, vertex_weights, joint_weights,
                                   beta_regularizer, beta_regularizer2, kid_regularizer=kid_reg,
@@ -446,6 +504,7 @@ class BodyFitter(nn.Module):
             out['kid_factor'] = r['kid_factor']
         if 'scale_corr' in r:
             out['scale_corr'] = r['scale_corr']
+        out.update(self._recon_after(recon, composed, target_vertices, target_joints, out))
         return out
 
     def fit_with_known_shape(
@@ -474,7 +533,10 @@ class BodyFitter(nn.Module):
         requires grad, the results carry a ``grad_fn`` whose backward is one native call
         (``smplfit_fit_known_shape_backward_f32``); once differentiable; up to 17 shape unknowns
         natively (more, and ``native_backward=False``: the PyTorch restatement); ``scale_fit`` and
-        ``initial_pose_rotvecs`` with gradients raise ``NotImplementedError``."""
+        ``initial_pose_rotvecs`` with gradients raise ``NotImplementedError``.
+
+        ``requested_keys`` understands ``'vertices'``, ``'joints'``, ``'vertex_error'``, ``'joint_error'`` as in
+        :meth:`fit`, served by ``smplfit_mesh_error_f32`` behind the fit (not with ``scale_fit``)."""
         if requested_keys is None:
             requested_keys = ['pose_rotvecs']
         bm = self.body_model
@@ -483,6 +545,8 @@ class BodyFitter(nn.Module):
                 raise TypeError(f"Expected torch.Tensor for '{name}', got numpy.ndarray.")
         if target_vertices.ndim != 3:
             raise ValueError(f'Expected batched target_vertices (B, V, 3), got {tuple(target_vertices.shape)}')
+        recon = _recon_keys(requested_keys, target_joints, scale_fit=scale_fit)
+        composed = torch.compiler.is_compiling()
         if torch.is_grad_enabled() and not torch.compiler.is_compiling() and any(
                 isinstance(t, torch.Tensor) and t.requires_grad for t in
                 (shape_betas, target_vertices, target_joints, vertex_weights, joint_weights, kid_factor, initial_pose_rotvecs)):
@@ -491,6 +555,7 @@ class BodyFitter(nn.Module):
             if bad:
                 raise NotImplementedError(f'the differentiable fit does not implement {", ".join(bad)}; detach the inputs to use the HIP path')
             n_unknowns = bm.num_betas + int(kid_factor is not None)
+            composed = True
             if self.native_backward and n_unknowns <= 17 and target_vertices.shape[0] > 0:
                 opts = (int(num_iter), bool(final_adjust_rots))
                 pose, trans, orient, rel = _KnownShapeFn.apply(self, opts, shape_betas, kid_factor, target_vertices,
@@ -508,6 +573,8 @@ class BodyFitter(nn.Module):
         else:
             out = self._fit_known_shape_direct(shape_betas, target_vertices, target_joints, vertex_weights, joint_weights,
                                                kid_factor, num_iter, final_adjust_rots, initial_pose_rotvecs, scale_fit)
+        out.update(self._recon_after(recon, composed, target_vertices, target_joints, out, shape_betas=shape_betas,
+                                     kid_factor=kid_factor))
         if 'relative_orientations' not in requested_keys and 'pose_rotvecs' not in requested_keys:
             out.pop('relative_orientations')
         if 'pose_rotvecs' not in requested_keys:

@@ -320,6 +320,46 @@ class BodyModel(nn.Module):
     def _forward_direct(self, pose_rotvecs=None, shape_betas=None, trans=None, kid_factor=None,
                         rel_rotmats=None, glob_rotmats=None, return_vertices: bool = True):
         """The C-ABI call behind ``forward`` (and behind the ``smplfitter_amd::forward`` operator)."""
+        self._check_forward_inputs(pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)
+        device = self.v_template.device
+        J, V = self.num_joints, self.num_vertices
+        batch = 0
+        for arg in (pose_rotvecs, shape_betas, trans, rel_rotmats, glob_rotmats):
+            if arg is not None:
+                batch = arg.shape[0]
+                break
+        if batch == 0:
+            res = dict(
+                joints=torch.empty((0, J, 3), device=device),
+                orientations=torch.empty((0, J, 3, 3), device=device),
+            )
+            if return_vertices:
+                res['vertices'] = torch.empty((0, V, 3), device=device)
+            return res
+        pose, glob, rel, betas, nb, tr, kid = self._prep_forward_inputs(batch, pose_rotvecs, shape_betas, trans, kid_factor,
+                                                                        rel_rotmats, glob_rotmats)
+        h = self._native(device, kid=kid is not None)
+        ws = self._workspace(h, batch, device)
+        joints = torch.empty((batch, J, 3), dtype=torch.float32, device=device)
+        orient = torch.empty((batch, J, 3, 3), dtype=torch.float32, device=device)
+        verts = torch.empty((batch, V, 3), dtype=torch.float32, device=device) if return_vertices else None
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            args = _lib.ForwardArgs(
+                pose_rotvecs=p(pose), glob_rotmats=p(glob), rel_rotmats=p(rel), shape_betas=p(betas),
+                num_betas_given=nb, trans=p(tr), kid_factor=p(kid), batch=batch, vertices=p(verts),
+                joints=p(joints), orientations=p(orient), workspace=ws.data_ptr(), workspace_bytes=ws.numel(),
+                hip_stream=stream)
+            _lib.check(_lib.load().smplfit_forward_ex_f32(h.ptr, C.byref(args)))
+        res = dict(joints=joints, orientations=orient)
+        if return_vertices:
+            res['vertices'] = verts
+        return res
+
+    @staticmethod
+    def _check_forward_inputs(pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats):
+        """The input checks of ``forward`` (and of ``mesh_error``): one rotation form, batched torch tensors."""
         n_rot = sum(x is not None for x in (pose_rotvecs, rel_rotmats, glob_rotmats))
         if n_rot > 1:
             raise ValueError(
@@ -343,21 +383,12 @@ class BodyModel(nn.Module):
                         f'{min_ndim} dimensions, but got shape {tuple(arg.shape)}. '
                         f'For single (unbatched) inputs, use model.single() instead.'
                     )
+
+    def _prep_forward_inputs(self, batch, pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats):
+        """The inputs of a forward call as contiguous fp32 tensors on the model's device: (pose, glob, rel, betas cut to
+        the model's ``num_betas``, their count, trans and kid_factor expanded to the batch)."""
         device = self.v_template.device
-        J, V = self.num_joints, self.num_vertices
-        batch = 0
-        for arg in (pose_rotvecs, shape_betas, trans, rel_rotmats, glob_rotmats):
-            if arg is not None:
-                batch = arg.shape[0]
-                break
-        if batch == 0:
-            res = dict(
-                joints=torch.empty((0, J, 3), device=device),
-                orientations=torch.empty((0, J, 3, 3), device=device),
-            )
-            if return_vertices:
-                res['vertices'] = torch.empty((0, V, 3), device=device)
-            return res
+        J = self.num_joints
         prep = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
         # rel_rotmats: the kinematic chain of pt/bodymodel.py:230-234 runs inside the joint kernel
         rel = prep(rel_rotmats.reshape(batch, J, 3, 3)) if rel_rotmats is not None else None
@@ -377,24 +408,7 @@ class BodyModel(nn.Module):
         if kid_factor is not None:
             kid = torch.as_tensor(kid_factor, dtype=torch.float32, device=device).reshape(-1)
             kid = kid.expand(batch).contiguous() if kid.numel() == 1 else kid.contiguous()
-        h = self._native(device, kid=kid is not None)
-        ws = self._workspace(h, batch, device)
-        joints = torch.empty((batch, J, 3), dtype=torch.float32, device=device)
-        orient = torch.empty((batch, J, 3, 3), dtype=torch.float32, device=device)
-        verts = torch.empty((batch, V, 3), dtype=torch.float32, device=device) if return_vertices else None
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
-            p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            args = _lib.ForwardArgs(
-                pose_rotvecs=p(pose), glob_rotmats=p(glob), rel_rotmats=p(rel), shape_betas=p(betas),
-                num_betas_given=nb, trans=p(tr), kid_factor=p(kid), batch=batch, vertices=p(verts),
-                joints=p(joints), orientations=p(orient), workspace=ws.data_ptr(), workspace_bytes=ws.numel(),
-                hip_stream=stream)
-            _lib.check(_lib.load().smplfit_forward_ex_f32(h.ptr, C.byref(args)))
-        res = dict(joints=joints, orientations=orient)
-        if return_vertices:
-            res['vertices'] = verts
-        return res
+        return pose, glob, rel, betas, nb, tr, kid
 
     def single(self, pose_rotvecs=None, shape_betas=None, trans=None, kid_factor=None,
                rel_rotmats=None, glob_rotmats=None, return_vertices: bool = True):
@@ -407,6 +421,104 @@ class BodyModel(nn.Module):
         res = self.forward(u(pose_rotvecs), u(shape_betas), u(trans), kid_factor, u(rel_rotmats),
                            u(glob_rotmats), return_vertices)
         return {k: v.squeeze(0) for k, v in res.items()}
+
+    # -- mesh error ------------------------------------------------------------------------------
+    def mesh_error(
+        self,
+        target_vertices: torch.Tensor,
+        target_joints: Optional[torch.Tensor] = None,
+        pose_rotvecs: Optional[torch.Tensor] = None,
+        shape_betas: Optional[torch.Tensor] = None,
+        trans: Optional[torch.Tensor] = None,
+        kid_factor: Optional[torch.Tensor] = None,
+        rel_rotmats: Optional[torch.Tensor] = None,
+        glob_rotmats: Optional[torch.Tensor] = None,
+        return_mesh: bool = False,
+    ) -> dict[str, torch.Tensor]:
+        """How far the model at the given parameters lies from target points (no counterpart in the reference; DESIGN.md
+        §22): ``vertex_error`` (B, V), the Euclidean distance of every vertex of ``forward(...)`` to its row of
+        ``target_vertices`` (B, V, 3); with ``target_joints`` (B, J, 3) also ``joint_error`` (B, J); with
+        ``return_mesh`` also ``vertices`` and ``joints``, the bits ``forward`` gives.  Unweighted.  One C-ABI call
+        (``smplfit_mesh_error_f32``): without ``return_mesh`` the mesh is measured where it is formed and never written
+        as (B, V, 3) on the batch-major kernels.  The parameters are those of ``forward``; an empty batch returns empty
+        tensors.  With gradients enabled and an input that requires grad, and under ``torch.compile``, the same keys
+        come from ``forward`` and PyTorch arithmetic, so they are differentiable like ``forward``."""
+        keys = ['vertex_error'] + (['joint_error'] if target_joints is not None else [])
+        if return_mesh:
+            keys += ['vertices', 'joints']
+        params = dict(pose_rotvecs=pose_rotvecs, shape_betas=shape_betas, trans=trans, kid_factor=kid_factor,
+                      rel_rotmats=rel_rotmats, glob_rotmats=glob_rotmats)
+        ins = (target_vertices, target_joints, *params.values())
+        if torch.compiler.is_compiling() or (
+                torch.is_grad_enabled() and any(isinstance(a, torch.Tensor) and a.requires_grad for a in ins)):
+            return self._recon_composed(keys, target_vertices, target_joints, **params)
+        return self._recon_direct(keys, target_vertices, target_joints, **params)
+
+    def _check_recon_targets(self, keys, target_vertices, target_joints):
+        """The target checks of the mesh-error step (no device needed); returns the batch."""
+        for name, arg in (('target_vertices', target_vertices), ('target_joints', target_joints)):
+            if isinstance(arg, np.ndarray):
+                raise TypeError(f"Expected torch.Tensor for '{name}', got numpy.ndarray.")
+        J, V = self.num_joints, self.num_vertices
+        if target_vertices.ndim != 3 or tuple(target_vertices.shape[1:]) != (V, 3):
+            raise ValueError(f'target_vertices must have shape (batch, {V}, 3), got {tuple(target_vertices.shape)}')
+        batch = target_vertices.shape[0]
+        if target_joints is not None and tuple(target_joints.shape) != (batch, J, 3):
+            raise ValueError(f'target_joints must have shape ({batch}, {J}, 3), got {tuple(target_joints.shape)}')
+        if 'joint_error' in keys and target_joints is None:
+            raise ValueError("'joint_error' needs target_joints")
+        return batch
+
+    def _recon_composed(self, keys, target_vertices, target_joints, **params):
+        """The keys of the mesh-error step from ``forward`` and PyTorch arithmetic: the route of calls that carry
+        gradients or are being traced (gradients flow through ``forward``'s backward)."""
+        self._check_recon_targets(keys, target_vertices, target_joints)
+        fw = self.forward(**params, return_vertices='vertices' in keys or 'vertex_error' in keys)
+        out = {}
+        if 'vertices' in keys:
+            out['vertices'] = fw['vertices']
+        if 'joints' in keys:
+            out['joints'] = fw['joints']
+        if 'vertex_error' in keys:
+            out['vertex_error'] = torch.linalg.vector_norm(fw['vertices'] - target_vertices.to(fw['vertices'].device), dim=-1)
+        if 'joint_error' in keys:
+            out['joint_error'] = torch.linalg.vector_norm(fw['joints'] - target_joints.to(fw['joints'].device), dim=-1)
+        return out
+
+    def _recon_direct(self, keys, target_vertices, target_joints, pose_rotvecs=None, shape_betas=None, trans=None,
+                      kid_factor=None, rel_rotmats=None, glob_rotmats=None):
+        """The C-ABI call of the mesh-error step on its own (``smplfit_mesh_error_f32``): the keys of ``keys`` (of
+        ``_lib.RECON_KEYS``) at the given forward inputs."""
+        self._check_forward_inputs(pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)
+        batch = self._check_recon_targets(keys, target_vertices, target_joints)
+        for name, arg in (('pose_rotvecs', pose_rotvecs), ('shape_betas', shape_betas), ('rel_rotmats', rel_rotmats),
+                          ('glob_rotmats', glob_rotmats)):
+            if arg is not None and arg.shape[0] != batch:
+                raise ValueError(f'{name} has {arg.shape[0]} rows, target_vertices {batch}')
+        if trans is not None and trans.shape[0] not in (1, batch):
+            raise ValueError(f'trans has {trans.shape[0]} rows, target_vertices {batch}')
+        device = self.v_template.device
+        J, V = self.num_joints, self.num_vertices
+        shapes = dict(vertices=(batch, V, 3), joints=(batch, J, 3), vertex_error=(batch, V), joint_error=(batch, J))
+        out = {k: torch.empty(shapes[k], dtype=torch.float32, device=device) for k in _lib.RECON_KEYS if k in keys}
+        if batch == 0 or not out:
+            return out
+        prep = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        pose, glob, rel, betas, nb, tr, kid = self._prep_forward_inputs(batch, pose_rotvecs, shape_betas, trans, kid_factor,
+                                                                        rel_rotmats, glob_rotmats)
+        tv, tj = prep(target_vertices), prep(target_joints)
+        h = self._native(device, kid=kid is not None)
+        ws = torch.empty(h.mesh_error_workspace_bytes(batch), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            args = _lib.MeshErrorArgs(
+                pose_rotvecs=p(pose), glob_rotmats=p(glob), rel_rotmats=p(rel), shape_betas=p(betas),
+                num_betas_given=nb, trans=p(tr), kid_factor=p(kid), batch=batch, target_vertices=p(tv),
+                target_joints=p(tj), **{k: p(out.get(k)) for k in _lib.RECON_KEYS}, workspace=ws.data_ptr(),
+                workspace_bytes=ws.numel(), hip_stream=stream)
+            _lib.check(_lib.load().smplfit_mesh_error_f32(h.ptr, C.byref(args)))
+        return out
 
     # -- rototranslate ---------------------------------------------------------------------------
     def rototranslate(
