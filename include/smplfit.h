@@ -875,6 +875,72 @@ size_t smplfit_fit_recon_workspace_bytes(const smplfit_handle* h, int batch, con
 int smplfit_fit_recon_f32(const smplfit_handle* h, const smplfit_fit_args* args, const smplfit_share_segments* plan,
                           const smplfit_fit_recon_args* recon);
 
+/* ---- robust reweighting and the reweighted fit ------------------------------------------
+ * Weights that take gross outliers out of a fit, from the per-point errors of the fit before: per row b a scale
+ * sigma_b, then w = w0 * psi(e / (tuning * sigma_b)) for the row's vertices and, with the same sigma_b, joints.
+ *   psi(u): huber min(1, 1/u); cauchy 1 / (1 + u^2); geman_mcclure 1 / (1 + u^2)^2; tukey (1 - u^2)^2 for u < 1, else
+ *   exactly 0.  fp32, IEEE division, no transcendental.
+ *   sigma_b: `scale` > 0: that value for every row; else `scale_rows` (B) if given; else max(1.4826f * med_b,
+ *   scale_floor), med_b the LOWER median — element (n - 1) / 2 of the n sorted values — of the row's vertex errors whose
+ *   prior weight is > 0 (all of them without prior weights), an exact selection; no such entry: scale_floor.
+ * Errors are magnitudes (the sign bit is ignored); prior weights w0 (NULL = 1) are meant non-negative, a prior weight
+ * of 0 gives exactly 0.  A row that holds a non-finite error, vertex or joint, gets NaN scale and NaN weights throughout
+ * (entries with a zero prior weight included); so does a row whose scale_rows entry is not positive and finite, which
+ * only the device can see.  No other row is affected.  SMPLFIT_ERR_BAD_ARG: an unknown loss, tuning <= 0, scale < 0, scale together with
+ * scale_rows, scale_floor <= 0 where the median is the source, non-finite numbers.  A refused call enqueues nothing.
+ *   smplfit_robust_weights_f32: the step on its own, one launch, no handle and no workspace: the counts are free.
+ *   joint_error NULL (or num_joint_errors 0): vertices alone.  out_scale may be NULL.  Outputs may not alias inputs.
+ *   smplfit_fit_robust_f32: round 0 is the fit of smplfit_fit_recon_f32 (args, plan).  Each of the num_rounds later
+ *   rounds runs the mesh-error step at the previous round's results (errors into the workspace, no mesh written), the
+ *   reweighting with args->vertex_weights / joint_weights as the prior weights, and the fit again with the new weights
+ *   (both kinds whenever there are target joints), warm-started from the previous round's pose_rotvecs alone, with
+ *   round_num_iter rotation passes (0: args->num_iter).  The results are those of the last round; vertex_weights /
+ *   joint_weights / scale_out receive the weights and scales that produced it (num_rounds = 0: the prior weights or
+ *   ones, and NaN scales; the fit's results are then the bits of smplfit_fit_recon_f32).  `recon` (may be NULL): the
+ *   mesh-error step once more at the final results.  A plan of segments and share_beta hold in every round; sigma stays
+ *   per row.  Refused: args->scale_mode != 0 (SMPLFIT_ERR_UNSUPPORTED), share_allreduce, initial_pose_rotvecs /
+ *   initial_shape_betas / initial_kid_factor, num_rounds < 0, round_num_iter < 0, the joint_weights output without
+ *   target_joints (SMPLFIT_ERR_BAD_ARG).  Stream-ordered: no allocation, no synchronisation.  Workspace
+ *   (args->workspace): smplfit_fit_robust_workspace_bytes(h, batch, plan); 0 for a batch that is not the plan's. */
+enum smplfit_robust_loss {
+  SMPLFIT_ROBUST_HUBER = 0,
+  SMPLFIT_ROBUST_CAUCHY = 1,
+  SMPLFIT_ROBUST_GEMAN_MCCLURE = 2,
+  SMPLFIT_ROBUST_TUKEY = 3,
+};
+typedef struct smplfit_robust_weights_args {
+  int32_t batch, num_vertex_errors, num_joint_errors;
+  const float* vertex_error;   /* (B,num_vertex_errors) */
+  const float* joint_error;    /* (B,num_joint_errors) or NULL */
+  const float* vertex_weights; /* prior (B,num_vertex_errors) or NULL */
+  const float* joint_weights;  /* prior (B,num_joint_errors) or NULL */
+  int32_t loss;                /* smplfit_robust_loss */
+  float tuning;
+  float scale;                 /* > 0: fixed sigma; 0: not given */
+  const float* scale_rows;     /* (B) or NULL */
+  float scale_floor;
+  float* out_vertex_weights;   /* out (B,num_vertex_errors) */
+  float* out_joint_weights;    /* out (B,num_joint_errors); required with joint_error */
+  float* out_scale;            /* out (B) or NULL */
+  void* hip_stream;
+} smplfit_robust_weights_args;
+int smplfit_robust_weights_f32(const smplfit_robust_weights_args* args);
+typedef struct smplfit_fit_robust_args {
+  int32_t loss;                /* smplfit_robust_loss */
+  float tuning;
+  float scale;                 /* > 0: fixed sigma; 0: not given */
+  const float* scale_rows;     /* (B) or NULL */
+  float scale_floor;
+  int32_t num_rounds;          /* reweighted rounds behind the first fit, >= 0 */
+  int32_t round_num_iter;      /* num_iter of the later rounds; 0: args->num_iter */
+  float* vertex_weights;       /* out (B,V) or NULL */
+  float* joint_weights;        /* out (B,J) or NULL; needs args->target_joints */
+  float* scale_out;            /* out (B) or NULL */
+} smplfit_fit_robust_args;
+size_t smplfit_fit_robust_workspace_bytes(const smplfit_handle* h, int batch, const smplfit_share_segments* plan);
+int smplfit_fit_robust_f32(const smplfit_handle* h, const smplfit_fit_args* args, const smplfit_share_segments* plan,
+                           const smplfit_fit_recon_args* recon, const smplfit_fit_robust_args* robust);
+
 /* Re-reads the SMPLFIT_* tuning variables (INTEGRATION.md lists them).  They are read once, at first use; tests and
  * the A/B tools that switch kernel paths inside one process call this after changing the environment.  Not to be
  * called while other threads are inside the library. */

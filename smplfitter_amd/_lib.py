@@ -63,11 +63,16 @@ EXPORTED_SYMBOLS = [
     'smplfit_shape_solve_segments_f32', 'smplfit_gemm_plane_launches', 'smplfit_stage_launches',
     'smplfit_rotation_spread_launches', 'smplfit_rototranslate_f32', 'smplfit_rototranslate_backward_f32',
     'smplfit_mesh_error_workspace_bytes', 'smplfit_mesh_error_f32', 'smplfit_fit_recon_workspace_bytes',
-    'smplfit_fit_recon_f32',
+    'smplfit_fit_recon_f32', 'smplfit_robust_weights_f32', 'smplfit_fit_robust_workspace_bytes', 'smplfit_fit_robust_f32',
 ]  # fmt: skip
 
 # the result keys of the mesh-error step (BodyFitter.fit(requested_keys=...), BodyModel.mesh_error)
 RECON_KEYS = ('vertices', 'joints', 'vertex_error', 'joint_error')
+
+# smplfit_robust_loss, and the tuning constant BodyFitter.fit_robust picks for each (an API default: the classical 95 %
+# efficiency values of Huber, Cauchy and Tukey; 3 for Geman-McClure)
+ROBUST_LOSSES = dict(huber=0, cauchy=1, geman_mcclure=2, tukey=3)
+ROBUST_TUNING = dict(huber=1.345, cauchy=2.385, geman_mcclure=3.0, tukey=4.685)
 
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -138,6 +143,26 @@ class FitReconArgs(C.Structure):
     """smplfit_fit_recon_args (include/smplfit.h)."""
     _fields_ = [('vertices', C.c_void_p), ('joints', C.c_void_p), ('vertex_error', C.c_void_p),
                 ('joint_error', C.c_void_p)]
+
+
+class RobustWeightsArgs(C.Structure):
+    """smplfit_robust_weights_args (include/smplfit.h)."""
+    _fields_ = [
+        ('batch', C.c_int32), ('num_vertex_errors', C.c_int32), ('num_joint_errors', C.c_int32),
+        ('vertex_error', C.c_void_p), ('joint_error', C.c_void_p), ('vertex_weights', C.c_void_p),
+        ('joint_weights', C.c_void_p), ('loss', C.c_int32), ('tuning', C.c_float), ('scale', C.c_float),
+        ('scale_rows', C.c_void_p), ('scale_floor', C.c_float), ('out_vertex_weights', C.c_void_p),
+        ('out_joint_weights', C.c_void_p), ('out_scale', C.c_void_p), ('hip_stream', C.c_void_p),
+    ]
+
+
+class FitRobustArgs(C.Structure):
+    """smplfit_fit_robust_args (include/smplfit.h)."""
+    _fields_ = [
+        ('loss', C.c_int32), ('tuning', C.c_float), ('scale', C.c_float), ('scale_rows', C.c_void_p),
+        ('scale_floor', C.c_float), ('num_rounds', C.c_int32), ('round_num_iter', C.c_int32),
+        ('vertex_weights', C.c_void_p), ('joint_weights', C.c_void_p), ('scale_out', C.c_void_p),
+    ]
 
 
 class ForwardBackwardArgs(C.Structure):
@@ -469,6 +494,13 @@ def load():
         lib.smplfit_fit_recon_workspace_bytes.restype = sz
         lib.smplfit_fit_recon_f32.argtypes = [vp, C.POINTER(FitArgs), vp, C.POINTER(FitReconArgs)]
         lib.smplfit_fit_recon_f32.restype = i32
+    if hasattr(lib, 'smplfit_fit_robust_f32'):  # (as above)
+        lib.smplfit_robust_weights_f32.argtypes = [C.POINTER(RobustWeightsArgs)]
+        lib.smplfit_robust_weights_f32.restype = i32
+        lib.smplfit_fit_robust_workspace_bytes.argtypes = [vp, i32, vp]
+        lib.smplfit_fit_robust_workspace_bytes.restype = sz
+        lib.smplfit_fit_robust_f32.argtypes = [vp, C.POINTER(FitArgs), vp, C.POINTER(FitReconArgs), C.POINTER(FitRobustArgs)]
+        lib.smplfit_fit_robust_f32.restype = i32
     if os.environ.get('SMPLFIT_LIB') and not hasattr(lib, 'smplfit_abi_version'):
         _lib = lib  # an older build loaded by the A/B tools (tools/ab_fit.py): no version / share-table exports
         return lib
@@ -580,6 +612,9 @@ class Handle:
 
     def fit_recon_workspace_bytes(self, batch: int, plan: 'ShareSegments | None' = None) -> int:
         return int(load().smplfit_fit_recon_workspace_bytes(self._h, int(batch), plan.ptr if plan is not None else None))
+
+    def fit_robust_workspace_bytes(self, batch: int, plan: 'ShareSegments | None' = None) -> int:
+        return int(load().smplfit_fit_robust_workspace_bytes(self._h, int(batch), plan.ptr if plan is not None else None))
 
     def forward_backward_workspace_bytes(self, batch: int) -> int:
         return int(load().smplfit_forward_backward_workspace_bytes(self._h, int(batch)))

@@ -4,6 +4,7 @@
 #pragma once
 #include <math.h>
 #include <stddef.h>
+#include <stdint.h>
 
 #if defined(__HIPCC__)
 #define SF_HD __host__ __device__ __forceinline__
@@ -617,6 +618,49 @@ SF_HD void mat2rotvec_adjoint_add(const float* r, const double* rvbar, double* r
     relbar[2] += xb; relbar[6] += xb; relbar[7] += yb; relbar[5] += yb; relbar[8] += zb; relbar[0] -= zb; relbar[4] -= zb;
     relbar[3] += wb; relbar[1] -= wb;
   }
+}
+
+// ---- robust reweighting (k_robust_reweight and its host emulation) ---------------------
+// The per-element pieces: the key of an error, the digit of a selection pass, the scale from the median and the four
+// weight functions of u = e / (tuning * scale).  All four are rational: +, *, / alone (IEEE division).
+enum RobustLoss { kRobustHuber = 0, kRobustCauchy = 1, kRobustGemanMcClure = 2, kRobustTukey = 3, kRobustLossCount = 4 };
+constexpr int kRobustPasses = 4;               // 8 bits a pass, most significant first
+constexpr uint32_t kRobustInfKey = 0x7F800000u;  // keys >= this one: inf and NaN
+
+// The magnitude's bit pattern: non-negative floats order as these unsigned integers (denormals and inf included), every
+// NaN lies above inf.  (The sign bit is dropped, so -0 has the key of 0.)
+SF_HD uint32_t robust_key(float e) {
+  uint32_t k;
+  __builtin_memcpy(&k, &e, 4);
+  return k & 0x7FFFFFFFu;
+}
+SF_HD float robust_key_value(uint32_t k) {
+  float e;
+  __builtin_memcpy(&e, &k, 4);
+  return e;
+}
+SF_HD uint32_t robust_digit(uint32_t key, int pass) { return (key >> (24 - 8 * pass)) & 0xFFu; }
+// what the passes before `pass` have fixed of a key: the selection counts the keys that agree with it there
+SF_HD uint32_t robust_prefix(uint32_t key, int pass) { return pass == 0 ? 0u : key >> (32 - 8 * pass); }
+// sigma = max(1.4826 * median, floor): the MAD-style consistency factor of the normal distribution, one fp32 product
+SF_HD float robust_scale(float median, float floor) {
+  const float s = 1.4826f * median;
+  return s > floor ? s : floor;
+}
+SF_HD float robust_huber(float u) { return u <= 1.f ? 1.f : 1.f / u; }
+SF_HD float robust_cauchy(float u) { return 1.f / (1.f + u * u); }
+SF_HD float robust_geman_mcclure(float u) {
+  const float d = 1.f + u * u;
+  return 1.f / (d * d);
+}
+SF_HD float robust_tukey(float u) {
+  if (!(u < 1.f)) return 0.f;
+  const float t = (1.f - u) * (1.f + u);  // 1 - u^2 without the cancellation next to u = 1
+  return t * t;
+}
+SF_HD float robust_weight(int loss, float u) {
+  return loss == kRobustHuber ? robust_huber(u) : loss == kRobustCauchy ? robust_cauchy(u)
+       : loss == kRobustGemanMcClure ? robust_geman_mcclure(u) : robust_tukey(u);
 }
 
 }  // namespace sf

@@ -499,6 +499,7 @@ __device__ __forceinline__ void st_stream(float* p, float v) {
 #include "kernels_bwd.inc"
 #include "kernels_adj.inc"
 #include "kernels_rigid.inc"
+#include "kernels_robust.inc"
 
 // ------------------------------------------------------------------------------------------------
 // launch helpers
@@ -2614,6 +2615,28 @@ ReconLayout recon_layout(const smplfit_handle* h, int B, const smplfit_share_seg
   return l;
 }
 
+// LAYOUT robust fit: the fit with reconstruction's (the rounds' fits and mesh-error steps run in its fit region), then
+// what a round hands to the next: the errors at the previous results (B,V) + (B,J), the weights (B,V) + (B,J) and the
+// scales (B) — each of the three only where the caller gave no output buffer for it —, and the previous round's pose
+// (B,3J), which the warm fit reads while it writes the caller's
+struct RobustLayout {
+  ReconLayout rc;
+  float *verr, *jerr, *wv, *wj, *sigma, *pose;
+};
+RobustLayout robust_layout(const smplfit_handle* h, int B, const smplfit_share_segments* segments, bool own_wv, bool own_wj,
+                           bool own_sigma, Arena& ar) {
+  RobustLayout l{};
+  l.rc = recon_layout(h, B, segments, ar);
+  const size_t BV = (size_t)B * h->t.V, BJ = (size_t)B * h->t.J;
+  l.verr = ar.take<float>(BV);
+  l.jerr = ar.take<float>(BJ);
+  if (own_wv) l.wv = ar.take<float>(BV);
+  if (own_wj) l.wj = ar.take<float>(BJ);
+  if (own_sigma) l.sigma = ar.take<float>((size_t)B);
+  l.pose = ar.take<float>(BJ * 3);
+  return l;
+}
+
 // [dfeat | dshape] = dv_posed . [posedirs | shapedirs]^T: the split-K partial products, then their sum in chunk order
 void launch_bwd_reduce(const DevModel& d, const BwdWorkspace& bw, int B, hipStream_t st) {
   const int NC = d.P + d.S, nsplit = bwd_nsplit(d.Vp);
@@ -4160,6 +4183,167 @@ int smplfit_fit_recon_f32(const smplfit_handle* h, const smplfit_fit_args* args,
   me.verr = recon->vertex_error;
   me.jerr = recon->joint_error;
   if (int rc = launch_mesh_error(h, route_of(h, B, {Entry::kForward}), me, ws, B, st)) return rc;
+  return post_launch_check();
+}
+
+// ---- robust reweighting and the reweighted fit ----------------------------------------
+// What both entries check of the loss and the scale source before anything is enqueued
+int check_robust_options(const char* who, int loss, float tuning, float scale, const float* scale_rows, float scale_floor) {
+  const auto bad = [who](const char* what) { return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  if (loss < 0 || loss >= sf::kRobustLossCount) return bad("unknown loss (0 huber, 1 cauchy, 2 geman_mcclure, 3 tukey)");
+  if (!(tuning > 0.f) || !std::isfinite(tuning)) return bad("tuning must be positive and finite");
+  if (!(scale >= 0.f) || !std::isfinite(scale)) return bad("scale must be positive and finite, or 0 for none");
+  if (scale > 0.f && scale_rows) return bad("scale and scale_rows cannot both be given");
+  if (!(scale > 0.f) && !scale_rows && (!(scale_floor > 0.f) || !std::isfinite(scale_floor)))
+    return bad("scale_floor must be positive and finite where the scale comes from the median");
+  return 0;
+}
+
+// STEP reweight: sigma and the weights of every row from its errors, one launch
+void launch_robust_reweight(const RobustArgs& a, int B, hipStream_t st) {
+  const bool median = !(a.scale > 0.f) && !a.scale_rows;
+  const size_t lds = (median && (size_t)a.nv * 4 <= kRobustStageBytes) ? (size_t)a.nv * 4 : 0;
+  hipLaunchKernelGGL(k_robust_reweight, dim3(B), dim3(kRobustThreads), lds, st, a, lds ? 1 : 0);
+}
+void launch_robust_prior(const float* src, float value, float* dst, size_t n, hipStream_t st) {
+  if (dst && n) hipLaunchKernelGGL(k_robust_prior, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, value, dst, n);
+}
+
+int smplfit_robust_weights_f32(const smplfit_robust_weights_args* a) {
+  const char* who = "smplfit_robust_weights_f32";
+  const auto bad = [who](const char* what) { return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  if (!a) return bad("null arguments");
+  if (a->batch <= 0) return bad("batch must be positive");
+  if (a->num_vertex_errors < 1 || a->num_vertex_errors > (1 << 30)) return bad("num_vertex_errors must lie in [1, 2^30]");
+  if (a->num_joint_errors < 0 || a->num_joint_errors > (1 << 30)) return bad("num_joint_errors must lie in [0, 2^30]");
+  if (!a->vertex_error || !a->out_vertex_weights) return bad("vertex_error and out_vertex_weights are required");
+  const bool joints = a->num_joint_errors > 0 && a->joint_error;
+  if (a->joint_error && !a->num_joint_errors) return bad("joint_error given with num_joint_errors = 0");
+  if (joints && !a->out_joint_weights) return bad("joint_error needs out_joint_weights");
+  if (!joints && (a->joint_weights || a->out_joint_weights)) return bad("joint weights need joint_error");
+  if (int rc = check_robust_options(who, a->loss, a->tuning, a->scale, a->scale_rows, a->scale_floor)) return rc;
+  RobustArgs r{};
+  r.ev = a->vertex_error;
+  r.ej = joints ? a->joint_error : nullptr;
+  r.w0v = a->vertex_weights;
+  r.w0j = a->joint_weights;
+  r.wv = a->out_vertex_weights;
+  r.wj = a->out_joint_weights;
+  r.sigma = a->out_scale;
+  r.scale_rows = a->scale_rows;
+  r.nv = a->num_vertex_errors;
+  r.nj = joints ? a->num_joint_errors : 0;
+  r.loss = a->loss;
+  r.tuning = a->tuning;
+  r.scale = a->scale;
+  r.floor = a->scale_floor;
+  launch_robust_reweight(r, a->batch, (hipStream_t)a->hip_stream);
+  return post_launch_check();
+}
+
+size_t smplfit_fit_robust_workspace_bytes(const smplfit_handle* h, int batch, const smplfit_share_segments* segments) {
+  if (!h || batch <= 0 || (segments && batch != segments->t.batch)) return 0;
+  Arena ar{nullptr};
+  robust_layout(h, batch, segments, true, true, true, ar);
+  return ar.off;
+}
+
+int smplfit_fit_robust_f32(const smplfit_handle* h, const smplfit_fit_args* args, const smplfit_share_segments* segments,
+                           const smplfit_fit_recon_args* recon, const smplfit_fit_robust_args* robust) {
+  const char* who = "smplfit_fit_robust_f32";
+  const auto bad = [who](const char* what) { return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  if (!args || !robust) return bad("null arguments");
+  const int B = args->batch;
+  if (int rc = check_segments(who, segments, B, args->share_allreduce)) return rc;
+  if (int rc = check_call(who, h, B, args->workspace, args->workspace_bytes, smplfit_fit_robust_workspace_bytes(h, B, segments),
+                          "smplfit_fit_robust_workspace_bytes"))
+    return rc;
+  if (!args->target_vertices) return bad("target_vertices is required");
+  if (recon)
+    if (int rc = check_recon_outputs(who, recon->vertices, recon->joints, recon->vertex_error, recon->joint_error,
+                                     args->target_vertices, args->target_joints))
+      return rc;
+  // (the errors of a scaled fit refer to an undecided target, as with reconstruction: refused before anything is enqueued)
+  if (args->scale_mode) return fail(SMPLFIT_ERR_UNSUPPORTED, std::string(who) + ": the scale options are not served with robust rounds");
+  if (args->share_allreduce) return bad("share_allreduce cannot be combined with robust rounds");
+  if (args->initial_pose_rotvecs || args->initial_shape_betas || args->initial_kid_factor)
+    return bad("warm starts are not served: every round after the first starts from the previous round's pose");
+  if (int rc = check_robust_options(who, robust->loss, robust->tuning, robust->scale, robust->scale_rows, robust->scale_floor))
+    return rc;
+  if (robust->num_rounds < 0) return bad("num_rounds must be >= 0");
+  if (robust->round_num_iter < 0) return bad("round_num_iter must be >= 1, or 0 for num_iter");
+  const bool joints = args->target_joints != nullptr;
+  if (!joints && robust->joint_weights) return bad("the joint_weights output needs target_joints");
+  const sf::HostTables& t = h->t;
+  hipStream_t st = (hipStream_t)args->hip_stream;
+  Arena ar{(char*)args->workspace};
+  const RobustLayout l = robust_layout(h, B, segments, !robust->vertex_weights, !robust->joint_weights, !robust->scale_out, ar);
+  float* wv = robust->vertex_weights ? robust->vertex_weights : l.wv;
+  float* wj = !joints ? nullptr : robust->joint_weights ? robust->joint_weights : l.wj;
+  float* sigma = robust->scale_out ? robust->scale_out : l.sigma;
+
+  // round 0: the fit as smplfit_fit_recon_f32 runs it
+  smplfit_fit_args f = *args;
+  if (!f.orientations) f.orientations = l.rc.orient;
+  if (t.n_kid && !f.kid_factor) f.kid_factor = l.rc.kid;
+  f.workspace = l.rc.fit;
+  f.workspace_bytes = l.rc.fit_bytes;
+  if (segments) f.share_beta = 1;  // segments imply shared shapes within them
+  if (int rc = fit_impl(h, &f, nullptr, false, segments)) return rc;
+
+  // the mesh-error step at the current results (the fit's chunks have been joined: one pass, as one fit workspace)
+  const DevModel& d = h->d;
+  const auto mesh_error = [&](float* vertices, float* joints_out, float* verr, float* jerr) {
+    const Workspace ws = fit_workspace(h, B, l.rc.fit);
+    ForwardInputs in{};
+    in.glob = f.orientations;
+    in.betas = f.shape_betas;
+    in.given = t.num_betas();
+    in.kid = t.n_kid ? f.kid_factor : nullptr;
+    MeshError me;
+    me.fa = forward_args(in, forward_nb(d, in), f.trans, joints_out ? joints_out : ws.rjoints, nullptr);
+    me.tv = args->target_vertices;
+    me.tj = args->target_joints;
+    me.vertices = vertices;
+    me.verr = verr;
+    me.jerr = jerr;
+    return launch_mesh_error(h, route_of(h, B, {Entry::kForward}), me, ws, B, st);
+  };
+
+  // every later round: errors at the previous results, weights from them, the fit again from the previous pose
+  smplfit_fit_args g = f;
+  g.vertex_weights = wv;
+  g.joint_weights = wj;
+  g.initial_pose_rotvecs = l.pose;
+  if (robust->round_num_iter) g.num_iter = robust->round_num_iter;
+  RobustArgs r{};
+  r.ev = l.verr;
+  r.ej = joints ? l.jerr : nullptr;
+  r.w0v = args->vertex_weights;
+  r.w0j = joints ? args->joint_weights : nullptr;
+  r.wv = wv;
+  r.wj = wj;
+  r.sigma = sigma;
+  r.scale_rows = robust->scale_rows;
+  r.nv = t.V;
+  r.nj = joints ? t.J : 0;
+  r.loss = robust->loss;
+  r.tuning = robust->tuning;
+  r.scale = robust->scale;
+  r.floor = robust->scale_floor;
+  for (int round = 1; round <= robust->num_rounds; ++round) {
+    if (int rc = mesh_error(nullptr, nullptr, l.verr, joints ? l.jerr : nullptr)) return rc;
+    launch_robust_reweight(r, B, st);
+    SF_HIP_TRY(hipMemcpyAsync(l.pose, f.pose_rotvecs, (size_t)B * t.J * 3 * 4, hipMemcpyDeviceToDevice, st));
+    if (int rc = fit_impl(h, &g, nullptr, false, segments)) return rc;
+  }
+  if (robust->num_rounds == 0) {  // no round: the prior weights (or ones), and no scale was formed
+    launch_robust_prior(args->vertex_weights, 1.f, robust->vertex_weights, (size_t)B * t.V, st);
+    if (joints) launch_robust_prior(args->joint_weights, 1.f, robust->joint_weights, (size_t)B * t.J, st);
+    launch_robust_prior(nullptr, __builtin_nanf(""), robust->scale_out, (size_t)B, st);
+  }
+  if (recon)
+    if (int rc = mesh_error(recon->vertices, recon->joints, recon->vertex_error, recon->joint_error)) return rc;
   return post_launch_check();
 }
 

@@ -357,6 +357,206 @@ class BodyFitter(nn.Module):
         result.update(extra)
         return result
 
+    @staticmethod
+    def _robust_options(loss, tuning, scale, scale_floor, batch):
+        """``loss, tuning, scale, scale_floor`` of :meth:`fit_robust` / :meth:`_robust_weights`, checked on the host:
+        ``(loss id, tuning, fixed scale or 0, (B,) scale tensor or None, scale_floor)``."""
+        if loss not in _lib.ROBUST_LOSSES:
+            raise ValueError(f'loss must be one of {list(_lib.ROBUST_LOSSES)}, got {loss!r}')
+        tuning = float(_lib.ROBUST_TUNING[loss] if tuning is None else tuning)
+        if not (tuning > 0 and np.isfinite(tuning)):
+            raise ValueError(f'tuning must be positive and finite, got {tuning}')
+        scale_floor = float(scale_floor)
+        fixed, rows = 0.0, None
+        if isinstance(scale, torch.Tensor) and scale.ndim > 0:
+            if tuple(scale.shape) != (batch,) or not scale.is_floating_point():
+                raise ValueError(f'scale must be None, a positive number or a floating-point tensor of shape ({batch},), '
+                                 f'got shape {tuple(scale.shape)}')
+            rows = scale
+        elif scale is not None:
+            fixed = float(scale)
+            if not (fixed > 0 and np.isfinite(fixed)):
+                raise ValueError(f'scale must be positive and finite, got {fixed}')
+        elif not (scale_floor > 0 and np.isfinite(scale_floor)):
+            raise ValueError(f'scale_floor must be positive and finite, got {scale_floor}')
+        return _lib.ROBUST_LOSSES[loss], tuning, fixed, rows, scale_floor
+
+    def _robust_weights(self, vertex_error, joint_error=None, vertex_weights=None, joint_weights=None, *,
+                        loss='geman_mcclure', tuning=None, scale=None, scale_floor=1e-3, _out=None):
+        """The reweighting step alone (``smplfit_robust_weights_f32``): from errors ``(B, N_v)`` and
+        optionally ``(B, N_j)`` — any counts, not the model's — and optional prior weights of the same shapes,
+        ``robust_scale`` (B,), ``robust_vertex_weights`` and, with joint errors, ``robust_joint_weights``; the options
+        are those of :meth:`fit_robust`.  ``_out``: a dict of preallocated contiguous fp32 result tensors by those
+        keys."""
+        if vertex_error.ndim != 2 or vertex_error.shape[1] < 1:
+            raise ValueError(f'vertex_error must have shape (batch, N >= 1), got {tuple(vertex_error.shape)}')
+        B, Nv = vertex_error.shape
+        if joint_error is not None and (joint_error.ndim != 2 or joint_error.shape[0] != B or joint_error.shape[1] < 1):
+            raise ValueError(f'joint_error must have shape ({B}, N >= 1), got {tuple(joint_error.shape)}')
+        Nj = 0 if joint_error is None else joint_error.shape[1]
+        if vertex_weights is not None and tuple(vertex_weights.shape) != (B, Nv):
+            raise ValueError(f'vertex_weights must have shape ({B}, {Nv})')
+        if joint_weights is not None and (joint_error is None or tuple(joint_weights.shape) != (B, Nj)):
+            raise ValueError(f'joint_weights need joint_error and the shape ({B}, {Nj})')
+        loss_id, tuning, fixed, rows, scale_floor = self._robust_options(loss, tuning, scale, scale_floor, B)
+        device = vertex_error.device if vertex_error.device.type == 'cuda' else self.body_model.v_template.device
+        if device.type != 'cuda':
+            raise RuntimeError("smplfitter_amd runs on MI355X only: move the model or the errors to a 'cuda' (ROCm) device")
+        prep = lambda t: None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        ev, ej, w0v, w0j, rows = prep(vertex_error), prep(joint_error), prep(vertex_weights), prep(joint_weights), prep(rows)
+        out = dict(_out or {})
+        shapes = dict(robust_vertex_weights=(B, Nv), robust_scale=(B,))
+        if ej is not None:
+            shapes['robust_joint_weights'] = (B, Nj)
+        for k, sh in shapes.items():
+            t = out.get(k)
+            if t is None:
+                out[k] = torch.empty(sh, dtype=torch.float32, device=device)
+            elif tuple(t.shape) != sh or t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
+                raise ValueError(f'_out[{k!r}] must be a contiguous float32 tensor of shape {sh} on {device}')
+        out = {k: out[k] for k in shapes}
+        if B > 0:
+            p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            with torch.cuda.device(device):
+                args = _lib.RobustWeightsArgs(
+                    batch=B, num_vertex_errors=Nv, num_joint_errors=Nj, vertex_error=p(ev), joint_error=p(ej),
+                    vertex_weights=p(w0v), joint_weights=p(w0j), loss=loss_id, tuning=tuning, scale=fixed,
+                    scale_rows=p(rows), scale_floor=scale_floor, out_vertex_weights=p(out['robust_vertex_weights']),
+                    out_joint_weights=p(out.get('robust_joint_weights')), out_scale=p(out['robust_scale']),
+                    hip_stream=torch.cuda.current_stream(device).cuda_stream)
+                _lib.check(_lib.load().smplfit_robust_weights_f32(C.byref(args)))
+        return out
+
+    def fit_robust(
+        self,
+        target_vertices: torch.Tensor,
+        target_joints: Optional[torch.Tensor] = None,
+        vertex_weights: Optional[torch.Tensor] = None,
+        joint_weights: Optional[torch.Tensor] = None,
+        *,
+        loss: str = 'geman_mcclure',
+        tuning: Optional[float] = None,
+        scale=None,
+        scale_floor: float = 1e-3,
+        num_rounds: int = 2,
+        num_iter: int = 1,
+        round_num_iter: Optional[int] = None,
+        beta_regularizer: float = 1,
+        beta_regularizer2: float = 0,
+        kid_regularizer: Optional[float] = None,
+        share_beta: bool = False,
+        final_adjust_rots: bool = True,
+        scale_target: bool = False,
+        scale_fit: bool = False,
+        requested_keys: Optional[list[str]] = None,
+        _workspace: Optional[torch.Tensor] = None,
+        share_beta_group=None,
+        share_beta_segments=None,
+    ) -> dict[str, torch.Tensor]:
+        """:meth:`fit` for targets with gross outliers (not in the reference): the fit, then
+        ``num_rounds`` times the per-point errors at its results, weights from them, and the fit again with those
+        weights from the previous pose — one native call (``smplfit_fit_robust_f32``), nothing between the fits but one
+        mesh-error pass and one reweighting launch.
+
+        Per row ``b`` the weights are ``w0 * psi(e / (tuning * sigma_b))`` with the prior weights ``w0`` given here
+        (``vertex_weights, joint_weights``; none: 1) and ``psi`` of ``loss``: ``'huber'`` min(1, 1/u), ``'cauchy'``
+        1/(1+u²), ``'geman_mcclure'`` 1/(1+u²)², ``'tukey'`` (1-u²)² below 1 and exactly 0 from 1 on.  ``tuning=None``
+        picks 1.345 / 2.385 / 3.0 / 4.685 (API defaults).  ``scale``: ``None`` — ``sigma_b = max(1.4826 * lower median of
+        the row's vertex errors with a positive prior weight, scale_floor)``, found on the device —, a positive number
+        for all rows, or a ``(B,)`` tensor.  The joints are weighted with the same ``sigma_b``.  ``round_num_iter``:
+        ``num_iter`` of the later rounds (``None``: ``num_iter``).  A row with a non-finite error, or with an entry of a
+        ``(B,)`` ``scale`` that is not positive and finite (the tensor is read on the device alone), gets NaN scale and
+        weights throughout, and with them a non-finite fit; other rows are not affected.
+
+        Returns ``fit``'s keys (``requested_keys`` as there, the four reconstruction keys included: measured at the last
+        round's results) plus ``robust_vertex_weights`` (B, V), ``robust_joint_weights`` (B, J) with target joints and
+        ``robust_scale`` (B,): the weights and scales that produced the last round.  ``num_rounds=0`` returns the bits
+        of ``fit``, the prior weights (or ones) and NaN scales.  The rounds have the bits of the same loop written with
+        ``fit(requested_keys=[errors])``, :meth:`_robust_weights` and a warm ``fit``.
+
+        ``ValueError``: wrong shapes, an unknown loss, bad numbers.  ``NotImplementedError``: ``scale_target`` /
+        ``scale_fit``, ``share_beta_group``, inputs that require grad, ``torch.compile``.  A caller ``_workspace`` has
+        the size of ``Handle.fit_robust_workspace_bytes``."""
+        if requested_keys is None:
+            requested_keys = ['pose_rotvecs']
+        bm = self.body_model
+        J, V, S = bm.num_joints, bm.num_vertices, self.n_betas
+        if target_vertices.ndim != 3 or tuple(target_vertices.shape[1:]) != (V, 3):
+            raise ValueError(f'target_vertices must have shape (batch, {V}, 3), got {tuple(target_vertices.shape)}')
+        B = target_vertices.shape[0]
+        if target_joints is not None and tuple(target_joints.shape) != (B, J, 3):
+            raise ValueError(f'target_joints must have shape ({B}, {J}, 3), got {tuple(target_joints.shape)}')
+        if vertex_weights is not None and tuple(vertex_weights.shape) != (B, V):
+            raise ValueError(f'vertex_weights must have shape ({B}, {V})')
+        if joint_weights is not None and tuple(joint_weights.shape) != (B, J):
+            raise ValueError(f'joint_weights must have shape ({B}, {J})')
+        loss_id, tuning, fixed, rows, scale_floor = self._robust_options(loss, tuning, scale, scale_floor, B)
+        num_rounds, num_iter = int(num_rounds), int(num_iter)
+        round_num_iter = num_iter if round_num_iter is None else int(round_num_iter)
+        if num_rounds < 0:
+            raise ValueError(f'num_rounds must be >= 0, got {num_rounds}')
+        if num_iter < 1 or round_num_iter < 1:
+            raise ValueError(f'num_iter and round_num_iter must be >= 1, got {num_iter} and {round_num_iter}')
+        segments = None
+        if share_beta_segments is not None:
+            if share_beta_group is not None:
+                raise ValueError('share_beta_segments cannot be combined with share_beta_group')
+            segments = _segment_sizes(share_beta_segments, B)
+            share_beta = True
+        if scale_target or scale_fit:
+            raise NotImplementedError('fit_robust does not serve scale_target / scale_fit (which target the errors of a '
+                                      'scaled fit refer to is undecided)')
+        if share_beta_group is not None:
+            raise NotImplementedError('fit_robust does not serve share_beta_group (a sharded share_beta fit)')
+        if torch.compiler.is_compiling():
+            raise NotImplementedError('fit_robust cannot be traced; call it outside the compiled region')
+        if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in
+                                          (target_vertices, target_joints, vertex_weights, joint_weights, rows)):
+            raise NotImplementedError('fit_robust is not differentiable; detach the inputs')
+        recon = _recon_keys(requested_keys, target_joints)
+        kid_reg = float(beta_regularizer if kid_regularizer is None else kid_regularizer)
+
+        device = bm.v_template.device
+        prep = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        tv, tj, vw, jw, rows = prep(target_vertices), prep(target_joints), prep(vertex_weights), prep(joint_weights), prep(rows)
+        new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=device)  # noqa: E731
+        result = dict(pose_rotvecs=new(B, 3 * J), shape_betas=new(B, S), trans=new(B, 3), orientations=new(B, J, 3, 3),
+                      relative_orientations=new(B, J, 3, 3))
+        if self.enable_kid:
+            result['kid_factor'] = new(B)
+        shapes = dict(vertices=(B, V, 3), joints=(B, J, 3), vertex_error=(B, V), joint_error=(B, J))
+        extra = {k: new(*shapes[k]) for k in recon}
+        robust = dict(robust_vertex_weights=new(B, V), robust_scale=new(B))
+        if tj is not None:
+            robust['robust_joint_weights'] = new(B, J)
+        if B > 0:
+            h = bm._native(device, kid=self.enable_kid)
+            plan = self._segment_plan(device, segments) if segments is not None else None
+            ws = _workspace if _workspace is not None else torch.empty(h.fit_robust_workspace_bytes(B, plan), dtype=torch.uint8,
+                                                                       device=device)
+            p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            with torch.cuda.device(device):
+                args = _lib.FitArgs(
+                    target_vertices=p(tv), target_joints=p(tj), vertex_weights=p(vw), joint_weights=p(jw), batch=B,
+                    num_iter=num_iter, beta_regularizer=float(beta_regularizer), beta_regularizer2=float(beta_regularizer2),
+                    kid_regularizer=kid_reg, final_adjust_rots=int(bool(final_adjust_rots)), share_beta=int(bool(share_beta)),
+                    pose_rotvecs=p(result['pose_rotvecs']), shape_betas=p(result['shape_betas']), trans=p(result['trans']),
+                    kid_factor=p(result.get('kid_factor')), orientations=p(result['orientations']),
+                    relative_orientations=p(result['relative_orientations']), workspace=ws.data_ptr(),
+                    workspace_bytes=ws.numel(), hip_stream=torch.cuda.current_stream(device).cuda_stream)
+                rargs = _lib.FitReconArgs(**{k: t.data_ptr() for k, t in extra.items()}) if recon else None
+                bargs = _lib.FitRobustArgs(
+                    loss=loss_id, tuning=tuning, scale=fixed, scale_rows=p(rows), scale_floor=scale_floor,
+                    num_rounds=num_rounds, round_num_iter=round_num_iter, vertex_weights=p(robust['robust_vertex_weights']),
+                    joint_weights=p(robust.get('robust_joint_weights')), scale_out=p(robust['robust_scale']))
+                _lib.check(_lib.load().smplfit_fit_robust_f32(h.ptr, C.byref(args), plan.ptr if plan is not None else None,
+                                                              C.byref(rargs) if rargs is not None else None, C.byref(bargs)))
+        result.update(extra)
+        result.update(robust)
+        if 'pose_rotvecs' not in requested_keys:
+            result.pop('pose_rotvecs', None)
+        return result
+
     def _recon_after(self, recon, composed, target_vertices, target_joints, result, shape_betas=None, kid_factor=None):
         """The keys ``recon`` of the mesh-error step at the parameters of ``result`` (``orientations, trans`` and, unless
         given, ``shape_betas, kid_factor``), for the calls whose own native call does not return them: ``composed`` —
