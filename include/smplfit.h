@@ -875,6 +875,81 @@ size_t smplfit_fit_recon_workspace_bytes(const smplfit_handle* h, int batch, con
 int smplfit_fit_recon_f32(const smplfit_handle* h, const smplfit_fit_args* args, const smplfit_share_segments* plan,
                           const smplfit_fit_recon_args* recon);
 
+/* ---- aligned errors: the model moved onto the targets before it is measured -------------
+ * Per row: model points x_n, target points y_n, weights w_n >= 0 (NULL = 1), W = sum w_n, weighted means xbar, ybar,
+ * K = sum w_n (y_n - ybar)(x_n - xbar)^T.  The error of a point is |s R x_n + t - y_n|, unweighted, with
+ *   none          s = 1, R = I, t = 0                     (the bits of smplfit_mesh_error_f32)
+ *   root          s = 1, R = I, t = y_root - x_root       (joint 0; needs target_joints; both sets get it)
+ *   translation   s = 1, R = I, t = ybar - xbar
+ *   rigid         s = 1, R = proj_SO3(K) (det +1 also where the best orthogonal fit is a reflection), t = ybar - R xbar
+ *   similarity    s = tr(R^T K) / sum w_n |x_n - xbar|^2, R as rigid, t = ybar - s R xbar
+ * align_on: each (the vertices are aligned on the vertices, the joints on the joints: PA-PVE and PA-MPJPE), vertices
+ * or joints (one transform from that set for both).  The row means are sum w_n e_n / W over a set, accumulated in fp64
+ * in a fixed order and rounded once.  A row whose W is 0, whose spread is 0 under similarity, or that holds a
+ * non-finite point or a negative or non-finite weight in the set that gives a transform gets NaN errors, means and
+ * transform under that transform; no other row is affected (with root the set is the joints; the weights of a set
+ * always enter its own mean).  The model moves, the target stays.  Two runs give the same bits: no float atomics.
+ *   smplfit_mesh_error_aligned_f32: smplfit_mesh_error_f32 with an alignment.  A NULL `align` makes it that call.
+ *   Outputs: the four of the argument struct, the two means and the transforms: scale / rotation / translation the
+ *   vertices' (with align_on = joints, and with root, the joints'), joint_* the joints' own with align_on = each.
+ *   `vertices` keeps the forward's bits, unaligned.  SMPLFIT_ERR_BAD_ARG, before anything is enqueued and with the
+ *   outputs untouched: an unknown align or align_on; root, align_on = joints or any joint output or joint_weights
+ *   without target_joints; no output at all; a transform output with none; joint_* without align_on = each.  With
+ *   an alignment the mesh is written as (B,V,3), to `vertices` or into the workspace, on every kernel route.
+ *   Stream-ordered: no allocation, no synchronisation.  Workspace: smplfit_mesh_error_aligned_workspace_bytes(h, batch),
+ *   the most any call takes; its last three regions, B*V*12, B*V*4 and B*J*4 bytes (each rounded up to 256), stand
+ *   in for `vertices`, `vertex_error` and `joint_error`, and a call that is given one of these buffers may leave that
+ *   region off.
+ *   smplfit_align_points_f32: the step on two arbitrary (B,N,3) arrays, no handle: translation, rigid or similarity.
+ *   Workspace: smplfit_align_points_workspace_bytes(batch, num_points); 0 for a batch < 1,
+ *   num_points outside [1, 2^26] or batch * num_points above 2^38, which the call refuses (SMPLFIT_ERR_BAD_ARG). */
+enum smplfit_align_mode {
+  SMPLFIT_ALIGN_NONE = 0,
+  SMPLFIT_ALIGN_ROOT = 1,
+  SMPLFIT_ALIGN_TRANSLATION = 2,
+  SMPLFIT_ALIGN_RIGID = 3,
+  SMPLFIT_ALIGN_SIMILARITY = 4,
+};
+enum smplfit_align_on {
+  SMPLFIT_ALIGN_ON_EACH = 0,
+  SMPLFIT_ALIGN_ON_VERTICES = 1,
+  SMPLFIT_ALIGN_ON_JOINTS = 2,
+};
+typedef struct smplfit_mesh_align_args {
+  int32_t align;               /* smplfit_align_mode */
+  int32_t align_on;            /* smplfit_align_on */
+  const float* vertex_weights; /* (B,V) or NULL */
+  const float* joint_weights;  /* (B,J) or NULL */
+  float* mean_vertex_error;    /* out (B) or NULL */
+  float* mean_joint_error;     /* out (B) or NULL */
+  float* scale;                /* out (B) or NULL */
+  float* rotation;             /* out (B,3,3) or NULL */
+  float* translation;          /* out (B,3) or NULL */
+  float* joint_scale;          /* out (B) or NULL */
+  float* joint_rotation;       /* out (B,3,3) or NULL */
+  float* joint_translation;    /* out (B,3) or NULL */
+} smplfit_mesh_align_args;
+size_t smplfit_mesh_error_aligned_workspace_bytes(const smplfit_handle* h, int batch);
+int smplfit_mesh_error_aligned_f32(const smplfit_handle* h, const smplfit_mesh_error_args* args,
+                                   const smplfit_mesh_align_args* align);
+typedef struct smplfit_align_points_args {
+  int32_t batch, num_points;
+  const float* source;         /* (B,N,3): the points that move */
+  const float* target;         /* (B,N,3) */
+  const float* weights;        /* (B,N) or NULL */
+  int32_t align;               /* smplfit_align_mode: translation, rigid or similarity */
+  float* error;                /* out (B,N) or NULL */
+  float* mean_error;           /* out (B) or NULL */
+  float* scale;                /* out (B) or NULL */
+  float* rotation;             /* out (B,3,3) or NULL */
+  float* translation;          /* out (B,3) or NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  void* hip_stream;
+} smplfit_align_points_args;
+size_t smplfit_align_points_workspace_bytes(int batch, int num_points);
+int smplfit_align_points_f32(const smplfit_align_points_args* args);
+
 /* ---- robust reweighting and the reweighted fit ------------------------------------------
  * Weights that take gross outliers out of a fit, from the per-point errors of the fit before: per row b a scale
  * sigma_b, then w = w0 * psi(e / (tuning * sigma_b)) for the row's vertices and, with the same sigma_b, joints.

@@ -64,6 +64,8 @@ EXPORTED_SYMBOLS = [
     'smplfit_rotation_spread_launches', 'smplfit_rototranslate_f32', 'smplfit_rototranslate_backward_f32',
     'smplfit_mesh_error_workspace_bytes', 'smplfit_mesh_error_f32', 'smplfit_fit_recon_workspace_bytes',
     'smplfit_fit_recon_f32', 'smplfit_robust_weights_f32', 'smplfit_fit_robust_workspace_bytes', 'smplfit_fit_robust_f32',
+    'smplfit_mesh_error_aligned_workspace_bytes', 'smplfit_mesh_error_aligned_f32',
+    'smplfit_align_points_workspace_bytes', 'smplfit_align_points_f32',
 ]  # fmt: skip
 
 # the result keys of the mesh-error step (BodyFitter.fit(requested_keys=...), BodyModel.mesh_error)
@@ -73,6 +75,10 @@ RECON_KEYS = ('vertices', 'joints', 'vertex_error', 'joint_error')
 # efficiency values of Huber, Cauchy and Tukey; 3 for Geman-McClure)
 ROBUST_LOSSES = dict(huber=0, cauchy=1, geman_mcclure=2, tukey=3)
 ROBUST_TUNING = dict(huber=1.345, cauchy=2.385, geman_mcclure=3.0, tukey=4.685)
+
+# smplfit_align_mode / smplfit_align_on (aligned errors)
+ALIGN_MODES = dict(none=0, root=1, translation=2, rigid=3, similarity=4)
+ALIGN_ON = dict(each=0, vertices=1, joints=2)
 
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
@@ -135,6 +141,26 @@ class MeshErrorArgs(C.Structure):
         ('kid_factor', C.c_void_p), ('batch', C.c_int32), ('target_vertices', C.c_void_p),
         ('target_joints', C.c_void_p), ('vertices', C.c_void_p), ('joints', C.c_void_p),
         ('vertex_error', C.c_void_p), ('joint_error', C.c_void_p), ('workspace', C.c_void_p),
+        ('workspace_bytes', C.c_size_t), ('hip_stream', C.c_void_p),
+    ]
+
+
+class MeshAlignArgs(C.Structure):
+    """smplfit_mesh_align_args (include/smplfit.h)."""
+    _fields_ = [
+        ('align', C.c_int32), ('align_on', C.c_int32), ('vertex_weights', C.c_void_p), ('joint_weights', C.c_void_p),
+        ('mean_vertex_error', C.c_void_p), ('mean_joint_error', C.c_void_p), ('scale', C.c_void_p),
+        ('rotation', C.c_void_p), ('translation', C.c_void_p), ('joint_scale', C.c_void_p),
+        ('joint_rotation', C.c_void_p), ('joint_translation', C.c_void_p),
+    ]
+
+
+class AlignPointsArgs(C.Structure):
+    """smplfit_align_points_args (include/smplfit.h)."""
+    _fields_ = [
+        ('batch', C.c_int32), ('num_points', C.c_int32), ('source', C.c_void_p), ('target', C.c_void_p),
+        ('weights', C.c_void_p), ('align', C.c_int32), ('error', C.c_void_p), ('mean_error', C.c_void_p),
+        ('scale', C.c_void_p), ('rotation', C.c_void_p), ('translation', C.c_void_p), ('workspace', C.c_void_p),
         ('workspace_bytes', C.c_size_t), ('hip_stream', C.c_void_p),
     ]
 
@@ -501,6 +527,15 @@ def load():
         lib.smplfit_fit_robust_workspace_bytes.restype = sz
         lib.smplfit_fit_robust_f32.argtypes = [vp, C.POINTER(FitArgs), vp, C.POINTER(FitReconArgs), C.POINTER(FitRobustArgs)]
         lib.smplfit_fit_robust_f32.restype = i32
+    if hasattr(lib, 'smplfit_mesh_error_aligned_f32'):  # (as above)
+        lib.smplfit_mesh_error_aligned_workspace_bytes.argtypes = [vp, i32]
+        lib.smplfit_mesh_error_aligned_workspace_bytes.restype = sz
+        lib.smplfit_mesh_error_aligned_f32.argtypes = [vp, C.POINTER(MeshErrorArgs), C.POINTER(MeshAlignArgs)]
+        lib.smplfit_mesh_error_aligned_f32.restype = i32
+        lib.smplfit_align_points_workspace_bytes.argtypes = [i32, i32]
+        lib.smplfit_align_points_workspace_bytes.restype = sz
+        lib.smplfit_align_points_f32.argtypes = [C.POINTER(AlignPointsArgs)]
+        lib.smplfit_align_points_f32.restype = i32
     if os.environ.get('SMPLFIT_LIB') and not hasattr(lib, 'smplfit_abi_version'):
         _lib = lib  # an older build loaded by the A/B tools (tools/ab_fit.py): no version / share-table exports
         return lib
@@ -609,6 +644,9 @@ class Handle:
 
     def mesh_error_workspace_bytes(self, batch: int) -> int:
         return int(load().smplfit_mesh_error_workspace_bytes(self._h, int(batch)))
+
+    def mesh_error_aligned_workspace_bytes(self, batch: int) -> int:
+        return int(load().smplfit_mesh_error_aligned_workspace_bytes(self._h, int(batch)))
 
     def fit_recon_workspace_bytes(self, batch: int, plan: 'ShareSegments | None' = None) -> int:
         return int(load().smplfit_fit_recon_workspace_bytes(self._h, int(batch), plan.ptr if plan is not None else None))

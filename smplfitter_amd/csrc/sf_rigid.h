@@ -93,4 +93,71 @@ SF_HD void rototranslate_instance_backward(const float* j_ext, int S, const floa
   if (gkid) gkid[0] = kid ? (float)(j_ext[S] * gp[0] + j_ext[S1 + S] * gp[1] + j_ext[2 * S1 + S] * gp[2]) : 0.f;
 }
 
+// ---- Procrustes alignment of two weighted point sets from their moments -------------------------
+// The solve of smplfit_align_points_f32 / smplfit_mesh_error_aligned_f32 (k_align_solve, one lane per row) and of the
+// host emulation.  m: the kAlignMoments sums of a row over points taken about provisional origins ox / oy (x' = x - ox
+// the model, y' = y - oy the target), so that they hold body-sized numbers wherever the row lies:
+//   m[0] = W = sum w      m[1..3] = sum w x'      m[4..6] = sum w y'      m[7 + 3 r + c] = sum w y'_r x'_c
+//   m[16] = sum w |x'|^2
+// mode: kAlignTranslation (s = 1, R = I), kAlignRigid (R = proj_so3(K), K the centred cross-covariance: det +1 also
+// where the best orthogonal fit is a reflection), kAlignSimilarity (s = tr(R^T K) / sum w |x - xbar|^2).
+// Out, fp64: s, R (9), t (3) with y ~ s R x + t, and c (3) = ybar' - s R xbar' = t + s R ox - oy, the body-sized
+// offset of the centred form  s R (x - ox) + c - (y - oy)  the errors are evaluated in.
+// W not positive and finite, a similarity with no spread, or any non-finite moment: every output NaN.
+enum { kAlignNone = 0, kAlignRoot = 1, kAlignTranslation = 2, kAlignRigid = 3, kAlignSimilarity = 4, kAlignModeCount = 5 };
+enum { kAlignEach = 0, kAlignOnVertices = 1, kAlignOnJoints = 2, kAlignOnCount = 3 };
+constexpr int kAlignMoments = 17;
+constexpr int kAlignRecord = 18;  // floats of a row's record for the apply kernel: s R (9), c (3), ox (3), oy (3)
+
+SF_HD void align_solve(int mode, const double* m, const double* ox, const double* oy, double* s, double* R, double* t,
+                       double* c) {
+  const double W = m[0];
+  const double iw = 1.0 / W;
+  double xm[3], ym[3], K[9], kmax = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    xm[k] = m[1 + k] * iw;
+    ym[k] = m[4 + k] * iw;
+  }
+  for (int r = 0; r < 3; ++r)
+    for (int k = 0; k < 3; ++k) {
+      K[r * 3 + k] = m[7 + r * 3 + k] - W * ym[r] * xm[k];
+      kmax = fmax(kmax, fabs(K[r * 3 + k]));
+    }
+  const double var = m[16] - W * (xm[0] * xm[0] + xm[1] * xm[1] + xm[2] * xm[2]);
+  for (int k = 0; k < 9; ++k) R[k] = k % 4 == 0 ? 1.0 : 0.0;
+  *s = 1.0;
+  bool ok = W > 0.0;
+  if (mode >= kAlignRigid) {
+    // (the projection normalises its input: scaled to unit size first, so that the fp32 copy neither over- nor underflows)
+    float Kf[9], Rf[9];
+    const double ik = kmax > 0.0 ? 1.0 / kmax : 0.0;
+    for (int k = 0; k < 9; ++k) Kf[k] = (float)(K[k] * ik);
+    proj_so3(Kf, Rf);
+    for (int k = 0; k < 9; ++k) R[k] = (double)Rf[k];
+  }
+  if (mode == kAlignSimilarity) {
+    double tr = 0.0;
+    for (int k = 0; k < 9; ++k) tr += R[k] * K[k];
+    ok = ok && var > 0.0;
+    *s = tr / var;
+  }
+  double chk = *s;
+  for (int r = 0; r < 3; ++r) {
+    double rx = 0.0, ro = 0.0;
+    for (int k = 0; k < 3; ++k) {
+      rx += R[r * 3 + k] * xm[k];
+      ro += R[r * 3 + k] * (xm[k] + ox[k]);
+    }
+    c[r] = ym[r] - *s * rx;
+    t[r] = (ym[r] + oy[r]) - *s * ro;
+    chk += c[r] + t[r] + R[r * 3] + R[r * 3 + 1] + R[r * 3 + 2];
+  }
+  if (!ok || !(chk - chk == 0.0)) {  // (NaN or inf anywhere)
+    const double nan = __builtin_nan("");
+    *s = nan;
+    for (int k = 0; k < 9; ++k) R[k] = nan;
+    for (int k = 0; k < 3; ++k) t[k] = c[k] = nan;
+  }
+}
+
 }  // namespace sf

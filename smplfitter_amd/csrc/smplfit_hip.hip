@@ -500,6 +500,7 @@ __device__ __forceinline__ void st_stream(float* p, float v) {
 #include "kernels_adj.inc"
 #include "kernels_rigid.inc"
 #include "kernels_robust.inc"
+#include "kernels_align.inc"
 
 // ------------------------------------------------------------------------------------------------
 // launch helpers
@@ -4183,6 +4184,198 @@ int smplfit_fit_recon_f32(const smplfit_handle* h, const smplfit_fit_args* args,
   me.verr = recon->vertex_error;
   me.jerr = recon->joint_error;
   if (int rc = launch_mesh_error(h, route_of(h, B, {Entry::kForward}), me, ws, B, st)) return rc;
+  return post_launch_check();
+}
+
+// ---- aligned errors: Procrustes alignment of the model onto the targets, then the distances ----
+// A row-major point set of a call: x the model, y the target, w the weights or null
+struct AlignSet {
+  const float *x, *y, *w;
+  int n;
+};
+int align_nslab(int n) { return (n + kAlignSlab - 1) / kAlignSlab; }
+// What the launches of a (B, n, 3) set can address: the slabs of a row are grid.y of k_align_moments (at most 65535: n
+// up to 2^26 gives 32768), the points of the batch in blocks of 256 are grid.x of k_align_apply (below 2^31)
+constexpr int kAlignMaxPoints = 1 << 26;
+bool align_counts_ok(int B, int n) { return B > 0 && n > 0 && n <= kAlignMaxPoints && (size_t)B * (size_t)n <= ((size_t)1 << 38); }
+
+// STEP transform of a set: its moments and the solve (kAlignRoot: `set` is the joints; the moments give the row's
+// validity).  rec (B, kAlignRecord) is what launch_align_measure reads; scale / rot / trans: the caller's, each may be null.
+void launch_align_transform(const AlignSet& set, int mode, double* part, float* rec, float* scale, float* rot, float* trans, int B,
+                            hipStream_t st) {
+  const int nslab = align_nslab(set.n);
+  hipLaunchKernelGGL(k_align_moments, dim3(B, nslab), dim3(256), 0, st, set.x, set.y, set.w, set.n, B, part);
+  AlignSolveArgs sa{};
+  sa.part = part;
+  sa.x = set.x;
+  sa.y = set.y;
+  sa.n = set.n;
+  sa.nslab = nslab;
+  sa.B = B;
+  sa.mode = mode;
+  sa.rec = rec;
+  sa.scale = scale;
+  sa.rot = rot;
+  sa.trans = trans;
+  hipLaunchKernelGGL(k_align_solve, dim3((B + 63) / 64), dim3(64), 0, st, sa);
+}
+// STEP row means of (B, n) errors
+void launch_align_means(const float* err, const float* w, int n, float* mean, int B, hipStream_t st) {
+  hipLaunchKernelGGL(k_align_row_means, dim3((B + 3) / 4), dim3(256), 0, st, err, w, n, B, mean);
+}
+// STEP measure a set under the transform of `rec`: the errors (B, n), and their row means where asked for
+void launch_align_measure(const AlignSet& set, const float* rec, float* err, float* mean, int B, hipStream_t st) {
+  const size_t total = (size_t)B * set.n;
+  hipLaunchKernelGGL(k_align_apply, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, set.x, set.y, rec, err, set.n, total);
+  if (mean) launch_align_means(err, set.w, set.n, mean, B, st);
+}
+
+// LAYOUT alignment of two (B, n, 3) arrays: the slab moments, the rows' records, and the errors where only their means
+// are asked for
+struct AlignPointsLayout {
+  double* part;
+  float *rec, *err;
+};
+AlignPointsLayout align_points_layout(int B, int n, Arena& ar) {
+  AlignPointsLayout l;
+  l.part = ar.take<double>((size_t)align_nslab(n) * B * sf::kAlignMoments);
+  l.rec = ar.take<float>((size_t)B * sf::kAlignRecord);
+  l.err = ar.take<float>((size_t)B * n);
+  return l;
+}
+size_t smplfit_align_points_workspace_bytes(int batch, int num_points) {
+  if (!align_counts_ok(batch, num_points)) return 0;
+  Arena ar{nullptr};
+  align_points_layout(batch, num_points, ar);
+  return ar.off;
+}
+
+int smplfit_align_points_f32(const smplfit_align_points_args* a) {
+  const char* who = "smplfit_align_points_f32";
+  const auto bad = [who](const char* what) { return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  if (!a) return bad("null arguments");
+  if (a->batch <= 0) return bad("batch must be positive");
+  if (a->num_points < 1 || a->num_points > kAlignMaxPoints) return bad("num_points must lie in [1, 2^26]");
+  if (!align_counts_ok(a->batch, a->num_points)) return bad("batch * num_points must not exceed 2^38");
+  if (!a->source || !a->target) return bad("source and target are required");
+  if (a->align != SMPLFIT_ALIGN_TRANSLATION && a->align != SMPLFIT_ALIGN_RIGID && a->align != SMPLFIT_ALIGN_SIMILARITY)
+    return bad("align must be translation (2), rigid (3) or similarity (4)");
+  if (!a->error && !a->mean_error && !a->scale && !a->rotation && !a->translation) return bad("at least one output is required");
+  if (!a->workspace || ((uintptr_t)a->workspace & 255))
+    return fail(SMPLFIT_ERR_WORKSPACE, std::string(who) + ": workspace must be a 256-byte aligned device pointer");
+  if (a->workspace_bytes < smplfit_align_points_workspace_bytes(a->batch, a->num_points))
+    return fail(SMPLFIT_ERR_WORKSPACE, std::string(who) + ": workspace too small (see smplfit_align_points_workspace_bytes)");
+  hipStream_t st = (hipStream_t)a->hip_stream;
+  Arena ar{(char*)a->workspace};
+  const AlignPointsLayout l = align_points_layout(a->batch, a->num_points, ar);
+  const AlignSet set{a->source, a->target, a->weights, a->num_points};
+  launch_align_transform(set, a->align, l.part, l.rec, a->scale, a->rotation, a->translation, a->batch, st);
+  if (a->error || a->mean_error) launch_align_measure(set, l.rec, a->error ? a->error : l.err, a->mean_error, a->batch, st);
+  return post_launch_check();
+}
+
+// LAYOUT aligned mesh error: the mesh-error step's workspace, the slab moments and the records of the two sets, then
+// the mesh (B,V,3) and the errors (B,V) + (B,J), each only where the caller gave no buffer for it (own_*).  The query
+// has no call to look at and counts all three.
+struct MeshAlignLayout {
+  char* fit;
+  float *mesh, *verr, *jerr, *recv, *recj;
+  double *partv, *partj;
+};
+MeshAlignLayout mesh_align_layout(const smplfit_handle* h, int B, bool own_mesh, bool own_verr, bool own_jerr, Arena& ar) {
+  MeshAlignLayout l{};
+  const size_t V = h->t.V, J = h->t.J;
+  l.fit = ar.take<char>(smplfit_workspace_bytes(h, B));
+  l.partv = ar.take<double>((size_t)align_nslab((int)V) * B * sf::kAlignMoments);
+  l.partj = ar.take<double>((size_t)align_nslab((int)J) * B * sf::kAlignMoments);
+  l.recv = ar.take<float>((size_t)B * sf::kAlignRecord);
+  l.recj = ar.take<float>((size_t)B * sf::kAlignRecord);
+  if (own_mesh) l.mesh = ar.take<float>((size_t)B * V * 3);
+  if (own_verr) l.verr = ar.take<float>((size_t)B * V);
+  if (own_jerr) l.jerr = ar.take<float>((size_t)B * J);
+  return l;
+}
+size_t mesh_align_bytes(const smplfit_handle* h, int batch, bool own_mesh, bool own_verr, bool own_jerr) {
+  if (!h || batch <= 0) return 0;
+  Arena ar{nullptr};
+  mesh_align_layout(h, batch, own_mesh, own_verr, own_jerr, ar);
+  return ar.off;
+}
+size_t smplfit_mesh_error_aligned_workspace_bytes(const smplfit_handle* h, int batch) {
+  return mesh_align_bytes(h, batch, true, true, true);
+}
+
+int smplfit_mesh_error_aligned_f32(const smplfit_handle* h, const smplfit_mesh_error_args* a, const smplfit_mesh_align_args* al) {
+  const char* who = "smplfit_mesh_error_aligned_f32";
+  if (!al) return smplfit_mesh_error_f32(h, a);
+  const auto bad = [who](const char* what) { return fail(SMPLFIT_ERR_BAD_ARG, std::string(who) + ": " + what); };
+  if (!a) return bad("null arguments");
+  const int B = a->batch;
+  // (what the align struct asks for is checked first: these refusals need no device)
+  const int mode = al->align, on = al->align_on;
+  const float *tv = a->target_vertices, *tj = a->target_joints;
+  if (mode < 0 || mode >= sf::kAlignModeCount) return bad("unknown align (0 none, 1 root, 2 translation, 3 rigid, 4 similarity)");
+  if (on < 0 || on >= sf::kAlignOnCount) return bad("unknown align_on (0 each, 1 vertices, 2 joints)");
+  if (!tv) return bad("target_vertices is required");
+  if (mode == sf::kAlignRoot && !tj) return bad("align = root needs target_joints");
+  if (mode != sf::kAlignNone && on == sf::kAlignOnJoints && !tj) return bad("align_on = joints needs target_joints");
+  const bool xform_out = al->scale || al->rotation || al->translation;
+  const bool jxform_out = al->joint_scale || al->joint_rotation || al->joint_translation;
+  if (!tj && (a->joint_error || al->mean_joint_error || jxform_out || al->joint_weights))
+    return bad("joint_error, mean_joint_error, the joints' transform and joint_weights need target_joints");
+  if (!a->vertices && !a->joints && !a->vertex_error && !a->joint_error && !al->mean_vertex_error && !al->mean_joint_error &&
+      !xform_out && !jxform_out)
+    return bad("at least one output is required");
+  if (mode == sf::kAlignNone && (xform_out || jxform_out)) return bad("align = none has no transform to return");
+  const bool each = mode >= sf::kAlignTranslation && on == sf::kAlignEach;
+  if (jxform_out && !each) return bad("the joints' own transform exists with align_on = each alone (not with align = root)");
+  // (a region the caller's own buffer stands in for is not asked of the workspace)
+  const bool own_mesh = !a->vertices, own_verr = !a->vertex_error, own_jerr = !a->joint_error;
+  if (int rc = check_call(who, h, B, a->workspace, a->workspace_bytes, mesh_align_bytes(h, B, own_mesh, own_verr, own_jerr),
+                          "smplfit_mesh_error_aligned_workspace_bytes"))
+    return rc;
+  const DevModel& d = h->d;
+  const ForwardInputs in = forward_inputs(*a);
+  if (int rc = check_forward_inputs(who, d, in)) return rc;
+  hipStream_t st = (hipStream_t)a->hip_stream;
+  Arena ar{(char*)a->workspace};
+  const MeshAlignLayout l = mesh_align_layout(h, B, own_mesh, own_verr, own_jerr, ar);
+  const Workspace ws = fit_workspace(h, B, l.fit);
+  const Route r = route_of(h, B, {Entry::kForward});
+  MeshError me;
+  me.fa = forward_args(in, forward_nb(d, in), a->trans, a->joints ? a->joints : ws.rjoints, nullptr);
+  me.tv = tv;
+  me.tj = tj;
+  me.vertices = a->vertices;
+  const bool want_v = a->vertex_error || al->mean_vertex_error, want_j = a->joint_error || al->mean_joint_error;
+  float* verr = !want_v ? nullptr : a->vertex_error ? a->vertex_error : l.verr;
+  float* jerr = !want_j ? nullptr : a->joint_error ? a->joint_error : l.jerr;
+  if (mode == sf::kAlignNone) {  // the mesh-error step as it is, then the row means
+    me.verr = verr;
+    me.jerr = jerr;
+    if (int rc = launch_mesh_error(h, r, me, ws, B, st)) return rc;
+    if (al->mean_vertex_error) launch_align_means(verr, al->vertex_weights, d.V, al->mean_vertex_error, B, st);
+    if (al->mean_joint_error) launch_align_means(jerr, al->joint_weights, d.J, al->mean_joint_error, B, st);
+    return post_launch_check();
+  }
+  // which set gives the transform the vertices are measured under, and the joints
+  const bool from_joints = mode == sf::kAlignRoot || on == sf::kAlignOnJoints;
+  const bool solve_v = !from_joints && (want_v || xform_out || (on == sf::kAlignOnVertices && want_j));
+  const bool solve_j = from_joints ? (want_v || want_j || xform_out) : (each && (want_j || jxform_out));
+  launch_forward_joint(d, me.fa, ws, B, st);
+  const bool need_mesh = a->vertices || want_v || solve_v;
+  float* mesh = a->vertices ? a->vertices : l.mesh;
+  if (need_mesh)
+    if (int rc = launch_posed_pass(h, r, {nullptr, mesh_alone(&me.fa, mesh)}, ws, B, st)) return rc;
+  const AlignSet sv{mesh, tv, al->vertex_weights, d.V}, sj{me.fa.joints, tj, al->joint_weights, d.J};
+  if (solve_v) launch_align_transform(sv, mode, l.partv, l.recv, al->scale, al->rotation, al->translation, B, st);
+  if (solve_j) {
+    if (from_joints) launch_align_transform(sj, mode, l.partj, l.recj, al->scale, al->rotation, al->translation, B, st);
+    else launch_align_transform(sj, mode, l.partj, l.recj, al->joint_scale, al->joint_rotation, al->joint_translation, B, st);
+  }
+  // (a record holds the origins of the set it was solved on; the other set is measured about the same two points)
+  if (want_v) launch_align_measure(sv, from_joints ? l.recj : l.recv, verr, al->mean_vertex_error, B, st);
+  if (want_j) launch_align_measure(sj, (from_joints || each) ? l.recj : l.recv, jerr, al->mean_joint_error, B, st);
   return post_launch_check();
 }
 

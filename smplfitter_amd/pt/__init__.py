@@ -19,10 +19,11 @@ from .bodyconverter import BodyConverter
 from .bodyflipper import BodyFlipper
 from .bodyflipper_opt import BodyFlipperOpt
 from .handreplacer import HandReplacer
+from .align import align_points
 from . import ops  # noqa: F401  (registers torch.ops.smplfitter_amd.fit / .forward)
 
 __all__ = ['BodyModel', 'BodyFitter', 'BodyFitterOpt', 'BodyConverter', 'BodyFlipper', 'BodyFlipperOpt',
-           'HandReplacer', 'get_cached_body_model', 'get_cached_fit_fn']
+           'HandReplacer', 'align_points', 'get_cached_body_model', 'get_cached_fit_fn']
 
 
 @functools.lru_cache()

@@ -434,6 +434,10 @@ class BodyModel(nn.Module):
         rel_rotmats: Optional[torch.Tensor] = None,
         glob_rotmats: Optional[torch.Tensor] = None,
         return_mesh: bool = False,
+        align: str = 'none',
+        align_on: str = 'each',
+        vertex_weights: Optional[torch.Tensor] = None,
+        joint_weights: Optional[torch.Tensor] = None,
     ) -> dict[str, torch.Tensor]:
         """How far the model at the given parameters lies from target points (no counterpart in the reference; DESIGN.md
         §22): ``vertex_error`` (B, V), the Euclidean distance of every vertex of ``forward(...)`` to its row of
@@ -442,17 +446,156 @@ class BodyModel(nn.Module):
         (``smplfit_mesh_error_f32``): without ``return_mesh`` the mesh is measured where it is formed and never written
         as (B, V, 3) on the batch-major kernels.  The parameters are those of ``forward``; an empty batch returns empty
         tensors.  With gradients enabled and an input that requires grad, and under ``torch.compile``, the same keys
-        come from ``forward`` and PyTorch arithmetic, so they are differentiable like ``forward``."""
+        come from ``forward`` and PyTorch arithmetic, so they are differentiable like ``forward``.
+
+        ``align`` ('none', 'root', 'translation', 'rigid', 'similarity') moves the model onto the targets
+        before it is measured — 'root' joint 0 onto joint 0 (MPJPE), 'similarity' with ``align_on='each'`` the
+        Procrustes-aligned errors (PA-PVE, PA-MPJPE); ``align_on`` 'vertices' / 'joints' takes one transform from that
+        set for both.  ``vertex_weights`` (B, V) / ``joint_weights`` (B, J) steer the alignment and the row means, not
+        the per-point distances.  With an alignment or weights the call (``smplfit_mesh_error_aligned_f32``) also returns
+        ``mean_vertex_error`` (B,) (and ``mean_joint_error``), ``align_scale`` (B,), ``align_rotation`` (B, 3, 3),
+        ``align_translation`` (B, 3) — the vertices' transform, the joints' for ``align_on='joints'`` and 'root' — and
+        with ``align_on='each'`` and target joints ``joint_align_scale`` / ``_rotation`` / ``_translation``.  A row
+        without a transform (zero total weight, a non-finite point, ...) is NaN, no other row is.  ``vertices`` stay
+        ``forward``'s bits, unaligned."""
         keys = ['vertex_error'] + (['joint_error'] if target_joints is not None else [])
         if return_mesh:
             keys += ['vertices', 'joints']
         params = dict(pose_rotvecs=pose_rotvecs, shape_betas=shape_betas, trans=trans, kid_factor=kid_factor,
                       rel_rotmats=rel_rotmats, glob_rotmats=glob_rotmats)
-        ins = (target_vertices, target_joints, *params.values())
-        if torch.compiler.is_compiling() or (
-                torch.is_grad_enabled() and any(isinstance(a, torch.Tensor) and a.requires_grad for a in ins)):
+        if align not in _lib.ALIGN_MODES:
+            raise ValueError(f'align must be one of {tuple(_lib.ALIGN_MODES)}, got {align!r}')
+        if align_on not in _lib.ALIGN_ON:
+            raise ValueError(f'align_on must be one of {tuple(_lib.ALIGN_ON)}, got {align_on!r}')
+        aligned = align != 'none' or vertex_weights is not None or joint_weights is not None
+        ins = (target_vertices, target_joints, vertex_weights, joint_weights, *params.values())
+        composed = torch.compiler.is_compiling() or (
+            torch.is_grad_enabled() and any(isinstance(a, torch.Tensor) and a.requires_grad for a in ins))
+        if aligned:
+            fn = self._aligned_composed if composed else self._aligned_direct
+            return fn(keys, target_vertices, target_joints, align, align_on, vertex_weights, joint_weights, **params)
+        if composed:
             return self._recon_composed(keys, target_vertices, target_joints, **params)
         return self._recon_direct(keys, target_vertices, target_joints, **params)
+
+    def _check_align(self, keys, target_vertices, target_joints, align, align_on, vertex_weights, joint_weights):
+        """The checks of an aligned mesh-error call beyond the step's own (no device needed); returns the batch."""
+        batch = self._check_recon_targets(keys, target_vertices, target_joints)
+        if target_joints is None:
+            if align == 'root':
+                raise ValueError("align='root' needs target_joints")
+            if align_on == 'joints' and align != 'none':
+                raise ValueError("align_on='joints' needs target_joints")
+            if joint_weights is not None:
+                raise ValueError('joint_weights need target_joints')
+        for name, arg, n in (('vertex_weights', vertex_weights, self.num_vertices), ('joint_weights', joint_weights, self.num_joints)):
+            if arg is None:
+                continue
+            if not isinstance(arg, torch.Tensor):
+                raise TypeError(f"Expected torch.Tensor for '{name}', got {type(arg).__name__}.")
+            if tuple(arg.shape) != (batch, n):
+                raise ValueError(f'{name} must have shape ({batch}, {n}), got {tuple(arg.shape)}')
+        return batch
+
+    @staticmethod
+    def _align_keys(align, align_on, joints):
+        """(transform keys of the primary set, of the joints' own) an aligned call returns."""
+        names = ('scale', 'rotation', 'translation')
+        own = joints and align_on == 'each' and align in ('translation', 'rigid', 'similarity')
+        return [f'align_{n}' for n in names], [f'joint_align_{n}' for n in names] if own else []
+
+    def _aligned_composed(self, keys, target_vertices, target_joints, align, align_on, vertex_weights, joint_weights, **params):
+        """The keys of an aligned mesh-error call from ``forward`` and PyTorch arithmetic in fp64 (pt/align.py): the route
+        of calls that carry gradients or are being traced."""
+        from . import align as A
+
+        batch = self._check_align(keys, target_vertices, target_joints, align, align_on, vertex_weights, joint_weights)
+        fw = self.forward(**params, return_vertices=True)
+        dev = fw['vertices'].device
+        to = lambda a: None if a is None else a.to(dev)  # noqa: E731
+        tv, tj, vw, jw = to(target_vertices), to(target_joints), to(vertex_weights), to(joint_weights)
+        sets = dict(v=(fw['vertices'], tv, vw))
+        if tj is not None:
+            sets['j'] = (fw['joints'], tj, jw)
+        one, eye = torch.ones(batch, dtype=torch.float64, device=dev), torch.eye(3, dtype=torch.float64, device=dev).expand(batch, 3, 3)
+        if align == 'none':
+            xf = {k: (one, eye, torch.zeros(batch, 3, dtype=torch.float64, device=dev)) for k in sets}
+        elif align == 'root':
+            x0, y0, w = fw['joints'].to(torch.float64), tj.to(torch.float64), A.weighted_row_mean(tj[..., 0] * 0, jw)
+            ok = torch.isfinite(w + (x0.sum((1, 2)) + y0.sum((1, 2))) * 0)
+            nan = torch.full_like(one, float('nan'))
+            t = torch.where(ok[:, None], y0[:, 0] - x0[:, 0], nan[:, None])
+            xf = {k: (torch.where(ok, one, nan), torch.where(ok[:, None, None], eye, nan[:, None, None]), t) for k in sets}
+        else:
+            src = dict(each=None, vertices='v', joints='j')[align_on]
+            solved = {k: A.procrustes(*sets[k], align) for k in sets if src in (None, k)}
+            xf = {k: solved[src or k] for k in sets}
+        f32 = lambda a: a.to(torch.float32)  # noqa: E731
+        out = {}
+        if 'vertices' in keys:
+            out['vertices'], out['joints'] = fw['vertices'], fw['joints']
+        for k, name in (('v', 'vertex'), ('j', 'joint')):
+            if k in sets:
+                x, y, w = sets[k]
+                e = A.aligned_errors(x, y, *xf[k])
+                out[f'{name}_error'], out[f'mean_{name}_error'] = f32(e), f32(A.weighted_row_mean(e, w))
+        first, own = self._align_keys(align, align_on, tj is not None)
+        primary = xf['j'] if (align == 'root' or (align_on == 'joints' and align != 'none')) else xf['v']
+        out.update({k: f32(v) for k, v in zip(first, primary)})
+        out.update({k: f32(v) for k, v in zip(own, xf.get('j', ()))})
+        return out
+
+    def _aligned_direct(self, keys, target_vertices, target_joints, align, align_on, vertex_weights, joint_weights,
+                        pose_rotvecs=None, shape_betas=None, trans=None, kid_factor=None, rel_rotmats=None, glob_rotmats=None):
+        """The C-ABI call of the aligned mesh-error step (``smplfit_mesh_error_aligned_f32``)."""
+        self._check_forward_inputs(pose_rotvecs, shape_betas, trans, kid_factor, rel_rotmats, glob_rotmats)
+        batch = self._check_align(keys, target_vertices, target_joints, align, align_on, vertex_weights, joint_weights)
+        for name, arg in (('pose_rotvecs', pose_rotvecs), ('shape_betas', shape_betas), ('rel_rotmats', rel_rotmats),
+                          ('glob_rotmats', glob_rotmats)):
+            if arg is not None and arg.shape[0] != batch:
+                raise ValueError(f'{name} has {arg.shape[0]} rows, target_vertices {batch}')
+        if trans is not None and trans.shape[0] not in (1, batch):
+            raise ValueError(f'trans has {trans.shape[0]} rows, target_vertices {batch}')
+        device = self.v_template.device
+        J, V = self.num_joints, self.num_vertices
+        joints = target_joints is not None
+        first, own = self._align_keys(align, align_on, joints)
+        shapes = dict(vertices=(batch, V, 3), joints=(batch, J, 3), vertex_error=(batch, V), joint_error=(batch, J))
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=device)  # noqa: E731
+        out = {k: new(*shapes[k]) for k in _lib.RECON_KEYS if k in keys}
+        out['mean_vertex_error'] = new(batch)
+        if joints:
+            out['mean_joint_error'] = new(batch)
+        for names in (first, own):
+            if names:
+                out.update({names[0]: new(batch), names[1]: new(batch, 3, 3), names[2]: new(batch, 3)})
+        if align == 'none':  # (no transform to solve for: the identity)
+            out[first[0]].fill_(1.0)
+            out[first[1]].copy_(torch.eye(3, device=device))
+            out[first[2]].zero_()
+        if batch == 0:
+            return out
+        prep = lambda t: None if t is None else t.to(device=device, dtype=torch.float32).contiguous()  # noqa: E731
+        pose, glob, rel, betas, nb, tr, kid = self._prep_forward_inputs(batch, pose_rotvecs, shape_betas, trans, kid_factor,
+                                                                        rel_rotmats, glob_rotmats)
+        tv, tj, vw, jw = prep(target_vertices), prep(target_joints), prep(vertex_weights), prep(joint_weights)
+        h = self._native(device, kid=kid is not None)
+        ws = torch.empty(h.mesh_error_aligned_workspace_bytes(batch), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            args = _lib.MeshErrorArgs(
+                pose_rotvecs=p(pose), glob_rotmats=p(glob), rel_rotmats=p(rel), shape_betas=p(betas),
+                num_betas_given=nb, trans=p(tr), kid_factor=p(kid), batch=batch, target_vertices=p(tv),
+                target_joints=p(tj), **{k: p(out.get(k)) for k in _lib.RECON_KEYS}, workspace=ws.data_ptr(),
+                workspace_bytes=ws.numel(), hip_stream=stream)
+            xf = {} if align == 'none' else dict(zip(('scale', 'rotation', 'translation'), (p(out[k]) for k in first)))
+            xf.update(zip(('joint_scale', 'joint_rotation', 'joint_translation'), (p(out[k]) for k in own)))
+            al = _lib.MeshAlignArgs(
+                align=_lib.ALIGN_MODES[align], align_on=_lib.ALIGN_ON[align_on], vertex_weights=p(vw), joint_weights=p(jw),
+                mean_vertex_error=p(out['mean_vertex_error']), mean_joint_error=p(out.get('mean_joint_error')), **xf)
+            _lib.check(_lib.load().smplfit_mesh_error_aligned_f32(h.ptr, C.byref(args), C.byref(al)))
+        return out
 
     def _check_recon_targets(self, keys, target_vertices, target_joints):
         """The target checks of the mesh-error step (no device needed); returns the batch."""
